@@ -2,11 +2,19 @@
 
     python bench.py --gpus N --steps K --warmup W          (N>1: spawns its N ranks itself, or joins the world
                                                             torch.distributed.run started it in)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                             (+ every other record: see below)
 
 A "step" is one UBTeacherTrainer.run_step_full_semisup on one synthetic COCO-shaped batch
 (FCOS R50-FPN, 4 labeled + 4 unlabeled 1333x800 images per GPU, post-burn-in: teacher EMA,
 teacher forward + two-criteria pseudo-labelling, two student forwards, backward, SGD).
 Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps (no instrumentation inside them), writes the outputs
+if asked and prints the line.  --full adds what takes instrumentation or runs of its own: the tower
+conv / weight-gradient rooflines, clock and board power, the exclusive pass, the host probe, the f32
+and other-16-bit records, the Faster-RCNN, small-batch, ragged-canvas and hipGraph sub-records, the
+CPU baselines and the full-size parity checks.
 """
 import argparse
 import json
@@ -338,8 +346,13 @@ def set_amp_type(dtype):
 
 
 def _cpu_threads():
-    # stock torch CPU convolutions stop scaling (and can slow down) far below the thread count of a 128-core host
-    return max(1, min(os.cpu_count() or 1, 32))
+    # stock torch CPU convolutions stop scaling (and can slow down) far below the thread count of a 128-core host; never more threads
+    # than the CPUs this process may use (its affinity mask, an OMP_NUM_THREADS set for it)
+    n = min(len(os.sched_getaffinity(0)), 32)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def _synthetic_cpu_batch(label, unlabel):
@@ -815,11 +828,59 @@ def subrecord_child(kind, dtype, label, unlabel, steps, warmup, ragged=False, ti
         return {"error": repr(e)}
 
 
+DUMP_SAMPLE = 3000000      # elements kept of each parameter / gradient arena by dump_outputs (12 MB of float32)
+
+
+def dump_outputs(tr, total_loss, metrics, out_dir):
+    """What the timed path computed in its last step - what a caller of run_step_full_semisup receives - as out_dir/<name>.npy:
+    total_loss (the returned objective) and every loss term of its record (float64 scalars); the gradient arena its backward filled
+    (student_grad) and the student / teacher arenas after its SGD / EMA updates (student_params, teacher_params): a fixed sample of
+    DUMP_SAMPLE elements each, the same positions in every run (numpy seed 0), float32; the teacher's pseudo-label sets of that step
+    (pseudo[_cls|_reg]_<field>: boxes, scores, classes, valid, ...; slots that hold no box are zeroed), float32 / float64 for integers.
+    About 37 MB in all at the default sizes.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {} if total_loss is None else {"total_loss": np.asarray(float(total_loss), dtype=np.float64)}
+    for k in sorted(metrics or {}):
+        if k.startswith("loss"):
+            out[k] = np.asarray(metrics[k], dtype=np.float64)
+    for name, flat in (("student_grad", tr.model.store.grad), ("student_params", tr.model.flat_state()),
+                       ("teacher_params", tr.model_teacher.flat_state())):
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[name] = flat.detach().float().cpu().numpy()
+    lp = getattr(tr, "_last_pseudo", None)
+    sets = [] if lp is None else (list(zip(("pseudo_cls", "pseudo_reg"), lp)) if isinstance(lp, tuple) else [("pseudo", lp)])
+    for prefix, pb in sets:
+        valid = pb.f["valid"]
+        for k in sorted(pb.f):
+            v = pb.f[k]
+            if not torch.is_tensor(v):
+                continue
+            v = v.detach().float() if v.is_floating_point() else v.detach().double()
+            if k != "valid" and v.dim() >= 2 and tuple(v.shape[:2]) == tuple(valid.shape):
+                keep = valid.bool().reshape(tuple(valid.shape) + (1,) * (v.dim() - 2))
+                v = torch.where(keep, v, torch.zeros((), dtype=v.dtype, device=v.device))
+            out["%s_%s" % (prefix, k)] = v.cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)       # BASELINE.md protocol: 10 warm-up + >= 50 timed steps
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines / clock / board power of the timed steps, the exclusive pass, the host probe, the "
+                         "f32 / other-16-bit, Faster-RCNN, small-batch, ragged-canvas and hipGraph sub-records, the CPU baselines and the "
+                         "full-size parity checks (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, gradient / parameter arena samples, pseudo "
+                         "labels) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--label", type=int, default=4, help="labeled images per GPU")
     ap.add_argument("--unlabel", type=int, default=4, help="unlabeled images per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -916,17 +977,20 @@ def worker(args):
         t.optimizer.param_groups[0]["lr"] = 1e-12
         return t
 
-    timer = ConvTimer(args.dtype)
-    timer.install()
-    wtimer = WgradTimer()
-    wtimer.install()
-    calls = CallCounter()
-    calls.install()
+    full = args.full
+    timer = wtimer = calls = None
+    if full:     # per-launch event timing of the dominant kernels and a count of the C-ABI calls, inside the timed steps
+        timer = ConvTimer(args.dtype)
+        timer.install()
+        wtimer = WgradTimer()
+        wtimer.install()
+        calls = CallCounter()
+        calls.install()
     tr = make_trainer(args.dtype)
     batch = tr._data_loader.batches[0]
     (tune_rcnn_for_pseudo_labels if rcnn else tune_for_pseudo_labels)(tr, batch)
     tr.sync_replicas()   # identical students / teachers on every rank (DDP broadcasts rank 0's parameters at construction)
-    parity = rank == 0 and world == 1 and args.dtype != "f32" and not args.no_f32 and not rcnn
+    parity = full and rank == 0 and world == 1 and args.dtype != "f32" and not args.no_f32 and not rcnn
     if parity:
         s0, t0 = tr.model.flat_state().clone(), tr.model_teacher.flat_state().clone()
     def pseudo_counts(t):
@@ -955,34 +1019,38 @@ def worker(args):
     gsync = getattr(tr, "_grad_sync", None)
     if gsync is not None:
         gsync.timing = True          # per-step exposure of the gradient all-reduce (what backward did not hide)
-    timer.enabled = wtimer.enabled = True
-    n0 = calls.n
-    power = BoardPower() if rank == 0 else None
+    n0 = 0
+    if full:
+        timer.enabled = wtimer.enabled = True
+        n0 = calls.n
+    power = BoardPower() if full and rank == 0 else None
     if power is not None:
         power.start()
     from ubteacher.engine.step_gc import StepGC
+    total_loss = None
     with StepGC() as step_gc:               # the collector policy of the product's own train_loop (engine/step_gc.py)
         sync()
         t0_ = time.perf_counter()
         for _ in range(args.steps):
-            tr.run_step_full_semisup(); tr.iter += 1
+            total_loss = tr.run_step_full_semisup(); tr.iter += 1
             step_gc.tick()
         t_host = time.perf_counter() - t0_      # the host has enqueued every step (it runs ahead of the GPU)
         sync()
         dt = time.perf_counter() - t0_
     board_power = power.stop() if power is not None else None
-    timer.enabled = wtimer.enabled = False
+    if full:
+        timer.enabled = wtimer.enabled = False
     # shader clock the chip sustained under the last multi-level (tower / RPN head) launch of the 256-tile conv kernel inside the timed
     # region (utv2_conv_clock_probe: s_memtime against the 100 MHz real-time counter over workgroup 0's lifetime)
     clock_ghz = None
-    if args.dtype != "f32":
+    if full and args.dtype != "f32":
         try:
             from ubteacher import hip as _hip
             g, us = _hip.conv_clock_probe()
             clock_ghz = {"ghz": g, "workgroup_lifetime_us": us} if g > 0 else None
         except Exception as e:  # noqa: BLE001
             clock_ghz = {"error": repr(e)}
-    calls_per_step = (calls.n - n0) / max(args.steps, 1)
+    calls_per_step = (calls.n - n0) / max(args.steps, 1) if full else None
     devices = [device_index]
     if world > 1:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -1011,13 +1079,18 @@ def worker(args):
     metrics = tr.flush_metrics()
     amp_state = tr._amp_state.cpu().tolist() if getattr(tr, "_amp_state", None) is not None else None
     pseudo_count = pseudo_counts(tr)
-    conv, wg = timer.summary(), wtimer.summary()
-    conv_gnb = timer.summary(gnb=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before anything else runs on this trainer
+        dumped = dump_outputs(tr, total_loss, metrics, args.dump_outputs)
+    conv = wg = conv_gnb = None
+    if full:
+        conv, wg = timer.summary(), wtimer.summary()
+        conv_gnb = timer.summary(gnb=True)
 
     # the same launches with the step's side streams off (teacher pass / weight gradients back on the main stream): the dominant kernels
     # alone on the GPU.  Not part of the timed region - reported beside the in-step figures as `exclusive`.
     conv_x = wg_x = conv_gnb_x = None
-    if rank == 0 and world == 1 and args.dtype != "f32" and not args.timed_only:
+    if full and rank == 0 and world == 1 and args.dtype != "f32" and not args.timed_only:
         saved = {k: os.environ.get(k) for k in ("UTV2_OVERLAP_TEACHER", "UTV2_WGRAD_STREAM")}
         os.environ["UTV2_OVERLAP_TEACHER"] = os.environ["UTV2_WGRAD_STREAM"] = "0"
         ot = getattr(tr, "overlap_teacher", None)
@@ -1040,7 +1113,7 @@ def worker(args):
                 os.environ[k] = v
 
     host_ms = None
-    if rank == 0 and world == 1 and not args.timed_only:
+    if full and rank == 0 and world == 1 and not args.timed_only:
         # host cost of one step: the same trainer code on 96 x 128 images, where the GPU work is negligible and the step time IS the
         # Python / launch overhead (on the 1333 x 800 batch the host runs ahead until the launch queue is full, so its enqueue time
         # only mirrors the GPU time)
@@ -1131,7 +1204,7 @@ def worker(args):
             ops.set_precision("bf16")
 
     rcnn_rec = None
-    if rank == 0 and world == 1 and not rcnn and not args.no_rcnn and not args.timed_only and args.dtype != "f32":
+    if full and rank == 0 and world == 1 and not rcnn and not args.no_rcnn and not args.timed_only and args.dtype != "f32":
         # the Faster-RCNN UTv2 trainer (BASELINE configs[2] / [4]: bf16 MFMA conv path) on the same per-GPU batch, as a sub-record
         args_r = argparse.Namespace(**vars(args)); args_r.model = "rcnn"
         timer_bf = ConvTimer("bf16")               # the sub-record's own 16-bit type (the headline's timer carries the headline's kernel name)
@@ -1158,7 +1231,7 @@ def worker(args):
             rcnn_rec["first_step_vs_f32"] = {"error": repr(e)}
 
     small_rec = ragged_rec = None
-    if rank == 0 and world == 1 and not args.timed_only and args.dtype != "f32" and not args.no_small and (args.label, args.unlabel) == (4, 4):
+    if full and rank == 0 and world == 1 and not args.timed_only and args.dtype != "f32" and not args.no_small and (args.label, args.unlabel) == (4, 4):
         # 2 + 2 images per GPU: the per-GPU workload of configs[2] / [4] (16 + 16 over 8 GPUs) and of the reference's FCOS recipe - the
         # size at which launch overheads and the host weigh twice as much per image as at 4 + 4
         small_rec = {}
@@ -1174,7 +1247,7 @@ def worker(args):
             rcnn_rec["ragged_canvases"] = subrecord_child("rcnn", "bf16", args.label, args.unlabel, 24, 16, ragged=True)
 
     graph_rec = None
-    if rank == 0 and world == 1 and not args.timed_only and args.dtype != "f32" and not args.no_graph:
+    if full and rank == 0 and world == 1 and not args.timed_only and args.dtype != "f32" and not args.no_graph:
         # the same step as ONE hipGraph launch (engine.trainer.run_step_graph): last, on a fresh trainer, so that a failed capture cannot
         # disturb any other measurement.  host_ms = what the host spends per step inside hipGraphLaunch (on this ROCm stack the runtime
         # enqueues the ~490 kernel nodes one by one on the host: measured 17 ms per step, MORE than the eager step's 10 ms of Python)
@@ -1208,7 +1281,7 @@ def worker(args):
     # work per 26 ms step), measured 277-282 img/s behind them and 305-308 without (same box, same process otherwise).  Each baseline
     # is a child process; a failure is reported in its record and cannot lose the GPU numbers, which are complete at this point.  The
     # children dump their first oracle step, which the parity checks below replay through the product's exact-f32 step.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # in its own process
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # in its own process
         import tempfile
         if not rcnn:
             dump = os.path.join(tempfile.gettempdir(), "utv2_bench_parity_%d.pt" % os.getpid())
@@ -1270,11 +1343,14 @@ def worker(args):
             "ranks": {"world_size": world, "backend": info["backend"], "devices": devices,
                       "launcher": _launcher_name(world), "rccl_selfcheck": rccl, "replicas": replicas, "allreduce": allreduce},
             "host": {"ms_per_step_on_96x128_images": host_ms, "enqueue_ms_per_step": 1e3 * t_host / args.steps,
-                     "cabi_calls_per_step": calls_per_step, "gpu_dispatches": dispatches_per_step(args.model) if args.dtype != "f32" else None},
+                     "cabi_calls_per_step": calls_per_step, "gpu_dispatches": dispatches_per_step(args.model) if full and args.dtype != "f32" else None},
             "losses": {k: v for k, v in metrics.items() if k.startswith("loss") or k.startswith("teacher")},
             "pseudo_boxes_first_step": pseudo_first, "pseudo_boxes_last_step": pseudo_count,
             "learning_rate": "1e-12 (keeps the synthetic pseudo-label problem stationary over the timed window; the step's work does not depend on it)",
+            "full": full,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if amp_state is not None:
             out["loss_scale_state"] = dict(zip(("scale", "found_inf", "clean_steps"), amp_state))
         if conv:

@@ -1,16 +1,31 @@
 """Config surface: our flattened presets must resolve to exactly the values of the reference's
-eight shipped YAMLs (checked in the build container, where /root/reference exists), and the
+eight shipped YAMLs (tests/golden/reference_configs.json: each YAML and the base file it names, as
+parsed mappings - written back to YAML files and merged through `_BASE_` here), and the
 yacs-like node must behave (unknown keys rejected, tuple decoding, freeze)."""
 import glob
+import json
 import os
 
 import pytest
+import yaml
 
 from ubteacher import add_ubteacher_config
 from ubteacher.d2 import get_cfg
 from ubteacher.presets import get_config
 
-REF = "/root/reference/configs"
+GOLDEN_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs.json")
+
+
+def _write_reference_configs(root):
+    """the stored YAMLs as files under `root`, at their paths under the reference's configs/ (so `_BASE_` resolves as it does there)"""
+    with open(GOLDEN_CONFIGS) as f:
+        files = json.load(f)
+    for rel, body in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            yaml.safe_dump(body, f)
+    return str(root)
 
 
 def _flat(node, prefix=""):
@@ -23,14 +38,14 @@ def _flat(node, prefix=""):
     return out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("family,sub,pat", [("fcos", "FCOS", "fcos_R_50_ut2_sup%d_run0.yaml"),
                                              ("rcnn", "Faster-RCNN", "faster_rcnn_R_50_FPN_ut2_sup%d_run0.yaml")])
 @pytest.mark.parametrize("sup", [1, 2, 5, 10])
-def test_presets_equal_reference_yaml(family, sub, pat, sup):
+def test_presets_equal_reference_yaml(family, sub, pat, sup, tmp_path):
+    configs = _write_reference_configs(tmp_path)
     ref = get_cfg()
     add_ubteacher_config(ref)
-    ref.merge_from_file(os.path.join(REF, sub, "coco-standard", pat % sup))
+    ref.merge_from_file(os.path.join(configs, sub, "coco-standard", pat % sup))
     mine = get_config(family, sup)
     a, b = _flat(ref), _flat(mine)
     assert set(a) == set(b)

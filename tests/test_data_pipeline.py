@@ -45,13 +45,13 @@ def test_divide_label_unlabel_matches_reference():
         divide_label_unlabel(dicts[:40], 10.0, 0, path)
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/dataseed/COCO_supervision.txt"), reason="the shipped seed table is not in this tree")
 def test_divide_label_unlabel_on_the_shipped_seed_table():
+    """the splits of dataseed/COCO_supervision.txt the goldens name, from the table's own lists for them (coco_supervision_subset.json)"""
     from ubteacher.data import divide_label_unlabel
     dicts = list(range(117266))
     for key, want in GOLD["divide_coco"].items():
         pct, seed = key.split("_")
-        lab, unl = divide_label_unlabel(dicts, float(pct), int(seed), "/root/reference/dataseed/COCO_supervision.txt")
+        lab, unl = divide_label_unlabel(dicts, float(pct), int(seed), os.path.join(G, "coco_supervision_subset.json"))
         assert (len(lab), len(unl), int(np.sum(lab)), lab[:8], unl[:8]) == (want["n_label"], want["n_unlabel"], want["label_sum"],
                                                                             want["label_head"], want["unlabel_head"])
 

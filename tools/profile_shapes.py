@@ -141,7 +141,7 @@ def main():
             if k == "enabled":
                 enabled[0] = bool(v)
     bench.ConvTimer = T
-    sys.argv = ["bench.py", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--no-f32", "--no-rcnn", "--timed-only"] + argv
+    sys.argv = ["bench.py", "--full", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--no-f32", "--no-rcnn", "--timed-only"] + argv
     out = sys.stdout
     sys.stdout = sys.stderr            # the bench's JSON line goes to stderr; the table alone to stdout
     bench.main()
