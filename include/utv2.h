@@ -530,6 +530,32 @@ int utv2_aug_erase_u8(unsigned char* img, int H, int W, int i, int j, int h, int
 /* dataset_mapper.py:139-147 image_strong_aug.transpose(2, 0, 1) */
 int utv2_aug_hwc_to_chw_u8(const unsigned char* src, unsigned char* dst, int64_t npix, utv2_stream_t stream);
 
+/* ---- COCO box evaluation (evaluation/coco_eval_device.py; the metric of Detectron2's COCOEvaluator behind the reference's
+ * build_evaluator), bit-identical to evaluation/coco_eval.py.  Detections / ground truth are CSR by image (off: device int64[N+1]) in the
+ * evaluator's image order; an (image, class) pair has the id image * (K + 1) + class, class K standing for every class outside [0, K).
+ * ubteacher/hip.py:coco_box_eval chains these with three stable sorts (torch.sort) of the keys - see csrc/coco_eval.hip. */
+/* keys[i] = pid << 32 | descending-score bits of scores[i] (scores NULL: 0) */
+int utv2_coco_pair_keys(const float* scores, const int* cls, const long long* off, int N, int K, long long* keys, utv2_stream_t stream);
+/* keys ascending: off[s] = first i with (keys[i] >> 32) >= s for s in [0, nseg] (ids above nseg count as nseg) */
+int utv2_coco_seg_offsets(const long long* keys, int64_t n, int64_t nseg, long long* off, utv2_stream_t stream);
+/* key1 sorted, pair_off its pair offsets: key2[p] = class << 32 | score bits when the class is < K and the rank of p inside its pair is
+ * < max_dets (else K << 32), rank[p] = that rank (255 when excluded); max_dets <= 254 */
+int utv2_coco_rank_keys(const long long* key1, const long long* pair_off, int64_t D, int K, int max_dets, long long* key2,
+                        unsigned char* rank, utv2_stream_t stream);
+/* the matched / ignored bits of every (sorted detection, area, IoU threshold) + the non-ignored ground-truth counts per (class, area),
+ * written by utv2_coco_match into ws and read by utv2_coco_accumulate */
+int64_t utv2_coco_eval_workspace_bytes(int64_t D, int K);
+/* dbox fp32 [D][4] xyxy, dperm: sorted position -> detection; gbox fp64 [G][4], gcrowd uint8, garea fp64 (NULL: box areas), gperm: sorted
+ * position -> ground truth; *_pair_off int64[N*(K+1)+1].  max_gt >= the ground-truth count of any pair (<= 12800);
+ * iou_thrs_host[10], area_rng_host[4][2] (lo, hi of all / small / medium / large) */
+int utv2_coco_match(const float* dbox, const long long* dperm, const long long* dpair_off, const double* gbox, const unsigned char* gcrowd,
+                    const double* garea, const long long* gperm, const long long* gpair_off, int N, int K, int64_t D, int max_dets,
+                    int max_gt, const double* iou_thrs_host, const double* area_rng_host, void* ws, utv2_stream_t stream);
+/* perm2: position in the class-merged order -> sorted position; cat_off int64[K+1]; rec_thrs_host[101].
+ * precision fp64 [10][101][K][4], recall fp64 [10][K][4][3] (maxDets 1, 10, max_dets); -1 where the class has no ground truth */
+int utv2_coco_accumulate(const long long* perm2, const long long* cat_off, const unsigned char* rank, int K, int64_t D,
+                         const double* rec_thrs_host, const void* ws, double* precision, double* recall, utv2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -628,6 +628,11 @@ class _TrainerBase:
         from ..evaluation import COCOBoxEvaluator
         rcnn = cfg.SEMISUPNET.Trainer == "ubteacher_rcnn"
         nc = cfg.MODEL.ROI_HEADS.NUM_CLASSES if rcnn else cfg.MODEL.FCOS.NUM_CLASSES
+        if cfg.TEST.EVALUATOR == "COCOeval_device":
+            # opt-in: the whole split scored by the HIP kernels (evaluation/coco_eval_device.py); every other value - the reference's
+            # build_evaluator maps them all to COCOEvaluator - keeps the host evaluator
+            from ..evaluation import DeviceCOCOBoxEvaluator
+            return DeviceCOCOBoxEvaluator(nc, dataset_name=dataset_name if DatasetCatalog.available(dataset_name) else None)
         return COCOBoxEvaluator(nc, dataset_name=dataset_name if DatasetCatalog.available(dataset_name) else None)
 
     @classmethod

@@ -190,3 +190,96 @@ class COCOBoxEvaluator:
                 pred.update(p)
                 gt.update(g)
         return {"bbox": coco_box_ap(pred, gt, self.num_classes)}
+
+
+AREA_NAMES = ("all", "small", "medium", "large")
+RECALL_MAX_DETS = (1, 10, MAX_DETS)
+
+
+def coco_box_eval(predictions, ground_truth, num_classes):
+    """coco_box_ap's protocol over the classes 0 .. num_classes - 1, keeping the arrays pycocotools' accumulate keeps:
+    precision [T=10, R=101, K, A=4] (area order AREA_NAMES) and recall [T, K, A, 3] (maxDets 1, 10, 100: pycocotools' rc[-1], where at
+    maxDets 1 / 10 only the first 1 / 10 detections of every (image, category) pair count), -1 where a class has no non-ignored ground
+    truth.  Returns (precision, recall, summarize(precision, recall)); the six AP numbers equal coco_box_ap's bit for bit (the classes
+    coco_box_ap leaves out have no ground truth, so they only add -1 entries, which the means skip)."""
+    K = int(num_classes)
+    T, R, A = len(IOU_THRS), len(REC_THRS), len(AREA_NAMES)
+    precision = -np.ones((T, R, K, A))
+    recall = -np.ones((T, K, A, len(RECALL_MAX_DETS)))
+    images = []
+    for img, g in ground_truth.items():
+        gb = np.asarray(g["boxes"], float).reshape(-1, 4)
+        gc = np.asarray(g["classes"]).reshape(-1)
+        gcrowd = np.asarray(g.get("iscrowd", np.zeros(len(gc))), bool).reshape(-1)
+        gar = np.asarray(g["area"], float).reshape(-1) if g.get("area") is not None else None
+        p = predictions.get(img)
+        if p is not None and len(np.asarray(p["classes"]).reshape(-1)):
+            pc = np.asarray(p["classes"]).reshape(-1)
+            pb = np.asarray(p["boxes"], float).reshape(-1, 4)
+            ps = np.asarray(p["scores"], float).reshape(-1)
+        else:
+            pc, pb, ps = np.zeros(0, np.int64), np.zeros((0, 4)), np.zeros(0)
+        images.append((gb, gc, gcrowd, gar, pc, pb, ps))
+    for c in range(K):
+        for ai, aname in enumerate(AREA_NAMES):
+            rng = AREA_RNG[aname]
+            sc_all, dm_all, di_all, rk_all, npig = [], [], [], [], 0
+            for gb, gc, gcrowd, gar, pc, pb, ps in images:
+                sel, psel = gc == c, pc == c
+                if not sel.any() and not psel.any():
+                    continue
+                s, dm, di, n = _evaluate_image(pb[psel], ps[psel], gb[sel], gcrowd[sel], rng, None if gar is None else gar[sel])
+                sc_all.append(s); dm_all.append(dm); di_all.append(di); rk_all.append(np.arange(len(s))); npig += n
+            if npig == 0:
+                continue
+            scores = np.concatenate(sc_all) if sc_all else np.zeros(0)
+            order = np.argsort(-scores, kind="mergesort")
+            dm = np.concatenate(dm_all, axis=1)[:, order] if dm_all else np.zeros((T, 0), bool)
+            di = np.concatenate(di_all, axis=1)[:, order] if di_all else np.zeros((T, 0), bool)
+            rk = np.concatenate(rk_all)[order] if rk_all else np.zeros(0, np.int64)
+            tps = np.cumsum(dm & ~di, axis=1).astype(float)
+            fps = np.cumsum(~dm & ~di, axis=1).astype(float)
+            for mi, m in enumerate(RECALL_MAX_DETS):
+                tp_m = (dm & ~di)[:, rk < m].sum(axis=1).astype(float)
+                recall[:, c, ai, mi] = tp_m / npig
+            for ti in range(T):
+                tp, fp = tps[ti], fps[ti]
+                rc = tp / npig
+                pr = tp / np.maximum(tp + fp, np.spacing(1))
+                for i in range(len(pr) - 1, 0, -1):  # monotone envelope
+                    if pr[i] > pr[i - 1]:
+                        pr[i - 1] = pr[i]
+                inds = np.searchsorted(rc, REC_THRS, side="left")
+                q = np.zeros(R)
+                ok = inds < len(pr)
+                q[ok] = pr[inds[ok]]
+                precision[ti, :, c, ai] = q
+    return precision, recall, summarize(precision, recall)
+
+
+def summarize(precision, recall, class_names=None):
+    """The `bbox` dict of Detectron2's COCOEvaluator from the accumulated arrays: coco_box_ap's six numbers (same numpy expressions, so
+    the same bits), pycocotools' AR1 / AR10 / AR100 / ARs / ARm / ARl (mean of recall > -1, times 100; the size splits at maxDets 100)
+    and `AP-<class name>` per class (area "all", maxDets 100; NaN for a class without ground truth).  class_names: one per class of
+    the arrays (None: the class index)."""
+    def mean_ap(ai, ti=None):
+        p = precision[..., ai] if ti is None else precision[ti:ti + 1, ..., ai]
+        p = p[p > -1]
+        return float(p.mean() * 100.0) if p.size else -1.0
+
+    def mean_ar(ai, mi):
+        r = recall[:, :, ai, mi]
+        r = r[r > -1]
+        return float(r.mean() * 100.0) if r.size else -1.0
+
+    res = {"AP": mean_ap(0), "AP50": mean_ap(0, 0), "AP75": mean_ap(0, 5), "APs": mean_ap(1), "APm": mean_ap(2), "APl": mean_ap(3),
+           "AR1": mean_ar(0, 0), "AR10": mean_ar(0, 1), "AR100": mean_ar(0, 2), "ARs": mean_ar(1, 2), "ARm": mean_ar(2, 2),
+           "ARl": mean_ar(3, 2)}
+    K = precision.shape[2]
+    names = list(class_names) if class_names is not None else [str(k) for k in range(K)]
+    assert len(names) == K, (len(names), K)
+    for k, name in enumerate(names):
+        p = precision[:, :, k, 0]
+        p = p[p > -1]
+        res["AP-{}".format(name)] = float(p.mean() * 100.0) if p.size else float("nan")
+    return res

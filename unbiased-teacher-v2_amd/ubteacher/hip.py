@@ -73,7 +73,8 @@ def _parse_header(path):
 
 _SIGS = _parse_header(HEADER_PATH)
 _PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats", "utv2_groupnorm_workspace_floats",
-          "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending"}  # return a value, not a status
+          "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
+          "utv2_coco_eval_workspace_bytes"}  # return a value, not a status
 
 
 _libs = {}
@@ -1437,3 +1438,61 @@ def aug_to_chw(img):
     out = torch.empty((3, img.shape[0], img.shape[1]), dtype=torch.uint8, device=img.device)
     call("utv2_aug_hwc_to_chw_u8", _p(img), _p(out), img.shape[0] * img.shape[1], _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# COCO box evaluation (evaluation/coco_eval_device.py)
+def _dbl_arr(vals):
+    return (ctypes.c_double * len(vals))(*[float(v) for v in vals])
+
+
+def coco_box_eval(det_boxes, det_scores, det_cls, det_off, gt_boxes, gt_crowd, gt_area, gt_cls, gt_off, num_classes, max_gt,
+                  iou_thrs, rec_thrs, area_rngs, max_dets=100):
+    """precision fp64 [10, 101, K, 4] and recall fp64 [10, K, 4, 3] of evaluation/coco_eval.py:coco_box_eval on the device.
+    Detections (boxes fp32 [D, 4] xyxy, scores fp32 [D], classes int32 [D]) and ground truth (boxes fp64 [G, 4], crowd uint8 [G], area fp64
+    [G] or None = box areas, classes int32 [G]) are CSR by image: det_off / gt_off int64 [N + 1], in the evaluator's image order.
+    max_gt: host-known bound of the ground-truth boxes of one image.  iou_thrs / rec_thrs / area_rngs: the host's fp64 values (numpy's
+    linspace, not i / 100).  Three stable sorts (torch.sort) order the int64 keys the kernels write; nothing synchronises."""
+    K = int(num_classes)
+    N = det_off.numel() - 1
+    assert N >= 1 and gt_off.numel() == N + 1 and K >= 1
+    assert len(iou_thrs) == 10 and len(rec_thrs) == 101 and len(area_rngs) == 4 and 1 <= max_dets <= 100
+    assert det_boxes.dtype == torch.float32 and det_scores.dtype == torch.float32 and det_cls.dtype == torch.int32
+    assert gt_boxes.dtype == torch.float64 and gt_crowd.dtype == torch.uint8 and gt_cls.dtype == torch.int32
+    assert gt_area is None or gt_area.dtype == torch.float64
+    assert det_off.dtype == torch.int64 and gt_off.dtype == torch.int64
+    dev = det_off.device
+    D, G = det_scores.numel(), gt_cls.numel()
+    npair = N * (K + 1)
+    if npair >= 1 << 31:
+        raise ValueError("coco_box_eval: %d images x %d classes exceed the pair-id range" % (N, K))
+    i64 = dict(dtype=torch.int64, device=dev)
+    st = _stream()
+
+    def sorted_pairs(scores, cls, off, n):
+        keys = torch.empty(n, **i64)
+        if n:
+            call("utv2_coco_pair_keys", _p(scores) if scores is not None else None, _p(cls), _p(off), N, K, _p(keys), st)
+        keys, perm = torch.sort(keys, stable=True)
+        poff = torch.empty(npair + 1, **i64)
+        call("utv2_coco_seg_offsets", _p(keys), n, npair, _p(poff), st)
+        return keys, perm, poff
+
+    key1, dperm, dpoff = sorted_pairs(det_scores, det_cls, det_off, D)
+    _, gperm, gpoff = sorted_pairs(None, gt_cls, gt_off, G)
+    key2 = torch.empty(D, **i64)
+    rank = torch.empty(D, dtype=torch.uint8, device=dev)
+    call("utv2_coco_rank_keys", _p(key1), _p(dpoff), D, K, int(max_dets), _p(key2), _p(rank), st)
+    key2, perm2 = torch.sort(key2, stable=True)
+    cat_off = torch.empty(K + 1, **i64)
+    call("utv2_coco_seg_offsets", _p(key2), D, K, _p(cat_off), st)
+    ws = torch.empty(int(load().utv2_coco_eval_workspace_bytes(D, K)), dtype=torch.uint8, device=dev)
+    area_flat = [v for lo_hi in area_rngs for v in lo_hi]
+    call("utv2_coco_match", _p(det_boxes), _p(dperm), _p(dpoff), _p(gt_boxes), _p(gt_crowd), _p(gt_area) if gt_area is not None else None,
+         _p(gperm), _p(gpoff), N, K, D, int(max_dets), int(max_gt), ctypes.cast(_dbl_arr(iou_thrs), c_p), ctypes.cast(_dbl_arr(area_flat), c_p),
+         _p(ws), st)
+    precision = torch.empty((10, 101, K, 4), dtype=torch.float64, device=dev)
+    recall = torch.empty((10, K, 4, 3), dtype=torch.float64, device=dev)
+    call("utv2_coco_accumulate", _p(perm2), _p(cat_off), _p(rank), K, D, ctypes.cast(_dbl_arr(rec_thrs), c_p), _p(ws), _p(precision),
+         _p(recall), st)
+    return precision, recall
