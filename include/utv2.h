@@ -556,6 +556,25 @@ int utv2_coco_match(const float* dbox, const long long* dperm, const long long* 
 int utv2_coco_accumulate(const long long* perm2, const long long* cat_off, const unsigned char* rank, int K, int64_t D,
                          const double* rec_thrs_host, const void* ws, double* precision, double* recall, utv2_stream_t stream);
 
+/* ---- grouped 3x3 convolution (ResNeXt conv2, modeling/backbone.py; D2 BottleneckBlock with num_groups > 1) -----------------------
+ * NHWC, pad 1, stride 1 or 2, C input = C output channels in G groups of g = C / G (g % 4 == 0); OH = (H - 1) / stride + 1.
+ * w = the arena matrix [C][3][3][g], element type op_dtype like the activation operand (UTV2_F32: exact fp32 mode; UTV2_BF16: the
+ * library's 16-bit type); fp32 accumulation; one launch for all groups (csrc/conv_grouped.hip).
+ * fwd:   y = relu?(conv(x, w) * scale[k] + shift[k]) (scale / shift NULL: 1 / 0); y_dtype UTV2_F32 or op_dtype.
+ * dgrad: dx = dgrad(dy) with scale[k] (NULL: 1) folded into the weights; then dx = mask > 0 ? dx : 0 (mask NULL: none), dx += residual;
+ *        mask / residual have dx's element type.
+ * wgrad: dw[k][kh][kw][c] (+)= scale[k] * sum_m dy[m][k] * x[...]: split over output pixels into ws, the splits added in a fixed order by
+ *        a second launch (deterministic, no atomics). */
+int utv2_gconv3x3_supported(int C, int G);
+int utv2_gconv3x3_fwd(const void* x, const void* w, int op_dtype, void* y, int y_dtype, const float* scale, const float* shift, int N,
+                      int H, int W, int C, int G, int stride, int OH, int OW, int relu, utv2_stream_t stream);
+int utv2_gconv3x3_dgrad(const void* dy, const void* w, int op_dtype, void* dx, int dx_dtype, const float* scale, const void* mask,
+                        const void* residual, int N, int H, int W, int C, int G, int stride, int OH, int OW, utv2_stream_t stream);
+int utv2_gconv3x3_wgrad_splits(int N, int OH, int OW, int C, int G);
+int64_t utv2_gconv3x3_wgrad_workspace_floats(int N, int OH, int OW, int C, int G);
+int utv2_gconv3x3_wgrad(const void* x, const void* dy, int op_dtype, float* dw, float* ws, const float* scale, int N, int H, int W,
+                        int C, int G, int stride, int OH, int OW, int accumulate, utv2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

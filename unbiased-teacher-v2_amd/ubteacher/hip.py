@@ -74,7 +74,8 @@ def _parse_header(path):
 _SIGS = _parse_header(HEADER_PATH)
 _PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats", "utv2_groupnorm_workspace_floats",
           "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
-          "utv2_coco_eval_workspace_bytes"}  # return a value, not a status
+          "utv2_coco_eval_workspace_bytes", "utv2_gconv3x3_supported", "utv2_gconv3x3_wgrad_splits",
+          "utv2_gconv3x3_wgrad_workspace_floats"}  # return a value, not a status
 
 
 _libs = {}
@@ -1282,6 +1283,60 @@ def conv2d_wgrad_bf16(x, dy2d, dw, rowinfo, C, kh, kw, accumulate=True, db=None,
         pitch = int(x_pitch) if x_pitch is not None else groups * C
         call("utv2_conv2d_wgrad_bf16_g", xp, _dt(x), pitch, c_p(dy2d.data_ptr()), _dt(dy2d), dy_pitch, _p(dw), _p(db), _p(ws), _p(rowinfo),
              _p(rowscale), M, C, K, kh, kw, int(accumulate), int(groups), _stream())
+    return dw
+
+
+# --------------------------------------------------------------------------------------------
+# grouped 3x3 convolution (ResNeXt conv2; csrc/conv_grouped.hip).  w: the arena matrix [C, 9 * C / groups], fp32 in the exact-fp32
+# mode, the 16-bit mirror under AMP; the activation operand (x / dy) has w's element type.
+def gconv3x3_supported(C, groups):
+    return bool(load().utv2_gconv3x3_supported(C, groups))
+
+
+def _gconv_check(t, w, groups):
+    C = t.shape[-1]
+    assert t.dim() == 4 and t.dtype == w.dtype and tuple(w.shape) == (C, 9 * C // groups), (tuple(t.shape), tuple(w.shape), groups)
+    assert gconv3x3_supported(C, groups), (C, groups)
+    return C
+
+
+def gconv3x3_fwd(x, w, groups, stride=1, scale=None, shift=None, relu=False, out_dtype=None, out=None):
+    """y [N, OH, OW, C] = relu?(grouped conv3x3 pad 1 (x) * scale + shift); out_dtype: fp32 or x's (default)"""
+    N, H, W, C = x.shape
+    _gconv_check(x, w, groups)
+    OH, OW = conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1)
+    if out is None:
+        out = torch.empty((N, OH, OW, C), dtype=out_dtype or x.dtype, device=x.device)
+    assert tuple(out.shape) == (N, OH, OW, C)
+    call("utv2_gconv3x3_fwd", _p(x), _p(w), _dt(x), _p(out), _dt(out), _p(scale), _p(shift), N, H, W, C, groups, stride, OH, OW,
+         int(relu), _stream())
+    return out
+
+
+def gconv3x3_dgrad(dy, w, groups, stride, in_shape, scale=None, mask=None, residual=None, out_dtype=None):
+    """dx [N, H, W, C] of the grouped conv3x3 pad 1 with the per-output-channel multiplier `scale` (FrozenBN) folded in; then
+    dx = mask > 0 ? dx : 0 and dx += residual (both of dx's element type)"""
+    N, OH, OW, C = dy.shape
+    _gconv_check(dy, w, groups)
+    N_, H, W, C_ = in_shape
+    assert (N_, C_) == (N, C) and (OH, OW) == (conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1))
+    out = torch.empty((N, H, W, C), dtype=out_dtype or dy.dtype, device=dy.device)
+    for t in (mask, residual):
+        assert t is None or (t.dtype == out.dtype and tuple(t.shape) == tuple(out.shape))
+    call("utv2_gconv3x3_dgrad", _p(dy), _p(w), _dt(dy), _p(out), _dt(out), _p(scale), _p(mask), _p(residual), N, H, W, C, groups, stride,
+         OH, OW, _stream())
+    return out
+
+
+def gconv3x3_wgrad(x, dy, dw, groups, stride, scale=None, accumulate=True):
+    """dw [C, 9 * C / groups] fp32 (+)= scale[k] * weight gradient; deterministic (fixed split order, no atomics)"""
+    N, H, W, C = x.shape
+    _, OH, OW, _ = dy.shape
+    assert x.dtype == dy.dtype and dw.dtype == torch.float32 and tuple(dw.shape) == (C, 9 * C // groups)
+    assert gconv3x3_supported(C, groups) and tuple(dy.shape) == (N, conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1), C)
+    ws = workspace(load().utv2_gconv3x3_wgrad_workspace_floats(N, OH, OW, C, groups), x.device, "gconv_wgrad")
+    call("utv2_gconv3x3_wgrad", _p(x), _p(dy), _same_dt(x, dy), _p(dw), _p(ws), _p(scale), N, H, W, C, groups, stride, OH, OW,
+         int(accumulate), _stream())
     return dw
 
 

@@ -1,13 +1,13 @@
-"""ResNet-50 + FPN on the HIP conv path.
+"""ResNet-50 / 101 / 152 and ResNeXt + FPN on the HIP conv path.
 
-Behavioural spec: Detectron2 v0.6 ResNet (STRIDE_IN_1X1, FrozenBN, FREEZE_AT=2) and FPN
+Behavioural spec: Detectron2 v0.6 ResNet (DEPTH, NUM_GROUPS, WIDTH_PER_GROUP, STRIDE_IN_1X1, FrozenBN, FREEZE_AT) and FPN
 [D2-recall, SURVEY.md appendix C]; FCOS top block: reference ubteacher/modeling/backbone/fpn.py:11-78
 (P6 = conv3x3 s2 (P5), P7 = conv3x3 s2 (relu(P6))).  State-dict keys follow Detectron2's
 (`bottom_up.stem.conv1.weight`, `bottom_up.res3.0.conv1.norm.running_mean`, `fpn_lateral3.weight`,
 `top_block.p6.weight`, ...) so checkpoints stay interchangeable.
 
 MI355X mapping: every conv is one implicit-GEMM launch with FrozenBN/ReLU/residual fused in
-the epilogue; stem+res2 (frozen) run outside autograd; the image batch enters as NHWC4.
+the epilogue (a grouped ResNeXt conv2: one launch of csrc/conv_grouped.hip for all groups); stem+res2 (frozen) run outside autograd; the image batch enters as NHWC4.
 """
 import math
 import os
@@ -84,18 +84,20 @@ class BNFolder:
                           self.scale_all, self.shift_all, eps)
 
 
-def _conv_bn(store, folder, prefix, cin, cout, k, stride, pad, relu, trainable):
+def _conv_bn(store, folder, prefix, cin, cout, k, stride, pad, relu, trainable, groups=1):
     kind = "decay" if trainable else "frozen"
-    w = store.new((cout, k * k * cin), kind, _msra_init(cout, cin, k)).export(prefix + ".weight", _nchw_view(cout, cin, k))
+    cg = cin // groups      # input channels per group: the weight is [cout, k * k * cg] ([cout, cg, k, k] in the state dict)
+    w = store.new((cout, k * k * cg), kind, _msra_init(cout, cg, k)).export(prefix + ".weight", _nchw_view(cout, cg, k))
     bn = folder.add(FrozenBN(store, prefix + ".norm", cout))
-    return ops.Conv(w, cin, cout, k, stride, pad, bias=None, bn=bn, relu=relu, trainable=trainable)
+    return ops.Conv(w, cg, cout, k, stride, pad, bias=None, bn=bn, relu=relu, trainable=trainable, groups=groups)
 
 
 class Bottleneck:
-    def __init__(self, store, folder, prefix, cin, cout, mid, stride, trainable):
-        # STRIDE_IN_1X1: the stride sits on conv1
-        self.conv1 = _conv_bn(store, folder, prefix + ".conv1", cin, mid, 1, stride, 0, True, trainable)
-        self.conv2 = _conv_bn(store, folder, prefix + ".conv2", mid, mid, 3, 1, 1, True, trainable)
+    def __init__(self, store, folder, prefix, cin, cout, mid, stride, trainable, groups=1, stride_in_1x1=True):
+        # STRIDE_IN_1X1: the stride sits on conv1 (True) or on the 3x3 conv2 (False); the shortcut always carries it
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)
+        self.conv1 = _conv_bn(store, folder, prefix + ".conv1", cin, mid, 1, s1, 0, True, trainable)
+        self.conv2 = _conv_bn(store, folder, prefix + ".conv2", mid, mid, 3, s3, 1, True, trainable, groups=groups)
         self.conv3 = _conv_bn(store, folder, prefix + ".conv3", mid, cout, 1, 1, 0, True, trainable)  # relu after add
         self.shortcut = None
         if cin != cout:
@@ -110,8 +112,43 @@ class Bottleneck:
         return ops.bottleneck(self, x)
 
 
-class ResNet50:
-    def __init__(self, store, folder, prefix, out_features, freeze_at=2):
+# Detectron2 build_resnet_backbone: blocks per stage of the bottleneck depths
+RESNET_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+
+
+def resnet_spec(cfg):
+    """(blocks per stage, groups, width per group, stride_in_1x1) of cfg.MODEL.RESNETS, or NotImplementedError naming the key of a
+    configuration this backbone does not build (it would otherwise be built as something else without a word)."""
+    r = cfg.MODEL.RESNETS
+    if r.DEPTH not in RESNET_DEPTHS:
+        raise NotImplementedError("MODEL.RESNETS.DEPTH %r: only the bottleneck depths %s are built (BasicBlock depths 18 / 34 are not)"
+                                  % (r.DEPTH, sorted(RESNET_DEPTHS)))
+    if any(bool(d) for d in r.DEFORM_ON_PER_STAGE):
+        raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE %r: deformable convolutions are not built" % (list(r.DEFORM_ON_PER_STAGE),))
+    if r.RES5_DILATION != 1:
+        raise NotImplementedError("MODEL.RESNETS.RES5_DILATION %r: only 1 is built" % (r.RES5_DILATION,))
+    if r.NORM != "FrozenBN":
+        raise NotImplementedError("MODEL.RESNETS.NORM %r: only FrozenBN is built" % (r.NORM,))
+    if r.RES2_OUT_CHANNELS != 256:
+        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS %r: only 256 is built" % (r.RES2_OUT_CHANNELS,))
+    if r.STEM_OUT_CHANNELS != 64:
+        raise NotImplementedError("MODEL.RESNETS.STEM_OUT_CHANNELS %r: only 64 is built" % (r.STEM_OUT_CHANNELS,))
+    if cfg.MODEL.FPN.NORM != "":
+        raise NotImplementedError("MODEL.FPN.NORM %r: only '' (no norm) is built" % (cfg.MODEL.FPN.NORM,))
+    if cfg.MODEL.FPN.FUSE_TYPE != "sum":
+        raise NotImplementedError("MODEL.FPN.FUSE_TYPE %r: only 'sum' is built" % (cfg.MODEL.FPN.FUSE_TYPE,))
+    groups, wpg = int(r.NUM_GROUPS), int(r.WIDTH_PER_GROUP)
+    if groups > 1 and wpg % 4:
+        raise NotImplementedError("MODEL.RESNETS.WIDTH_PER_GROUP %r: the grouped conv kernels take a multiple of 4 channels per group" % wpg)
+    return RESNET_DEPTHS[r.DEPTH], groups, wpg, bool(r.STRIDE_IN_1X1)
+
+
+class ResNet:
+    """Detectron2 build_resnet_backbone for bottleneck ResNets / ResNeXts: DEPTH 50 / 101 / 152, NUM_GROUPS x WIDTH_PER_GROUP bottleneck
+    width of res2 (doubling per stage; only conv2 is grouped), STRIDE_IN_1X1, FrozenBN, FREEZE_AT."""
+
+    def __init__(self, store, folder, prefix, out_features, freeze_at=2, num_blocks=(3, 4, 6, 3), groups=1, width_per_group=64,
+                 stride_in_1x1=True):
         self.out_features = out_features
         # stem on the NHWC4 image: [64][7*7*4 -> padded to 208]
         def stem_init(t):
@@ -125,13 +162,14 @@ class ResNet50:
         self.stem = ops.Conv(self.stem_w, 4, 64, 7, 2, 3, bn=self.stem_bn, relu=True, trainable=stem_train, kred=208)
         self.stages = []
         cin = 64
-        for si, (name, nblocks, mid, cout) in enumerate([("res2", 3, 64, 256), ("res3", 4, 128, 512),
-                                                          ("res4", 6, 256, 1024), ("res5", 3, 512, 2048)]):
+        for si, nblocks in enumerate(num_blocks):
+            name, mid, cout = "res%d" % (si + 2), groups * width_per_group * 2 ** si, 256 * 2 ** si
             trainable = freeze_at < si + 2
             blocks = []
             for b in range(nblocks):
                 stride = 2 if (b == 0 and name != "res2") else 1
-                blocks.append(Bottleneck(store, folder, "%s.%s.%d" % (prefix, name, b), cin, cout, mid, stride, trainable))
+                blocks.append(Bottleneck(store, folder, "%s.%s.%d" % (prefix, name, b), cin, cout, mid, stride, trainable, groups,
+                                         stride_in_1x1))
                 cin = cout
             self.stages.append((name, blocks, trainable))
         self.channels = {"res2": 256, "res3": 512, "res4": 1024, "res5": 2048}
@@ -175,6 +213,16 @@ class ResNet50:
         return outs
 
 
+def ResNet50(store, folder, prefix, out_features, freeze_at=2):
+    """the R-50 of the shipped configs (kept importable under its old name)"""
+    return ResNet(store, folder, prefix, out_features, freeze_at)
+
+
+def build_resnet(cfg, store, folder, prefix):
+    blocks, groups, wpg, s1x1 = resnet_spec(cfg)
+    return ResNet(store, folder, prefix, cfg.MODEL.RESNETS.OUT_FEATURES, cfg.MODEL.BACKBONE.FREEZE_AT, blocks, groups, wpg, s1x1)
+
+
 def _conv_bias(store, prefix, cin, cout, k, stride, pad, init, relu=False):
     w = store.new((cout, k * k * cin), "decay", init(cout, cin, k)).export(prefix + ".weight", _nchw_view(cout, cin, k))
     b = store.new((cout,), "decay", lambda t: t.zero_()).export(prefix + ".bias")
@@ -185,8 +233,7 @@ class FPN:
     """lateral 1x1 + top-down nearest x2 sum + output 3x3 (FUSE_TYPE sum, NORM '')."""
 
     def __init__(self, store, folder, cfg, top_block_kind):
-        self.bottom_up = ResNet50(store, folder, "backbone.bottom_up", cfg.MODEL.RESNETS.OUT_FEATURES,
-                                  cfg.MODEL.BACKBONE.FREEZE_AT)
+        self.bottom_up = build_resnet(cfg, store, folder, "backbone.bottom_up")
         self.in_features = list(cfg.MODEL.FPN.IN_FEATURES)
         oc = cfg.MODEL.FPN.OUT_CHANNELS
         self.out_channels = oc

@@ -361,7 +361,12 @@ class Conv:
         # [P, groups*cin] matrix; cin / kred are PER GROUP.  Two independent same-shape chains (the FCOS cls / bbox towers) run as ONE
         # launch per depth this way - half the launches, tile-quantisation remainders and split-K slabs of two separate convs.
         self.groups = groups
-        assert groups == 1 or (bn is None and colscale is None and cout % groups == 0)
+        # groups > 1 with a FrozenBN (the ResNeXt conv2, NHWC): cin == cout / groups channels per group, 3x3 pad 1, stride 1 or 2 - the
+        # grouped-conv kernels (hip.gconv3x3_*) in every precision mode, forward, dgrad and wgrad one launch each for all groups
+        self.gconv = groups > 1 and bn is not None
+        assert groups == 1 or (colscale is None and cout % groups == 0)
+        assert not self.gconv or (k == 3 and pad == 1 and stride in (1, 2) and cin * groups == cout and bias is None
+                                  and cin % 4 == 0)
         self.bias = bias  # Handle [cout] or None
         self.bn = bn  # FrozenBN or None
         self.relu = relu
@@ -438,8 +443,19 @@ class Conv:
                                  colscale_handle, meta)
         return self._forward(x, residual, out, colscale_handle, meta)
 
+    def gconv_weight(self):
+        """the grouped conv's weight as the kernels read it: the fp32 arena rows, or their 16-bit mirror under AMP"""
+        return self.w.store.bf16(self.w) if amp() else self.w.t
+
     def _forward(self, x, residual, out, cs, meta, relu_bits=None):
         sc, sh = self.scale_shift()
+        if self.gconv:
+            assert meta is None and residual is None and out is None and cs is None and relu_bits is None
+            w = self.gconv_weight()
+            if x.dtype != w.dtype:
+                raise RuntimeError("grouped conv: %s activation with %s weights (layer cout=%d)" % (x.dtype, w.dtype, self.cout))
+            return hip.gconv3x3_fwd(x.contiguous(), w, self.groups, self.stride, sc, sh, self.relu,
+                                    out_dtype=torch.float32 if self.out_fp32 else x.dtype)
         b16 = self.use_bf16()
         w = self.w.store.bf16(self.w) if b16 else self.w.t
         kw = {}
@@ -520,6 +536,8 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         layer = ctx.layer
+        if layer.gconv:
+            return _ConvFn._backward_grouped(ctx, dy)
         x, y = ctx.saved_tensors
         dy = dy.contiguous()
         if not x.is_contiguous() and not (layer.use_bf16_wgrad() and layer.use_bf16_dgrad()):
@@ -665,6 +683,29 @@ class _ConvFn(torch.autograd.Function):
             GRAD_SYNC[0].on_backward_done(_sync_handles(layer, ctx.cs))
         return dx, gres, None, None, None, None, None
 
+    @staticmethod
+    def _backward_grouped(ctx, dy):
+        """grouped conv (ResNeXt conv2): ReLU mask, then dgrad (FrozenBN multiplier folded, the input's ReLU mask in the epilogue when
+        premasked) and wgrad (multiplier as row scale) on the grouped kernels"""
+        layer = ctx.layer
+        x, y = ctx.saved_tensors
+        w = layer.gconv_weight()
+        g = dy.contiguous()
+        if g.dtype != w.dtype:
+            g = g.to(w.dtype)
+        relu = layer.relu and not (layer.grad_premasked and premask_on())
+        if relu:
+            g = hip.relu_bwd_scale(g, y if y.dtype == g.dtype else y.to(g.dtype), None)
+        sc, _ = layer.scale_shift()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            pm = x if (layer.premask_input and premask_on()) else None
+            dx = hip.gconv3x3_dgrad(g, w, layer.groups, layer.stride, tuple(x.shape), scale=sc, mask=pm, out_dtype=x.dtype)
+        _wgrad_launch(lambda: hip.gconv3x3_wgrad(x, g, layer.w.g, layer.groups, layer.stride, scale=sc, accumulate=True), x, g, key=layer)
+        if GRAD_SYNC[0] is not None:
+            GRAD_SYNC[0].on_backward_done(_sync_handles(layer))
+        return dx, None, None, None, None, None, None
+
 
 # ------------------------------------------------------------------------------------------------
 # AMP ResNet bottleneck as ONE autograd node: the backward chains the three (four) convs explicitly so that the ReLU
@@ -672,6 +713,10 @@ class _ConvFn(torch.autograd.Function):
 # gradient is added in the epilogue of conv1's dgrad (residual) and a stride-2 block interleaves zeros once for both
 # branches.  Left as elementwise work: one ReLU-mask pass over the block output's gradient.
 def _wgrad16(layer, x4, g4):
+    if layer.gconv:
+        _wgrad_launch(lambda: hip.gconv3x3_wgrad(x4, g4, layer.w.g, layer.groups, layer.stride, scale=layer.bn.scale, accumulate=True),
+                      x4, g4, key=layer)
+        return
     n_, h_, w_, _ = x4.shape
     ri = hip.rowinfo_nhwc(n_, h_, w_, g4.shape[1], g4.shape[2], layer.stride, layer.pad, layer.k, layer.k, x4.device)
     _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(x4, g4.reshape(-1, layer.cout), layer.w.g, ri, layer.cin, layer.k, layer.k, accumulate=True,
@@ -683,6 +728,10 @@ def _dgrad16(layer, g4, in_shape, mask=None, residual=None, post_mask=None, mask
         mask = None
     if post_mask_bits is not None:
         post_mask = None
+    if layer.gconv:     # the grouped kernel reads the 16-bit activation for its mask (no bit plane)
+        assert post_mask is None and post_mask_bits is None and mask_bits is None
+        return hip.gconv3x3_dgrad(g4, layer.gconv_weight(), layer.groups, layer.stride, tuple(in_shape), scale=layer.bn.scale, mask=mask,
+                                  residual=residual, out_dtype=hip.h16_dtype())
     BITS_STATS["reads"] += (mask_bits is not None) + (post_mask_bits is not None)
     return hip.conv2d_dgrad_bf16(g4, layer.wt16(layer.bn.scale), tuple(in_shape), layer.stride, layer.pad, layer.k, layer.k,
                                  out_dtype=hip.h16_dtype(), mask=mask, residual=residual, post_mask=post_mask, mask_bits=mask_bits,
@@ -757,8 +806,10 @@ class _BottleneckFn(torch.autograd.Function):
             for c in (c1, c2, c3):
                 h_, w_ = hip.conv_out_size(h_, c.k, c.stride, c.pad), hip.conv_out_size(w_, c.k, c.stride, c.pad)
                 planes.append(hip.relu_bits_buffer((n_, h_, w_, c.cout), x.device))
+            if c2.gconv:        # the grouped conv2 neither writes a plane of its output nor reads one of its input: only conv3's is kept
+                planes[0] = planes[1] = None
             b1, b2, b3 = planes
-            BITS_STATS["planes"] += 3
+            BITS_STATS["planes"] += sum(b is not None for b in planes)
         y1 = c1._forward(x, None, None, None, None, relu_bits=b1)
         y2 = c2._forward(y1, None, None, None, None, relu_bits=b2)
         y3 = c3._forward(y2, res, None, None, None, relu_bits=b3)
@@ -812,6 +863,13 @@ class _BottleneckFn(torch.autograd.Function):
                 dx = hip.zero_interleave2x(c, x.shape[1], x.shape[2], mask=pm if bx is None else None, mask_bits=bx if pm is not None else None,
                                            add=parked)
                 BITS_STATS["reads"] += (bx is not None and pm is not None)
+            elif cs.stride == 2:
+                # STRIDE_IN_1X1 False: conv1 is a stride-1 1x1 and only the shortcut is strided - its compact dgrad is zero-interleaved
+                # to the input grid (with the parked gradient) and added in the epilogue of conv1's dgrad
+                assert c1.stride == 1 and cs.k == 1 and cs.pad == 0
+                c = hip.conv2d_fwd_bf16(gm, cs.wt16(cs.bn.scale), out_dtype=hip.h16_dtype())
+                d = hip.zero_interleave2x(c, x.shape[1], x.shape[2], add=parked)
+                dx = _dgrad16(c1, g1, x.shape, residual=d, post_mask=pm, post_mask_bits=bx)
             else:
                 d = _dgrad16(cs, gm, x.shape, residual=parked)
                 dx = _dgrad16(c1, g1, x.shape, residual=d, post_mask=pm, post_mask_bits=bx)
@@ -830,9 +888,12 @@ def bottleneck(block, x):
     """one fused autograd node when every conv of the block runs on the bf16 kernels, else the per-conv graph"""
     convs = [c for c in (block.conv1, block.conv2, block.conv3, block.shortcut) if c is not None]
     fused = (amp() and torch.is_grad_enabled() and x.dtype == hip.h16_dtype()
-             and all(c.trainable and c.bn is not None and c.bias is None and c.use_bf16() and c.use_bf16_wgrad() and c.use_bf16_dgrad()
-                     for c in convs)
-             and block.conv1.stride in (1, 2) and block.conv1.k == 1 and block.conv3.k == 1)
+             and all(c.trainable and c.bn is not None and c.bias is None
+                     and (c.gconv or (c.use_bf16() and c.use_bf16_wgrad() and c.use_bf16_dgrad())) for c in convs)
+             and block.conv1.stride in (1, 2) and block.conv1.k == 1 and block.conv3.k == 1
+             and not (block.conv1.gconv or block.conv3.gconv)
+             and (block.conv1.stride == 1 or block.conv2.stride == 1)
+             and (block.shortcut is None or block.shortcut.stride == max(block.conv1.stride, block.conv2.stride)))
     if fused:
         return _BottleneckFn.apply(x, hook(x.device), block)
     if (amp() and x.dtype == hip.h16_dtype() and x.is_contiguous() and _fused_frozen_block_on()
@@ -841,6 +902,7 @@ def bottleneck(block, x):
             and (block.shortcut is None or block.shortcut.k == 1) and block.conv3.cout == 256
             and all(c.bn is not None and c.bias is None and c.use_bf16() for c in convs)
             and x.shape[1] * x.shape[2] * 256 < 2 ** 31           # the kernel's 32-bit element offsets inside one image
+            and block.conv2.groups == 1 and block.conv1.cout <= 64  # 64-channel dense intermediates in LDS: no grouped / wider block
             and hip.bottleneck_supported(block.conv1.cin, block.conv1.cout, block.shortcut is not None)):
         # a frozen stride-1 block (res2 under FREEZE_AT 2; the teacher's too): nothing is kept for a backward, so its convs run as one
         # kernel with the 64-channel intermediates in LDS (csrc/bottleneck.hip)
