@@ -287,7 +287,10 @@ int utv2_fcos_targets_range(int num_levels, const int* H_host, const int* W_host
                             int gt_img0, int gt_imgs, int num_classes, int drop_empty, float center_radius,
                             const unsigned char* img_active, int* labels, float* reg_targets, float* bvars, int* gt_inds,
                             utv2_stream_t stream);
-/* fvcore sigmoid_focal_loss_jit at :329-338,:619-628 with on-the-fly one-hot.  ws >= 1024 floats */
+/* fvcore sigmoid_focal_loss_jit at :329-338,:619-628 with on-the-fly one-hot.  ws >= 1024 floats.
+ * Checked (UTV2_EARG otherwise): non-null pointers, P >= 0, C >= 1 (any C; C % 4 == 0 with P * C < 2^32 takes the vector path).
+ * The caller's contract, NOT checked (device data / no defined error): labels in [-1, C] (-1 = row skipped, C = background; any other
+ * value is a row without a positive), gamma >= 0 (2 is a fast path); alpha < 0 = no class weighting (fvcore's rule). */
 int utv2_sigmoid_focal_fwd(const float* logits, const int* labels, int64_t P, int C, float alpha, float gamma,
                            float* loss_sum, float* ws, utv2_stream_t stream);
 int utv2_sigmoid_focal_bwd(const float* logits, const int* labels, int64_t P, int C, float alpha, float gamma,
@@ -295,7 +298,10 @@ int utv2_sigmoid_focal_bwd(const float* logits, const int* labels, int64_t P, in
 /* :340-416 / :514-590 fused over positive locations: Integral(:44-77), centerness target + BCE,
  * GIoU (layers/iou_loss.py:26-76), NLL (layers/kl_loss.py:69-105), TS-better L1 (:552-569).
  * sums[8] = {n_pos, sum ctr_t, sum bce, sum giou*ctr_t, sum nll*iou, n_sel, sum_sel|d-t|, 0}
- * ws >= 4096 floats. */
+ * ws >= 4096 floats.
+ * Accepted: reg_max == 16, box_stride >= 73 and % 4 == 0, P >= 0, flags = quality-iou (1) | klloss (2) | loc type 0..2 << 2 | kl-weight-ctr (16),
+ * bvars NULL = no teacher-better term; all of these are checked, anything else: UTV2_EARG.  P == 0: the forward writes sums = 0, the
+ * backward entries write nothing.  Not checked (device data): labels (< 0 or == num_classes: no gradient), targets > 0. */
 int utv2_fcos_loc_terms_fwd(const int* labels, const float* box, int box_stride, const float* reg_targets,
                             const float* bvars, int64_t P, int num_classes, int reg_max, float ts_better, float ts_cert,
                             int flags, float* sums, float* ws, utv2_stream_t stream);
@@ -470,11 +476,14 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
  * deltas / stdl = the predicted boundary deltas and std logits (row pitch ld floats), cls [R] int64 (-1 = empty slot, foreground =
  * [0, num_classes)), prop / gtb [R][4] proposal and matched gt boxes, gstd [R][4] the pseudo boxes' std logits or NULL.
  * mode 0: nlloss (L1 + 0.05 sum NLL * IoU, gradient through the IoU), 1: smooth_l1 at beta 0, 2: tsbetter, 3: pseudo smooth_l1.
- * Writes sum[0] and the derivatives gdeltas / gstd_out [R][4] (Box2BoxXYXYTransform weights wx, wy and clamp). */
+ * Writes sum[0] and the derivatives gdeltas / gstd_out [R][4] (Box2BoxXYXYTransform weights wx, wy and clamp).
+ * Accepted: R >= 0 (R == 0: sum 0), ld >= 4 (the pitch of deltas and of stdl), mode 0..3; anything else: UTV2_EARG. */
 int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
                       const float* gstd, int R, int num_classes, int mode, float wx, float wy, float scale_clamp, float ts_better,
                       float t_cert, float* sum, float* gdeltas, float* gstd_out, utv2_stream_t stream);
-/* roi_heads/fast_rcnn.py:925-936 + FocalLoss :1405-1429 (softmax CE focal, gamma 1.5), summed */
+/* roi_heads/fast_rcnn.py:925-936 + FocalLoss :1405-1429 (softmax CE focal, gamma 1.5), summed.  Accepted: R >= 0, any C >= 1 (one wave
+ * strides over the row); R < 0 or C < 1: UTV2_EARG.  The caller's contract, NOT checked (device data): target in [-1, C) (-1 = row
+ * skipped) - a target >= C reads past the row. */
 int utv2_softmax_focal_fwd(const float* logits, const int* target, int R, int C, float gamma, float* loss_sum, float* ws,
                            utv2_stream_t stream);
 int utv2_softmax_focal_bwd(const float* logits, const int* target, int R, int C, float gamma, const float* coef,

@@ -135,21 +135,27 @@ __global__ __launch_bounds__(256) void fcos_targets_kernel(LevelTable lt, int N,
 // Sigmoid focal loss (fvcore sigmoid_focal_loss_jit [fvcore-recall], called at
 // fcos_outputs.py:329-335,619-625) with the one-hot target built on the fly from labels.
 //   p = sigmoid(x); ce = max(x,0) - x*t + log1p(exp(-|x|)); p_t = p*t + (1-p)(1-t)
-//   loss = ce * (1-p_t)^gamma * (alpha*t + (1-alpha)(1-t))
+//   loss = ce * (1-p_t)^gamma * (alpha*t + (1-alpha)(1-t))      (the alpha factor only when alpha >= 0: fvcore's rule)
 // fwd: deterministic two-stage sum -> partial[gridDim.x];  rows with label < 0 are skipped.
-// One exponential serves both the sigmoid and the softplus: e = exp(-|x|) in (0, 1], p = 1 / (1 + e) or e / (1 + e), log1p(e) = log(1 + e)
-// (its series below 1e-2, where 1 + e loses digits).  Hardware exp2 / log2 / reciprocal (1 ulp each): ~25 instructions per element
-// instead of ~100 through the libm calls - the two focal kernels of a step were 3x off the HBM roofline on the serial loss tail.
+// One exponential serves both the sigmoid and the softplus: e = exp(-|x|) in (0, 1], p = 1 / (1 + e) or e / (1 + e), softplus tail log1p(e).
+// expf / log1pf, not the hardware exp2 / log2 shortcuts: __expf rounds x log2(e) first (|x| log2(e) u, 7 u at the prior-bias logit -4.6, 125 u
+// at -87, and it flushes results below 2^-126), the gradient of a negative goes with e^3, and log(1 + e) next to a series switch lost
+// u / e - measured against fp64 autograd the gradients were 60 - 250 u off where the fp32 formula is within 2 u
+// (tests/test_loss_kernels_fp64_gpu.py).  The hardware path had been chosen for speed (the focal kernels were off the
+// HBM roofline); the cost of going back has NOT been measured per kernel - the whole training step is within 1 % of what it was.
 __device__ __forceinline__ float focal_term(float x, float t, float alpha, float gamma, float* dldx) {
-  const float e = __expf(-fabsf(x));
-  const float r = __frcp_rn(1.f + e);
+  const float e = expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
   const float p = x >= 0.f ? r : e * r;
-  const float l1p = e < 1e-2f ? e * (1.f - e * (0.5f - e * (1.f / 3.f))) : __logf(1.f + e);   // below 1e-2 the rounding of 1 + e would cost log() digits
+  const float l1p = log1pf(e);
   const float ce = fmaxf(x, 0.f) - x * t + l1p;
-  const float pt = p * t + (1.f - p) * (1.f - t);
-  const float om = 1.f - pt;
+  // 1 - p from the same exponential, not as 1.f - p: for a negative near the prior-bias initialisation (p ~ 0.01) the rounding of 1 - p
+  // to 6e-8 and the subtraction 1 - (1 - p) left 1 - p_t with 1e-5 relative noise, and a zero gradient below x = -17 at gamma 0
+  const float q = x >= 0.f ? e * r : r;
+  const float pt = p * t + q * (1.f - t);
+  const float om = q * t + p * (1.f - t);
   const float mod = (gamma == 2.f) ? om * om : powf(om, gamma);
-  const float at = alpha * t + (1.f - alpha) * (1.f - t);
+  const float at = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;   // fvcore: a negative alpha means "no class weighting"
   if (dldx) {
     // dL/dx = a_t (2t-1) (1-pt)^g [ g*pt*log(pt) - (1-pt) ],  log(pt) = -ce
     *dldx = at * (2.f * t - 1.f) * mod * (gamma * pt * (-ce) - om);
@@ -266,6 +272,9 @@ struct LocTerms {
   float ctr_t, iou, giou_l, nll;
 };
 
+// d = sum_j p_j j taken around the mode: d = jm + delta, delta = sum_j p_j (j - jm).  On a sharply peaked row (delta ~ 1e-4) the plain sum
+// carries u d of rounding, and the backward's (j - d) at the mode - and (t - d) next to it - lost up to 9e-2 of their value to it
+// (tests/test_loss_kernels_fp64_gpu.py); the backward kernel does the same in double.
 template <int R1>
 __device__ __forceinline__ void integral4(const float* __restrict__ z, float* d, float (*prob)[R1]) {
 #pragma unroll
@@ -273,6 +282,10 @@ __device__ __forceinline__ void integral4(const float* __restrict__ z, float* d,
     float m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < R1; ++j) m = fmaxf(m, z[b * R1 + j]);
+    int jm = 0;
+#pragma unroll
+    for (int j = R1 - 1; j >= 0; --j)
+      if (z[b * R1 + j] == m) jm = j;   // the first maximum
     float s = 0.f, e[R1];
 #pragma unroll
     for (int j = 0; j < R1; ++j) { e[j] = expf(z[b * R1 + j] - m); s += e[j]; }
@@ -281,9 +294,9 @@ __device__ __forceinline__ void integral4(const float* __restrict__ z, float* d,
     for (int j = 0; j < R1; ++j) {
       const float pj = e[j] / s;
       if (prob) prob[b][j] = pj;
-      acc += pj * (float)j;
+      acc += pj * (float)(j - jm);
     }
-    d[b] = acc;
+    d[b] = (float)jm + acc;
   }
 }
 
@@ -327,6 +340,46 @@ __device__ __forceinline__ float giou_ltrb(const float* d, const float* t, float
     }
   }
   return loc_type == 0 ? 1.f - giou : (loc_type == 1 ? -logf(iou) : 1.f - iou);
+}
+
+// the same in double, for the backward kernel
+__device__ __forceinline__ double min_grad_f64(double a, double b) { return a < b ? 1.0 : (a == b ? 0.5 : 0.0); }
+__device__ __forceinline__ double max_grad_f64(double a, double b) { return a > b ? 1.0 : (a == b ? 0.5 : 0.0); }
+__device__ __forceinline__ double giou_ltrb_f64(const double* d, const double* t, double* iou_out, double* grad, int loc_type) {
+  const double ta = (t[0] + t[2]) * (t[1] + t[3]);
+  const double pw = d[0] + d[2], ph = d[1] + d[3];
+  const double pa = pw * ph;
+  const double wi = fmin(d[0], t[0]) + fmin(d[2], t[2]);
+  const double hi = fmin(d[3], t[3]) + fmin(d[1], t[1]);
+  const double gw = fmax(d[0], t[0]) + fmax(d[2], t[2]);
+  const double gh = fmax(d[3], t[3]) + fmax(d[1], t[1]);
+  const double ac = gw * gh;
+  const double I = wi * hi;
+  const double U = ta + pa - I;
+  const double iou = (I + 1.0) / (U + 1.0);
+  const double giou = iou - (ac - U) / ac;
+  if (iou_out) *iou_out = iou;
+  if (grad) {
+    // index 0: left, 1: top, 2: right, 3: bottom
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const bool horiz = (b == 0 || b == 2);
+      const double dpa = horiz ? ph : pw;
+      const double dI = horiz ? min_grad_f64(d[b], t[b]) * hi : min_grad_f64(d[b], t[b]) * wi;
+      const double dac = horiz ? max_grad_f64(d[b], t[b]) * gh : max_grad_f64(d[b], t[b]) * gw;
+      const double dU = dpa - dI;
+      const double diou = (dI * (U + 1.0) - (I + 1.0) * dU) / ((U + 1.0) * (U + 1.0));
+      // giou = iou - 1 + U/ac
+      const double dgiou = diou + dU / ac - U * dac / (ac * ac);
+      // three plain assignments, not one nested ?: - hipcc (ROCm 7.2) mis-folded `t == 1 ? -diou / iou : -diou` into the un-divided
+      // numerator for t == 2 (caught by tests/test_fcos_kernels_gpu.py::test_supervised_loss_variants_vs_reference_golden[loclinear])
+      double g = -diou;
+      if (loc_type == 1) g = g / iou;
+      if (loc_type == 0) g = -dgiou;
+      grad[b] = g;
+    }
+  }
+  return loc_type == 0 ? 1.0 - giou : (loc_type == 1 ? -log(iou) : 1.0 - iou);
 }
 
 // flags of the positive-location kernels (config-reachable variants; every shipped YAML uses 0)
@@ -429,59 +482,78 @@ __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict
       continue;
     }
     const float* row = box + i * BS;
-    float d[4], t[4], prob[4][R1];
-    integral4<R1>(row, d, prob);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) t[b] = reg_targets[i * 4 + b];
-    float ctr_t = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
-    float iou, gg[4];
-    giou_ltrb(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
-    if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
-    const float* sp = row + 4 * R1;
-    float dd[4], ds[4];
+    // The row's arithmetic is done in DOUBLE and rounded once per output element.  Only positive locations get here (hundreds to a
+    // few thousand rows per step), so the fp64 rate does not show; in fp32 the softmax - Integral - (t - d) - IoU quotient chain
+    // left errors of 1e-5 .. 9e-2 relative on sharply peaked rows and of 30 - 70 roundings next to d ~ t, against fp64 autograd
+    // (tests/test_loss_kernels_fp64_gpu.py).  The Integral is taken around the mode, d = jm + sum_j p_j (j - jm), so that (j - d) at
+    // the mode keeps its value where even the fp64 plain sum cancels to 0.  The teacher-better SELECTION stays in fp32, bit for bit
+    // the forward kernel's (n_sel and the L1 sum must count the same boundaries).
+    double d[4], t[4], dl[4], prob[4][R1];
+    int jm[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const float sg = 1.f / (1.f + expf(-sp[b]));
-      const float df = t[b] - d[b];
+      float m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < R1; ++j) m = fmaxf(m, row[b * R1 + j]);
+      int q = 0;
+#pragma unroll
+      for (int j = R1 - 1; j >= 0; --j)
+        if (row[b * R1 + j] == m) q = j;   // the first maximum
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < R1; ++j) { prob[b][j] = exp((double)row[b * R1 + j] - (double)m); s += prob[b][j]; }
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < R1; ++j) { prob[b][j] /= s; acc += prob[b][j] * (double)(j - q); }
+      jm[b] = q; dl[b] = acc; d[b] = (double)q + acc;
+      t[b] = (double)reg_targets[i * 4 + b];
+    }
+    double ctr_t = sqrt((fmin(t[0], t[2]) / fmax(t[0], t[2])) * (fmin(t[1], t[3]) / fmax(t[1], t[3])));
+    double iou, gg[4];
+    giou_ltrb_f64(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
+    if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
+    const float* sp = row + 4 * R1;
+    double dd[4], ds[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const double sg = 1.0 / (1.0 + exp(-(double)sp[b]));
+      const double df = d[b] == t[b] ? 0.0 : (t[b] - (double)jm[b]) - dl[b];   // a tie stays a tie
       if (flags & LT_KLLOSS) {
         // kl_b = exp(-s) * sl1(n) + s/2, n = |d - t|: d/dd = exp(-s) * min(n, 1) * sign(d - t); d/ds = 1/2 - exp(-s) * sl1(n)
-        const float n = fabsf(df), es = expf(-sp[b]);
-        const float sgn = df < 0.f ? 1.f : (df > 0.f ? -1.f : 0.f);
-        const float wk = (flags & LT_KL_WCTR) ? ctr_t : 1.f;   // a detached target
-        dd[b] = c_giou * ctr_t * gg[b] + c_nll * wk * es * fminf(n, 1.f) * sgn;
-        ds[b] = c_nll * wk * (0.5f - es * (n < 1.f ? 0.5f * n * n : n - 0.5f));
+        const double n = fabs(df), es = exp(-(double)sp[b]);
+        const double sgn = df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0);
+        const double wk = (flags & LT_KL_WCTR) ? ctr_t : 1.0;   // a detached target
+        dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * wk * es * fmin(n, 1.0) * sgn;
+        ds[b] = (double)c_nll * wk * (0.5 - es * (n < 1.0 ? 0.5 * n * n : n - 0.5));
       } else {
         // nll_b = df^2/(2 sg^2) + log(sg);  d/dd = -df/sg^2 ; d/ds = (1-sg) * (1 - df^2/sg^2)
-        dd[b] = c_giou * ctr_t * gg[b] + c_nll * iou * (-df / (sg * sg));
-        ds[b] = c_nll * iou * (1.f - sg) * (1.f - (df * df) / (sg * sg));
+        dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * iou * (-df / (sg * sg));
+        ds[b] = (double)c_nll * iou * (1.0 - sg) * (1.0 - (df * df) / (sg * sg));
       }
       if (bvars) {
-        const float cs = 1.f - sg;
+        const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
         const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
-        if (ct > ts_cert && ct > cs + ts_better) {
-          const float e = d[b] - t[b];
-          dd[b] += c_l1 * (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f));
-        }
+        if (ct > ts_cert && ct > cs + ts_better) dd[b] += (double)c_l1 * (d[b] > t[b] ? 1.0 : (d[b] < t[b] ? -1.0 : 0.0));
       }
     }
-    const float c = row[4 * R1 + 4];
-    const float dctr = c_bce * (1.f / (1.f + expf(-c)) - ctr_t);
+    const double c = (double)row[4 * R1 + 4];
+    const float dctr = (float)((double)c_bce * (1.0 / (1.0 + exp(-c)) - ctr_t));
     if (accumulate) {
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
-        for (int j = 0; j < R1; ++j) grow[b * R1 + j] += dd[b] * prob[b][j] * ((float)j - d[b]);
+        for (int j = 0; j < R1; ++j) grow[b * R1 + j] += (float)(dd[b] * prob[b][j] * ((double)(j - jm[b]) - dl[b]));
 #pragma unroll
-      for (int b = 0; b < 4; ++b) grow[4 * R1 + b] += ds[b];
+      for (int b = 0; b < 4; ++b) grow[4 * R1 + b] += (float)ds[b];
       grow[4 * R1 + 4] += dctr;
       continue;
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
-      for (int j = 0; j < R1; ++j) grow[b * R1 + j] = dd[b] * prob[b][j] * ((float)j - d[b]);
+      for (int j = 0; j < R1; ++j) grow[b * R1 + j] = (float)(dd[b] * prob[b][j] * ((double)(j - jm[b]) - dl[b]));
 #pragma unroll
-    for (int b = 0; b < 4; ++b) grow[4 * R1 + b] = ds[b];
+    for (int b = 0; b < 4; ++b) grow[4 * R1 + b] = (float)ds[b];
     grow[4 * R1 + 4] = dctr;
     for (int k = 4 * R1 + 5; k < BS; ++k) grow[k] = 0.f;
   }
@@ -825,7 +897,7 @@ int utv2_fcos_targets(int num_levels, const int* H, const int* W, const int* str
 // loss_sum[0] = sum over rows with label >= 0 and all C classes.  ws: >= FOCAL_BLOCKS floats.
 int utv2_sigmoid_focal_fwd(const float* logits, const int* labels, int64_t P, int C, float alpha, float gamma,
                            float* loss_sum, float* ws, hipStream_t stream) {
-  if (!logits || !labels || !loss_sum || !ws) return UTV2_EARG;
+  if (!logits || !labels || !loss_sum || !ws || P < 0 || C < 1) return UTV2_EARG;
   hipLaunchKernelGGL(focal_fwd_kernel, dim3(FOCAL_BLOCKS), dim3(256), 0, stream, logits, labels, (size_t)P, C, alpha, gamma, ws);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, FOCAL_BLOCKS, 1, loss_sum);
   return utv2_launch_status();
@@ -833,7 +905,7 @@ int utv2_sigmoid_focal_fwd(const float* logits, const int* labels, int64_t P, in
 
 int utv2_sigmoid_focal_bwd(const float* logits, const int* labels, int64_t P, int C, float alpha, float gamma,
                            const float* coef, float* dlogits, hipStream_t stream) {
-  if (!logits || !labels || !coef || !dlogits) return UTV2_EARG;
+  if (!logits || !labels || !coef || !dlogits || P < 0 || C < 1) return UTV2_EARG;
   hipLaunchKernelGGL(focal_bwd_kernel, dim3(2048), dim3(256), 0, stream, logits, labels, (size_t)P, C, alpha, gamma, coef, dlogits,
                      (const float*)nullptr, 0);
   return utv2_launch_status();
@@ -841,7 +913,7 @@ int utv2_sigmoid_focal_bwd(const float* logits, const int* labels, int64_t P, in
 
 int utv2_sigmoid_focal_bwd_acc(const float* logits, const int* labels, int64_t P, int C, float alpha, float gamma, const float* coef,
                                const float* gscale, float* dlogits, int accumulate, hipStream_t stream) {
-  if (!logits || !labels || !coef || !dlogits) return UTV2_EARG;
+  if (!logits || !labels || !coef || !dlogits || P < 0 || C < 1) return UTV2_EARG;
   hipLaunchKernelGGL(focal_bwd_kernel, dim3(2048), dim3(256), 0, stream, logits, labels, (size_t)P, C, alpha, gamma, coef, dlogits, gscale,
                      accumulate ? 1 : 0);
   return utv2_launch_status();
@@ -852,7 +924,7 @@ int utv2_sigmoid_focal_bwd_acc(const float* logits, const int* labels, int64_t P
 int utv2_fcos_loc_terms_fwd(const int* labels, const float* box, int box_stride, const float* reg_targets,
                             const float* bvars, int64_t P, int num_classes, int reg_max, float ts_better, float ts_cert,
                             int flags, float* sums, float* ws, hipStream_t stream) {
-  if (!labels || !box || !reg_targets || !sums || !ws || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3)) return UTV2_EARG;
+  if (!labels || !box || !reg_targets || !sums || !ws || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3) || P < 0) return UTV2_EARG;
   hipLaunchKernelGGL((fcos_loc_fwd_kernel<17>), dim3(LOC_BLOCKS), dim3(128), 0, stream, labels, box, box_stride, reg_targets,
                      bvars, (size_t)P, num_classes, ts_better, ts_cert, flags, ws);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(LT_NSUM), dim3(256), 0, stream, (const float*)ws, LOC_BLOCKS, LT_NSUM, sums);
@@ -862,7 +934,8 @@ int utv2_fcos_loc_terms_fwd(const int* labels, const float* box, int box_stride,
 int utv2_fcos_loc_terms_bwd(const int* labels, const float* box, int box_stride, const float* reg_targets,
                             const float* bvars, int64_t P, int num_classes, int reg_max, float ts_better, float ts_cert,
                             int flags, const float* coef, float* dbox, hipStream_t stream) {
-  if (!labels || !box || !reg_targets || !coef || !dbox || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3)) return UTV2_EARG;
+  if (!labels || !box || !reg_targets || !coef || !dbox || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3) || P < 0) return UTV2_EARG;
+  if (P == 0) return UTV2_OK;   // no row to write (and a grid of 0 workgroups is a launch error)
   hipLaunchKernelGGL((fcos_loc_bwd_kernel<17>), dim3(cdiv(P, 128)), dim3(128), 0, stream, labels, box, box_stride, reg_targets,
                      bvars, (size_t)P, num_classes, ts_better, ts_cert, flags, coef, dbox, (const float*)nullptr, 0, 0);
   return utv2_launch_status();
@@ -871,7 +944,8 @@ int utv2_fcos_loc_terms_bwd(const int* labels, const float* box, int box_stride,
 int utv2_fcos_loc_terms_bwd_acc(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
                                 int64_t P, int num_classes, int reg_max, float ts_better, float ts_cert, int flags, const float* coef8,
                                 const float* gscale, float* dbox, int accumulate, hipStream_t stream) {
-  if (!labels || !box || !reg_targets || !coef8 || !dbox || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3)) return UTV2_EARG;
+  if (!labels || !box || !reg_targets || !coef8 || !dbox || reg_max != 16 || flags < 0 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || flags >= 32 || box_stride < 4 * 17 + 5 || (box_stride & 3) || P < 0) return UTV2_EARG;
+  if (P == 0) return UTV2_OK;   // no row to write (and a grid of 0 workgroups is a launch error)
   hipLaunchKernelGGL((fcos_loc_bwd_kernel<17>), dim3(cdiv(P, 128)), dim3(128), 0, stream, labels, box, box_stride, reg_targets,
                      bvars, (size_t)P, num_classes, ts_better, ts_cert, flags, coef8, dbox, gscale, 1, accumulate ? 1 : 0);
   return utv2_launch_status();

@@ -573,7 +573,7 @@ __global__ __launch_bounds__(256) void softmax_focal_fwd_kernel(const float* __r
     for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
     s = wave_reduce_sum(s);
     if (lane == 0) {
-      const float ce = logf(s) + m - x[t];
+      const float ce = logf(s) + (m - x[t]);   // not (logf(s) + m) - x[t]: with logits of order 1e4 the sum m + log s rounds at 1e-3
       const float p = expf(-ce);
       acc += powf(1.f - p, gamma) * ce;
     }
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256) void softmax_focal_bwd_kernel(const float* __r
     for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
     s = wave_reduce_sum(s);
     s = __shfl(s, 0, 64);
-    const float ce = logf(s) + m - x[t];
+    const float ce = logf(s) + (m - x[t]);
     const float p = expf(-ce);
     const float om = 1.f - p;
     const float dce = powf(om, gamma) + (om > 0.f ? gamma * powf(om, gamma - 1.f) * p * ce : 0.f);
@@ -1341,7 +1341,7 @@ __global__ __launch_bounds__(64) void rcnn_loss_combine_kernel(RcnnCombineArgs a
 // loss_sum[0] = sum_r (1-p_r)^gamma * CE_r over rows with target >= 0.  ws >= 256 floats.
 int utv2_softmax_focal_fwd(const float* logits, const int* target, int R, int C, float gamma, float* loss_sum, float* ws,
                            hipStream_t stream) {
-  if (!logits || !target || !loss_sum || !ws) return UTV2_EARG;
+  if (!logits || !target || !loss_sum || !ws || R < 0 || C < 1) return UTV2_EARG;
   hipLaunchKernelGGL(softmax_focal_fwd_kernel, dim3(SF_BLOCKS), dim3(256), 0, stream, logits, target, R, C, gamma, ws);
   hipLaunchKernelGGL(sum_partials_f32, dim3(1), dim3(64), 0, stream, (const float*)ws, SF_BLOCKS, loss_sum);
   return utv2_launch_status();
@@ -1368,7 +1368,7 @@ int utv2_rcnn_loss_combine(const float* rpn_sup, const float* rpn_uns, const flo
 
 int utv2_softmax_focal_bwd(const float* logits, const int* target, int R, int C, float gamma, const float* coef,
                            float* dlogits, hipStream_t stream) {
-  if (!logits || !target || !coef || !dlogits) return UTV2_EARG;
+  if (!logits || !target || !coef || !dlogits || R < 0 || C < 1) return UTV2_EARG;
   if (R == 0) return UTV2_OK;
   hipLaunchKernelGGL(softmax_focal_bwd_kernel, dim3(cdiv(R, 4) > 4096 ? 4096 : cdiv(R, 4)), dim3(256), 0, stream, logits, target,
                      R, C, gamma, coef, dlogits);
