@@ -72,39 +72,31 @@ int utv2_conv2d_bf16_supported(int C, int KH, int KW);
  * s_memrealtime tick over that workgroup's lifetime) and the lifetime in microseconds; 0 / 0 before the first such launch.  The MFMA peak
  * is quoted at 2.4 GHz; under full-chip MFMA load the board's power limit holds the clock at 1.45-1.9 GHz.  No reference counterpart. */
 int utv2_conv_clock_probe(double* ghz, double* lifetime_us);
-/* mask (optional, y's type and shape): y = mask > 0 ? conv*scale+bias : 0, before the residual add - the ReLU backward of the
+/* NHWC conv on the 16-bit MFMA kernels (a dgrad is the same call over dy with the flipped weights).  w16 = bf16 [K][KH*KW*C], C % 8 == 0.
+ * mask (optional, y's type and shape): y = mask > 0 ? conv*scale+bias : 0, before the residual add - the ReLU backward of the
  * layer that produced the input, fused into the dgrad launch that computes its gradient; post_mask (optional, same type and shape):
  * y = post_mask > 0 ? y : 0 AFTER the residual add - the ReLU whose OUTPUT this gradient flows into (a bottleneck's input), so the
- * block that produced that output needs no separate mask pass */
-int utv2_conv2d_nhwc_fwd_bf16(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                              const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C, int K,
-                              int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                              utv2_stream_t stream);
-/* the same with the per-output-pixel geometry table of utv2_conv2d_wgrad_bf16 (rowinfo, optional; in_dil == 1): the tile prologues of
- * the bf16-input kernels load their rows' geometry instead of decoding it (2 us of a 70 us tile on the 256-tile kernel) */
-int utv2_conv2d_nhwc_fwd_bf16_ri(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                                 const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                                 int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                                 const int* rowinfo, utv2_stream_t stream);
-/* the same with ReLU masks as BIT planes (16-bit y, K % 8 == 0): uint8 [N*OH*OW][K / 8], bit q of byte c = channel 8c + q.
- * relu_bits (optional, WRITTEN): bit = the stored output is > 0 - all the backward of the ReLU needs of it; mask_bits / post_mask_bits
- * (optional, read) take the place of mask / post_mask (one form per mask).  The dgrads of a bottleneck (engine/trainer.py's backward
+ * block that produced that output needs no separate mask pass.
+ * rowinfo (optional; in_dil == 1): the per-output-pixel geometry table of utv2_rowinfo_nhwc for this conv, device int32[N*OH*OW][2] - the
+ * tile prologues of the bf16-input kernels load their rows' geometry instead of decoding it (2 us of a 70 us tile on the 256-tile kernel).
+ * ReLU masks as BIT planes (all optional; 16-bit y, K % 8 == 0): uint8 [N*OH*OW][K / 8], bit q of byte c = channel 8c + q.
+ * relu_bits (WRITTEN): bit = the stored output is > 0 - all the backward of the ReLU needs of it; mask_bits / post_mask_bits
+ * (read) take the place of mask / post_mask (one form per mask).  The dgrads of a bottleneck (engine/trainer.py's backward
  * through D2 BottleneckBlock) then read K / 8 bytes per pixel for a sign instead of re-reading 2 K bytes of forward activation. */
 int utv2_conv2d_nhwc_fwd_bf16_bits(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
                                    const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W,
                                    int C, int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
                                    const int* rowinfo, void* relu_bits, const void* mask_bits, const void* post_mask_bits,
                                    utv2_stream_t stream);
-int utv2_conv2d_ml_fwd_bf16(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                            const float* bias, const void* residual, int nlev, const int* H_host, const int* W_host, int N,
-                            int C, int K, int KH, int KW, int pad, int relu, int accumulate, utv2_stream_t stream);
-/* The same over column slices and / or GROUPED (the paired FCOS towers - cls | bbox, two independent 256 -> 256 chains of
+/* Multi-level KH x KW 'same' conv over a level-first [P][x_pitch] matrix (P = N * sum of H*W over the nlev levels; H_host / W_host: host
+ * arrays), optionally over column slices and / or GROUPED (the paired FCOS towers - cls | bbox, two independent 256 -> 256 chains of
  * fcos/fcos.py:252-304 - run as ONE launch per depth): x has row pitch x_pitch elements and group g reads its channels
- * [g*C, (g+1)*C) (C = input channels PER GROUP), w16 = bf16 [K][KH*KW*C], y / residual have row pitch y_pitch >= K.
- * Anything but (groups 1, x_pitch C, y_pitch K) needs bf16 x, C % 32 == 0, K % 4 == 0, pitches % 8 == 0, (K / groups) % 128 == 0.
+ * [g*C, (g+1)*C) (C = input channels PER GROUP, C % 8 == 0), w16 = bf16 [K][KH*KW*C], y / residual have row pitch y_pitch >= K.
+ * Anything but (groups 1, x_pitch C, y_pitch K, no gn_part, no rowinfo) needs bf16 x, C % 32 == 0, K % 4 == 0, pitches % 8 == 0,
+ * (K / groups) % 128 == 0.
  * gn_part (optional; bf16 y, K % 8 == 0): fp32 [ceil(P / 32)][K / 8][2] - per 32-row block and 8-channel group the sum and the sum of
  * squares of y as stored: the statistics pass of the GroupNorm that consumes y (fcos/fcos.py:263-264), see ..._seg_fwd_p32.
- * rowinfo (optional): device int32[P][2], the geometry table of utv2_conv2d_wgrad_bf16 for this conv (same k and pad). */
+ * rowinfo (optional): device int32[P][2], the geometry table of utv2_rowinfo_nhwc for this conv (same k and pad, one call per level). */
 int utv2_conv2d_ml_fwd_bf16_g(const void* x, int x_dtype, int x_pitch, const void* w16, void* y, int y_dtype, int y_pitch,
                               const float* scale, const float* bias, const void* residual, int nlev, const int* H_host,
                               const int* W_host, int N, int C, int K, int KH, int KW, int pad, int relu, int accumulate, int groups,
@@ -122,18 +114,17 @@ int utv2_conv2d_ml_fwd_bf16_gnb(const void* x, int x_pitch, const void* w16, voi
  * {input pixel index of tap (0,0), (W << 16) | mask of the taps that fall inside the image}; KH*KW <= 16 */
 int utv2_conv2d_wgrad_bf16_splits(int M, int K, int Kred);
 int64_t utv2_conv2d_wgrad_bf16_workspace_floats(int M, int K, int Kred);
-/* rowscale (optional, [K]): per-output-channel multiplier of the result (the folded FrozenBN scale: the kernels then
- * consume the gradient of the BN OUTPUT directly); the dgrad weight image takes the same multiplier at flip time */
-int utv2_conv2d_wgrad_bf16(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dw, float* db, float* ws,
-                           const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
-                           utv2_stream_t stream);
-/* x with pixel pitch x_pitch (a channel slice of a wider matrix), dy with row pitch dy_pitch >= K (the first K columns of a
- * zero-padded matrix) and / or grouped: dw rows [g*K/groups, (g+1)*K/groups) correlate dy with input channels [g*C, (g+1)*C)
- * (C per group; dw = [K][KH*KW*C]); (K / groups) % 128 == 0, x_pitch >= groups * C */
+/* dw [K][KH*KW*C] (+)= the weight gradient of a conv from x (`x_dtype`, C % 8 == 0) and dy (`dy_dtype`, [M][K], K % 8 == 0); db (optional,
+ * [K]) (+)= the column sums of dy; ws: utv2_conv2d_wgrad_bf16_workspace_floats floats of scratch.
+ * rowscale (optional, [K]): per-output-channel multiplier of the result (the folded FrozenBN scale: the kernels then
+ * consume the gradient of the BN OUTPUT directly); the dgrad weight image takes the same multiplier at flip time.
+ * x has pixel pitch x_pitch (C, or wider: a channel slice of a wider matrix), dy row pitch dy_pitch >= K (the first K columns of a
+ * zero-padded matrix); groups > 1: dw rows [g*K/groups, (g+1)*K/groups) correlate dy with input channels [g*C, (g+1)*C)
+ * (C per group); (K / groups) % 128 == 0, x_pitch >= groups * C */
 int utv2_conv2d_wgrad_bf16_g(const void* x, int x_dtype, int x_pitch, const void* dy, int dy_dtype, int dy_pitch, float* dw, float* db,
                              float* ws, const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
                              int groups, utv2_stream_t stream);
-/* The same launch with its split-K tail (slab reduction, bias reduction) RECORDED in a caller-owned pending table - host memory of
+/* utv2_conv2d_wgrad_bf16_g with its split-K tail (slab reduction, bias reduction) RECORDED in a caller-owned pending table - host memory of
  * utv2_wgrad_fold_table_bytes() bytes, zero-initialised - instead of launched: utv2_wgrad_fold_flush runs the recorded tails of up to 8
  * launches as ONE kernel, with the arithmetic of the separate kernels (bit-identical gradients).  dw / db are valid after the flush on the
  * same stream; every recorded launch needs its own ws until then; two recorded launches must not share dw or db (EARG: flush first).

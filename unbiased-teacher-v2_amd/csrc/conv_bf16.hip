@@ -54,7 +54,7 @@ struct ConvArgs16 {
   EpiBits bits;              // optional ReLU bit planes (see epilogue_rows): written from / read in place of 16-bit sign tensors
   int mtot;                  // conv_igemm_bf16_rs: rows of x / rowinfo (>= M: a launch may cover a row range of the matrix)
   const int2* rowinfo;       // optional: per OUTPUT row m {input pixel index of tap (0,0), (W << 16) | tap-validity mask} - the table the weight
-                             // gradient kernels read (utv2_conv2d_wgrad_bf16): the tile prologue then loads its rows' geometry instead of
+                             // gradient kernels read (utv2_rowinfo_nhwc): the tile prologue then loads its rows' geometry instead of
                              // decoding it (level search, two integer divisions and a KH x KW bounds loop per staged row: 2.0-2.2 us of a
                              // 70 us tile on the 256-tile kernel, tools/probe/pp_trace)
 };
@@ -1384,6 +1384,20 @@ static const int g_epi_general = env_int("UTV2_EPI_PLAIN", 1) ? 0 : 2;   // OR-e
 static const int g_use_pp = env_int("UTV2_PP", 2) == 1 ? 1 : 2;  // 256 x 256 forward tile, ping-pong schedule: 2 = persistent grid of 256 workgroups,
                                                                  // 1 = one tile per workgroup
 
+// Element-type dispatch: f(TypeTag<T>{}) with T = the type `dtype` names (h16_t / float) - the one place a launch site chooses between
+// the 16-bit and the fp32 instantiation of a kernel; with_types: the same for a kernel templated on two tensor types.
+template <typename T> struct TypeTag { using type = T; };
+#define TAG_T(tag) typename decltype(tag)::type
+template <typename F>
+static void with_type(int dtype, F&& f) {
+  if (dtype == UTV2_BF16) f(TypeTag<h16_t>{});
+  else f(TypeTag<float>{});
+}
+template <typename F>
+static void with_types(int dtype_a, int dtype_b, F&& f) {
+  with_type(dtype_a, [&](auto ta) { with_type(dtype_b, [&](auto tb) { f(ta, tb); }); });
+}
+
 template <int BN, bool ML>
 static void launch_igemm16(const ConvArgs16& a, int tiles, int x_dtype, int y_dtype, hipStream_t stream) {
   const dim3 g(tiles), b(256);
@@ -1425,12 +1439,9 @@ static void launch_igemm16(const ConvArgs16& a, int tiles, int x_dtype, int y_dt
             static LdsOptIn rs_opt_in;
             rs_opt_in({(const void*)conv_igemm_bf16_rs<ML, h16_t>, (const void*)conv_igemm_bf16_rs<ML, float>,
                        (const void*)conv_igemm_bf16_rs<ML, h16_t, ML>}, smem_rs);
-            m.mtot = a.M;
             if (gnb) hipLaunchKernelGGL((conv_igemm_bf16_rs<ML, h16_t, ML>), dim3(grid), dim3(512), smem_rs, stream, m);
-            else if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_rs<ML, h16_t>), dim3(grid), dim3(512), smem_rs, stream, m);
-            else hipLaunchKernelGGL((conv_igemm_bf16_rs<ML, float>), dim3(grid), dim3(512), smem_rs, stream, m);
-          } else if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_pp<ML, h16_t>), dim3(grid), dim3(512), smem, stream, m);
-          else hipLaunchKernelGGL((conv_igemm_bf16_pp<ML, float>), dim3(grid), dim3(512), smem, stream, m);
+            else with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_rs<ML, TAG_T(to)>), dim3(grid), dim3(512), smem_rs, stream, m); });
+          } else with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_pp<ML, TAG_T(to)>), dim3(grid), dim3(512), smem, stream, m); });
         }
         if (m.M == a.M) return;
         ConvArgs16 r = a;
@@ -1444,32 +1455,22 @@ static void launch_igemm16(const ConvArgs16& a, int tiles, int x_dtype, int y_dt
       static const bool use_tall = env_int("UTV2_CONV_TALL64", 1) != 0;
       if (use_tall && a.KH * a.KW > 1 && a.M - a.m_begin >= 65536 && a.K > 32) {
         const dim3 gt(cdiv(a.M - a.m_begin, 256) * cdiv(a.K, 64));
-        if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<64, ML, 32, h16_t, true>), gt, b, 0, stream, a);
-        else hipLaunchKernelGGL((conv_igemm_bf16_v2<64, ML, 32, float, true>), gt, b, 0, stream, a);
+        with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_v2<64, ML, 32, TAG_T(to), true>), gt, b, 0, stream, a); });
         return;
       }
     }
     if constexpr (BN == 96) {   // 256 x 96 tile: BK = 32 only (a BK = 64 stage would need 88 KB of LDS: one workgroup per CU)
-      if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<96, ML, 32, h16_t>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((conv_igemm_bf16_v2<96, ML, 32, float>), g, b, 0, stream, a);
+      with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_v2<96, ML, 32, TAG_T(to)>), g, b, 0, stream, a); });
     } else if (deep) {
       if (gnb) hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 64, h16_t, false, (ML && BN == 128)>), g, b, 0, stream, a);
-      else if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 64, h16_t>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 64, float>), g, b, 0, stream, a);
+      else with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 64, TAG_T(to)>), g, b, 0, stream, a); });
     } else {
-      if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 32, h16_t>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 32, float>), g, b, 0, stream, a);
+      with_type(y_dtype, [&](auto to) { hipLaunchKernelGGL((conv_igemm_bf16_v2<BN, ML, 32, TAG_T(to)>), g, b, 0, stream, a); });
     }
     return;
   }
   if constexpr (BN != 96) {   // (the callers send only v2-eligible problems to the 96-wide tile: n96_eligible)
-    if (x_dtype == UTV2_BF16) {
-      if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16<BN, ML, h16_t, h16_t>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((conv_igemm_bf16<BN, ML, h16_t, float>), g, b, 0, stream, a);
-    } else {
-      if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16<BN, ML, float, h16_t>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((conv_igemm_bf16<BN, ML, float, float>), g, b, 0, stream, a);
-    }
+    with_types(x_dtype, y_dtype, [&](auto ti, auto to) { hipLaunchKernelGGL((conv_igemm_bf16<BN, ML, TAG_T(ti), TAG_T(to)>), g, b, 0, stream, a); });
   }
 }
 
@@ -1481,6 +1482,28 @@ static bool n96_eligible(const ConvArgs16& a, int x_dtype) {
 }
 
 static inline bool bad_dtype(int d) { return d != UTV2_F32 && d != UTV2_BF16; }
+
+// The one place a ConvArgs16 is filled.  Every field has a value: what is not set here is zero / null (no level table, no optional
+// epilogue operand, no rowinfo, one tile per workgroup, from row 0), and the defaults here are those of a dense ungrouped conv
+// (xs = C, ldy = K, groups = 1, in_dil = 1) - an entry point then sets only what it adds.  M = output rows.
+static ConvArgs16 make_args(const void* x, const void* w16, void* y, const float* scale, const float* bias, const void* residual, int N, int C,
+                            int K, int KH, int KW, int stride, int pad, int relu, int accumulate, int M) {
+  ConvArgs16 a{};
+  a.x = x; a.w = (const h16_t*)w16; a.y = y; a.scale = scale; a.bias = bias; a.residual = residual;
+  a.N = N; a.C = C; a.K = K; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.in_dil = 1;
+  a.relu = (relu ? 1 : 0) | g_epi_general; a.accumulate = accumulate; a.Kred = KH * KW * C; a.M = a.mtot = M;
+  a.xs = C; a.groups = 1; a.ldy = K;
+  return a;
+}
+
+// an NHWC (single-level) conv: the 64-wide tiles for K <= 64, else the 128-wide ones
+static int launch_nhwc16(const ConvArgs16& a, int x_dtype, int y_dtype, hipStream_t stream) {
+  const bool small = a.K <= 64;
+  const int tiles = cdiv(a.M, 128) * cdiv(a.K, small ? 64 : 128);
+  if (small) launch_igemm16<64, false>(a, tiles, x_dtype, y_dtype, stream);
+  else launch_igemm16<128, false>(a, tiles, x_dtype, y_dtype, stream);
+  return utv2_launch_status();
+}
 
 extern "C" {
 
@@ -1503,71 +1526,27 @@ int utv2_conv_clock_probe(double* ghz, double* lifetime_us) {
 // 1 if the bf16 MFMA kernel supports this conv (C % 8 == 0), else the caller uses the fp32 kernel
 int utv2_conv2d_bf16_supported(int C, int KH, int KW) { return (C % 8 == 0) ? 1 : 0; }
 
-// w16: bf16 [K][KH*KW*C].  x is `x_dtype`, y and residual are `y_dtype` (UTV2_F32 / UTV2_BF16).  Otherwise the
-// contract of utv2_conv2d_nhwc_fwd (also serves as dgrad).
-// rowinfo (optional): the per-output-pixel geometry table of utv2_conv2d_wgrad_bf16 for this conv (device int32[N*OH*OW][2] =
-// {input pixel index of tap (0,0), (W << 16) | tap-validity mask}; in_dil == 1 only): tile prologues load it instead of decoding it
-int utv2_conv2d_nhwc_fwd_bf16_ri(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                                 const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                                 int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                                 const int* rowinfo, hipStream_t stream);
-
-int utv2_conv2d_nhwc_fwd_bf16(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                              const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                              int K, int KH,
-                              int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate, hipStream_t stream) {
-  return utv2_conv2d_nhwc_fwd_bf16_ri(x, x_dtype, w16, y, y_dtype, scale, bias, residual, mask, post_mask, N, H, W, C, K, KH, KW, stride, pad,
-                                      in_dil, OH, OW, relu, accumulate, nullptr, stream);
-}
-
-static int conv2d_nhwc_fwd_bf16_impl(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                                     const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                                     int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                                     const int* rowinfo, EpiBits bits, hipStream_t stream);
-
-int utv2_conv2d_nhwc_fwd_bf16_ri(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                                 const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                                 int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                                 const int* rowinfo, hipStream_t stream) {
-  return conv2d_nhwc_fwd_bf16_impl(x, x_dtype, w16, y, y_dtype, scale, bias, residual, mask, post_mask, N, H, W, C, K, KH, KW, stride, pad,
-                                   in_dil, OH, OW, relu, accumulate, rowinfo, EpiBits{nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
-}
-
-// The same with ReLU masks as BIT planes (16-bit y, K % 8 == 0; uint8 [N*OH*OW][K / 8], bit q of byte c = channel 8c + q):
-//   relu_bits (optional, written): bit = the stored output is > 0 - what the backward of the ReLU needs of it;
-//   mask_bits / post_mask_bits (optional, read): take the place of mask / post_mask (do not pass both forms of one mask).
+// NHWC conv (also serves as dgrad).  w16: bf16 [K][KH*KW*C].  x is `x_dtype`, y / residual / mask / post_mask are `y_dtype` (UTV2_F32 /
+// UTV2_BF16).  Otherwise the contract of utv2_conv2d_nhwc_fwd.
+// rowinfo (optional): the per-output-pixel geometry table of utv2_rowinfo_nhwc for this conv (device int32[N*OH*OW][2] =
+// {input pixel index of tap (0,0), (W << 16) | tap-validity mask}; in_dil == 1 only): tile prologues load it instead of decoding it.
+// ReLU masks as BIT planes (all optional; 16-bit y, K % 8 == 0; uint8 [N*OH*OW][K / 8], bit q of byte c = channel 8c + q):
+//   relu_bits (written): bit = the stored output is > 0 - what the backward of the ReLU needs of it;
+//   mask_bits / post_mask_bits (read): take the place of mask / post_mask (do not pass both forms of one mask).
 // The dgrad of a bottleneck's convs then reads K / 8 bytes per pixel for a sign instead of the 2 K bytes of the forward activation.
 int utv2_conv2d_nhwc_fwd_bf16_bits(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
                                    const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W,
                                    int C, int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
                                    const int* rowinfo, void* relu_bits, const void* mask_bits, const void* post_mask_bits,
                                    hipStream_t stream) {
+  if (!x || !w16 || !y || (C % 8) || bad_dtype(x_dtype) || bad_dtype(y_dtype) || (rowinfo && in_dil > 1)) return UTV2_EARG;
   if ((relu_bits || mask_bits || post_mask_bits) && (y_dtype != UTV2_BF16 || (K & 7))) return UTV2_EARG;
   if ((mask && mask_bits) || (post_mask && post_mask_bits)) return UTV2_EARG;
-  return conv2d_nhwc_fwd_bf16_impl(x, x_dtype, w16, y, y_dtype, scale, bias, residual, mask, post_mask, N, H, W, C, K, KH, KW, stride, pad,
-                                   in_dil, OH, OW, relu, accumulate, rowinfo,
-                                   EpiBits{(unsigned char*)relu_bits, (const unsigned char*)mask_bits, (const unsigned char*)post_mask_bits, nullptr, nullptr},
-                                   stream);
-}
-
-static int conv2d_nhwc_fwd_bf16_impl(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                                     const float* bias, const void* residual, const void* mask, const void* post_mask, int N, int H, int W, int C,
-                                     int K, int KH, int KW, int stride, int pad, int in_dil, int OH, int OW, int relu, int accumulate,
-                                     const int* rowinfo, EpiBits bits, hipStream_t stream) {
-  if (!x || !w16 || !y || (C % 8) || bad_dtype(x_dtype) || bad_dtype(y_dtype) || (rowinfo && in_dil > 1)) return UTV2_EARG;
-  ConvArgs16 a;
-  a.ntiles = 0;
-  a.bits = bits;
-  a.lt.n = 0;
-  a.x = x; a.w = (const h16_t*)w16; a.y = y; a.scale = scale; a.bias = bias; a.residual = residual; a.mask = mask; a.post_mask = post_mask;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.OH = OH; a.OW = OW; a.K = K; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-  a.in_dil = in_dil < 1 ? 1 : in_dil; a.relu = (relu ? 1 : 0) | g_epi_general; a.accumulate = accumulate; a.Kred = KH * KW * C; a.M = N * OH * OW;
-  a.xs = C; a.m_begin = 0; a.groups = 1; a.ldy = K; a.gn_part = nullptr; a.rowinfo = (const int2*)rowinfo;
-  const bool small = K <= 64;
-  const int tiles = cdiv(a.M, 128) * cdiv(K, small ? 64 : 128);
-  if (small) launch_igemm16<64, false>(a, tiles, x_dtype, y_dtype, stream);
-  else launch_igemm16<128, false>(a, tiles, x_dtype, y_dtype, stream);
-  return utv2_launch_status();
+  ConvArgs16 a = make_args(x, w16, y, scale, bias, residual, N, C, K, KH, KW, stride, pad, relu, accumulate, N * OH * OW);
+  a.mask = mask; a.post_mask = post_mask; a.H = H; a.W = W; a.OH = OH; a.OW = OW; a.in_dil = in_dil < 1 ? 1 : in_dil;
+  a.rowinfo = (const int2*)rowinfo;
+  a.bits = EpiBits{(unsigned char*)relu_bits, (const unsigned char*)mask_bits, (const unsigned char*)post_mask_bits, nullptr, nullptr};
+  return launch_nhwc16(a, x_dtype, y_dtype, stream);
 }
 
 // Multi-level k x k 'same' conv over a level-first [P][x_pitch] matrix, optionally GROUPED and on column slices:
@@ -1576,7 +1555,7 @@ static int conv2d_nhwc_fwd_bf16_impl(const void* x, int x_dtype, const void* w16
 //   C % 32 == 0, K % 4 == 0 and (K / groups) % 128 == 0.
 //   gn_part (optional; bf16 y, K % 8 == 0): fp32 [ceil(P / 32)][K / 8][2], per 32-row block and 8-channel group the sum / sum of squares
 //   of y as stored - the statistics pass of the GroupNorm that follows (utv2_groupnorm_relu_seg_fwd_p32).
-//   rowinfo (optional): device int32[P][2], the per-output-row geometry table of utv2_conv2d_wgrad_bf16 for this conv (same pad and k):
+//   rowinfo (optional): device int32[P][2], the per-output-row geometry table of utv2_rowinfo_nhwc for this conv (same pad and k):
 //   the tile prologues load it instead of decoding (level, image, row, column) and the tap bounds per staged row.
 static int ml_fwd_g(const void* x, int x_dtype, int x_pitch, const void* w16, void* y, int y_dtype, int y_pitch, const float* scale,
                     const float* bias, const void* residual, int nlev, const int* H_host, const int* W_host, int N, int C, int K, int KH, int KW,
@@ -1589,14 +1568,11 @@ static int ml_fwd_g(const void* x, int x_dtype, int x_pitch, const void* w16, vo
   if (!plain && (x_dtype != UTV2_BF16 || (C % 32) || (K & 3) || KH * KW > 16 || (x_pitch & 7) || (y_pitch & 7) ||
                  (groups > 1 && (K / groups) % 128)))
     return UTV2_EARG;
-  ConvArgs16 a;
-  a.ntiles = 0;
-  a.bits = bits;
-  a.M = fill_levels16(a.lt, nlev, N, H_host, W_host);
-  if (!plain && ((int64_t)a.M * x_pitch >= (1ll << 31) || (int64_t)K * KH * KW * C >= (1ll << 31))) return UTV2_EARG;
-  a.x = x; a.w = (const h16_t*)w16; a.y = y; a.scale = scale; a.bias = bias; a.residual = residual; a.mask = nullptr; a.post_mask = nullptr;
-  a.N = N; a.H = 0; a.W = 0; a.C = C; a.OH = 0; a.OW = 0; a.K = K; a.KH = KH; a.KW = KW; a.stride = 1; a.pad = pad; a.in_dil = 1;
-  a.relu = (relu ? 1 : 0) | g_epi_general; a.accumulate = accumulate; a.Kred = KH * KW * C; a.xs = x_pitch; a.m_begin = 0; a.groups = groups; a.ldy = y_pitch; a.gn_part = gn_part; a.rowinfo = (const int2*)rowinfo;
+  LevelTab lt;
+  const int M = fill_levels16(lt, nlev, N, H_host, W_host);
+  if (!plain && ((int64_t)M * x_pitch >= (1ll << 31) || (int64_t)K * KH * KW * C >= (1ll << 31))) return UTV2_EARG;
+  ConvArgs16 a = make_args(x, w16, y, scale, bias, residual, N, C, K, KH, KW, 1, pad, relu, accumulate, M);
+  a.lt = lt; a.xs = x_pitch; a.groups = groups; a.ldy = y_pitch; a.gn_part = gn_part; a.rowinfo = (const int2*)rowinfo; a.bits = bits;
   const bool small = K <= 64 && plain;
   const int tiles = cdiv(a.M, 128) * cdiv(K, small ? 64 : 128);
   if (n96_eligible(a, x_dtype)) launch_igemm16<96, true>(a, cdiv(a.M, 256), x_dtype, y_dtype, stream);
@@ -1628,59 +1604,21 @@ int utv2_conv2d_ml_fwd_bf16_gnb(const void* x, int x_pitch, const void* w16, voi
                   groups, nullptr, rowinfo, EpiBits{nullptr, (const unsigned char*)mask_bits, nullptr, gnb_x, gnb_part}, stream);
 }
 
-int utv2_conv2d_ml_fwd_bf16(const void* x, int x_dtype, const void* w16, void* y, int y_dtype, const float* scale,
-                            const float* bias, const void* residual, int nlev, const int* H_host, const int* W_host, int N,
-                            int C, int K, int KH, int KW, int pad, int relu, int accumulate, hipStream_t stream) {
-  if (!x || !w16 || !y || nlev < 1 || nlev > CONV_MAX_LEVELS || (C % 8) || N <= 0 || bad_dtype(x_dtype) || bad_dtype(y_dtype))
-    return UTV2_EARG;
-  ConvArgs16 a;
-  a.ntiles = 0;
-  a.bits = EpiBits{nullptr, nullptr, nullptr, nullptr, nullptr};
-  a.M = fill_levels16(a.lt, nlev, N, H_host, W_host);
-  a.x = x; a.w = (const h16_t*)w16; a.y = y; a.scale = scale; a.bias = bias; a.residual = residual; a.mask = nullptr; a.post_mask = nullptr;
-  a.N = N; a.H = 0; a.W = 0; a.C = C; a.OH = 0; a.OW = 0; a.K = K; a.KH = KH; a.KW = KW; a.stride = 1; a.pad = pad; a.in_dil = 1;
-  a.relu = (relu ? 1 : 0) | g_epi_general; a.accumulate = accumulate; a.Kred = KH * KW * C; a.xs = C; a.m_begin = 0; a.groups = 1; a.ldy = K; a.gn_part = nullptr; a.rowinfo = nullptr;
-  const bool small = K <= 64;
-  const int tiles = cdiv(a.M, 128) * cdiv(K, small ? 64 : 128);
-  if (n96_eligible(a, x_dtype)) launch_igemm16<96, true>(a, cdiv(a.M, 256), x_dtype, y_dtype, stream);
-  else if (small) launch_igemm16<64, true>(a, tiles, x_dtype, y_dtype, stream);
-  else launch_igemm16<128, true>(a, tiles, x_dtype, y_dtype, stream);
-  return utv2_launch_status();
-}
-
 // Image stem (7x7 stride 2 pad 3 on the 3-channel image) on bf16 MFMA.  xpad16: bf16 [N][H+6][W+8][4], the normalised NHWC4
 // image inside a zero border of 3 pixels (5 on the right), so no tap is ever out of bounds and every read is 16-byte
 // aligned.  One kernel row kh of an output pixel reads 8 consecutive input pixels = 32 contiguous bf16 (7 taps x 4
 // channels + one zero-weighted pixel): the conv is run as KH = 7, KW = 1, C = 32 with a 4-element pixel pitch.
 // w16s: bf16 [K][7][32] (last 4 of each 32 zero).  H, W: the padded image canvas (even).
+// (16-bit x, C = 32, 7 taps, no rowinfo and both operands under 2^31 elements: launch_igemm16 stays on conv_igemm_bf16_v2 with BK = 32 -
+// the 256 x 64 tile for M >= 65536 and 32 < K <= 64, else 128 x 64 / 128 x 128.)
 int utv2_conv2d_stem_fwd_bf16(const void* xpad16, const void* w16s, void* y, int y_dtype, const float* scale, const float* bias,
                               int N, int H, int W, int K, int OH, int OW, int relu, hipStream_t stream) {
   if (!xpad16 || !w16s || !y || N <= 0 || (W & 1) || (K & 3) || bad_dtype(y_dtype) || OH != (H + 6 - 7) / 2 + 1 ||
-      OW != (W + 6 - 7) / 2 + 1 || (int64_t)N * (H + 6) * (W + 8) * 4 >= (1ll << 31))
+      OW != (W + 6 - 7) / 2 + 1 || (int64_t)N * (H + 6) * (W + 8) * 4 >= (1ll << 31) || (int64_t)K * 7 * 32 >= (1ll << 31))
     return UTV2_EARG;
-  ConvArgs16 a;
-  a.ntiles = 0;
-  a.bits = EpiBits{nullptr, nullptr, nullptr, nullptr, nullptr};
-  a.lt.n = 0;
-  a.x = xpad16; a.w = (const h16_t*)w16s; a.y = y; a.scale = scale; a.bias = bias; a.residual = nullptr; a.mask = nullptr; a.post_mask = nullptr;
-  a.N = N; a.H = H + 6; a.W = W + 8; a.C = 32; a.OH = OH; a.OW = OW; a.K = K; a.KH = 7; a.KW = 1; a.stride = 2; a.pad = 0;
-  a.in_dil = 1; a.relu = (relu ? 1 : 0) | g_epi_general; a.accumulate = 0; a.Kred = 7 * 32; a.M = N * OH * OW; a.xs = 4; a.m_begin = 0; a.groups = 1; a.ldy = K; a.gn_part = nullptr; a.rowinfo = nullptr;
-  const bool small = K <= 64;
-  const int tiles = cdiv(a.M, 128) * cdiv(K, small ? 64 : 128);
-  const dim3 g(tiles), b(256);
-  static const bool use_tall = env_int("UTV2_CONV_TALL64", 1) != 0;
-  if (small && use_tall && a.M >= 65536 && K > 32) {
-    const dim3 gt(cdiv(a.M, 256));
-    if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<64, false, 32, h16_t, true>), gt, b, 0, stream, a);
-    else hipLaunchKernelGGL((conv_igemm_bf16_v2<64, false, 32, float, true>), gt, b, 0, stream, a);
-  } else if (small) {
-    if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<64, false, 32, h16_t>), g, b, 0, stream, a);
-    else hipLaunchKernelGGL((conv_igemm_bf16_v2<64, false, 32, float>), g, b, 0, stream, a);
-  } else {
-    if (y_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_igemm_bf16_v2<128, false, 32, h16_t>), g, b, 0, stream, a);
-    else hipLaunchKernelGGL((conv_igemm_bf16_v2<128, false, 32, float>), g, b, 0, stream, a);
-  }
-  return utv2_launch_status();
+  ConvArgs16 a = make_args(xpad16, w16s, y, scale, bias, nullptr, N, 32, K, 7, 1, 2, 0, relu, 0, N * OH * OW);
+  a.H = H + 6; a.W = W + 8; a.OH = OH; a.OW = OW; a.xs = 4;
+  return launch_nhwc16(a, UTV2_BF16, y_dtype, stream);
 }
 
 // The per-output-pixel geometry table of the 16-bit convs / weight gradients, built ON THE DEVICE (round 6): until then the host
@@ -2511,26 +2449,77 @@ int64_t utv2_conv2d_wgrad_bf16_workspace_floats(int M, int K, int Kred) {
   return n;
 }
 
-// rowinfo: device int32[M][2] = {anchor input pixel, (W << 16) | tapmask} for every OUTPUT pixel m (built once per
-// geometry by the host).  x is `x_dtype` with pixel pitch x_pitch elements, dy is `dy_dtype` [M][K].  C % 8 == 0, K % 8 == 0,
+// One split-K tail of a weight gradient: dst[n] (+)= rowscale * the sum of `parts` partial results at src - recorded in `pending` (see
+// reduce_slabs_table, which runs the same arithmetic) when there is one, else launched.  kind: 0 = weight slabs [parts][n] (rows of
+// rowlen), 1 = bias slabs [parts][n], 2 = per-row-block column sums [parts][n].
+static int wgrad16_tail(SlabFoldTable* pending, int kind, const float* src, float* dst, const float* rowscale, size_t n, int parts,
+                        int accumulate, int rowlen, hipStream_t stream) {
+  if (pending) return slab_fold_add(pending, kind, src, dst, rowscale, n, parts, accumulate, rowlen);
+  if (kind == 0) {
+    int rb = cdiv((int64_t)n / 4, 256);   // n = K * Kred, both multiples of 8
+    if (rb > 8192) rb = 8192;
+    hipLaunchKernelGGL(reduce_slabs16_f32, dim3(rb), dim3(256), 0, stream, src, dst, n, parts, accumulate, rowscale, rowlen);
+  } else if (kind == 1) {
+    hipLaunchKernelGGL(reduce_slabs16_scalar_f32, dim3(cdiv((int64_t)n, 256)), dim3(256), 0, stream, src, dst, n, parts, accumulate, rowscale);
+  } else {
+    hipLaunchKernelGGL(colsum_final_f32, dim3(cdiv((int64_t)n, 32)), dim3(256), 0, stream, src, dst, parts, (int)n, accumulate, rowscale);
+  }
+  return UTV2_OK;
+}
+
+// rowinfo: device int32[M][2] = {anchor input pixel, (W << 16) | tapmask} for every OUTPUT pixel m (utv2_rowinfo_nhwc, built once per
+// geometry).  x is `x_dtype` with pixel pitch x_pitch elements, dy is `dy_dtype` [M][K] with row pitch dy_pitch.  C % 8 == 0, K % 8 == 0,
 // KH*KW <= 16.  dw [K][KH*KW*C] (+)= rowscale[co] * result; db (optional, [K]) (+)= rowscale[co] * column sums of dy; rowscale optional.
 // groups > 1: grouped conv - output channels [g*K/groups, ...) correlate with input channels [g*C, (g+1)*C) (C per group),
-// (K / groups) % 128 == 0, x_pitch >= groups * C.
+// (K / groups) % 128 == 0, x_pitch >= groups * C.  pending (optional): the table the split-K tails are recorded in instead of launched.
 static int wgrad_bf16_impl(const void* x, int x_dtype, int x_pitch, const void* dy, int dy_dtype, int dy_pitch, float* dw, float* db,
                            float* ws, const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
-                           int groups, hipStream_t stream, SlabFoldTable* pending = nullptr);
-
-int utv2_conv2d_wgrad_bf16(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dw, float* db, float* ws,
-                           const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
-                           hipStream_t stream) {
-  return wgrad_bf16_impl(x, x_dtype, C, dy, dy_dtype, K, dw, db, ws, rowinfo, rowscale, M, C, K, KH, KW, accumulate, 1, stream);
+                           int groups, hipStream_t stream, SlabFoldTable* pending) {
+  if (!x || !dy || !dw || !ws || !rowinfo || (C & 7) || (K & 7) || M <= 0 || KH * KW > 16 || bad_dtype(x_dtype) ||
+      bad_dtype(dy_dtype) || groups < 1 || K % groups || x_pitch < groups * C || (groups > 1 && (K / groups) % 128) ||
+      (x_pitch != C && (x_pitch & (x_dtype == UTV2_BF16 ? 7 : 3))) || dy_pitch < K || (dy_pitch != K && (dy_pitch & (dy_dtype == UTV2_BF16 ? 7 : 3))))
+    return UTV2_EARG;
+  Wgrad16Args a;
+  a.x = x; a.dy = dy; a.ws = ws; a.rowinfo = (const int2*)rowinfo;
+  a.C = C; a.K = K; a.KH = KH; a.KW = KW; a.Kred = KH * KW * C; a.M = M; a.debug = 0; a.xs = x_pitch; a.groups = groups; a.dys = dy_pitch;
+  const size_t n = (size_t)K * a.Kred;
+  if (g_use_wgrad_w8 && x_dtype == UTV2_BF16 && dy_dtype == UTV2_BF16 && dy_pitch == K && wgrad16_w8_shape_ok(M, C, K, KH, KW, x_pitch, groups)) {
+    a.splits = wgrad16_w8_splits(M, K, a.Kred);
+    a.chunks_per_split = cdiv(cdiv(M, WGRAD_W8_BP), a.splits);
+    a.bias_ws = nullptr;
+    const int smem = 2 * 2 * WGRAD_W8_BP * 512;
+    static LdsOptIn pp_opt_in;
+    pp_opt_in({(const void*)conv_wgrad_bf16_pp}, smem);
+    hipLaunchKernelGGL(conv_wgrad_bf16_pp, dim3(wgrad16_w8_budget()), dim3(512), smem, stream, a);
+    if (int rc = wgrad16_tail(pending, 0, ws, dw, rowscale, n, a.splits, accumulate, a.Kred, stream)) return rc;
+    if (db) {   // the bias gradient as a pass of its own: per-row-block column sums of dy behind the weight slabs
+      float* part = ws + (size_t)a.splits * n;
+      int nb = cdiv(M, 64);
+      if (nb > WGRAD_W8_MAX_NB) nb = WGRAD_W8_MAX_NB;
+      const int rows = cdiv(M, nb);
+      nb = cdiv(M, rows);
+      hipLaunchKernelGGL(colsum_bf16_partial, dim3(nb), dim3(256), 0, stream, (const h16_t*)dy, part, M, K, rows);
+      if (int rc = wgrad16_tail(pending, 2, part, db, rowscale, (size_t)K, nb, accumulate, 1, stream)) return rc;
+    }
+    return utv2_launch_status();
+  }
+  a.splits = wgrad16_small_splits(M, K, a.Kred);
+  a.chunks_per_split = cdiv(cdiv(M, 32), a.splits);
+  a.bias_ws = db ? ws + (size_t)a.splits * n : nullptr;   // bias slabs sit behind the weight slabs
+  const int tiles = cdiv(K, 128) * cdiv(a.Kred, 128);
+  const dim3 g(tiles * a.splits), b(256);
+  with_types(x_dtype, dy_dtype, [&](auto tx, auto tdy) { hipLaunchKernelGGL((conv_wgrad_bf16<TAG_T(tx), TAG_T(tdy)>), g, b, 0, stream, a); });
+  if (int rc = wgrad16_tail(pending, 0, ws, dw, rowscale, n, a.splits, accumulate, a.Kred, stream)) return rc;
+  if (db)
+    if (int rc = wgrad16_tail(pending, 1, a.bias_ws, db, rowscale, (size_t)K, a.splits, accumulate, 1, stream)) return rc;
+  return utv2_launch_status();
 }
 
 int utv2_conv2d_wgrad_bf16_g(const void* x, int x_dtype, int x_pitch, const void* dy, int dy_dtype, int dy_pitch, float* dw, float* db,
                              float* ws, const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
                              int groups, hipStream_t stream) {
   return wgrad_bf16_impl(x, x_dtype, x_pitch, dy, dy_dtype, dy_pitch, dw, db, ws, rowinfo, rowscale, M, C, K, KH, KW, accumulate, groups,
-                         stream);
+                         stream, nullptr);
 }
 
 // The same with the split-K tail RECORDED in a caller-owned pending table instead of launched (see reduce_slabs_table): dw / db hold the
@@ -2558,75 +2547,6 @@ int utv2_wgrad_fold_flush(void* pending, hipStream_t stream) {
   hipLaunchKernelGGL(reduce_slabs_table, dim3(t->total_blocks), dim3(256), 0, stream, *t);
   t->count = 0;
   t->total_blocks = 0;
-  return utv2_launch_status();
-}
-
-static int wgrad_bf16_impl(const void* x, int x_dtype, int x_pitch, const void* dy, int dy_dtype, int dy_pitch, float* dw, float* db,
-                           float* ws, const int* rowinfo, const float* rowscale, int M, int C, int K, int KH, int KW, int accumulate,
-                           int groups, hipStream_t stream, SlabFoldTable* pending) {
-  if (!x || !dy || !dw || !ws || !rowinfo || (C & 7) || (K & 7) || M <= 0 || KH * KW > 16 || bad_dtype(x_dtype) ||
-      bad_dtype(dy_dtype) || groups < 1 || K % groups || x_pitch < groups * C || (groups > 1 && (K / groups) % 128) ||
-      (x_pitch != C && (x_pitch & (x_dtype == UTV2_BF16 ? 7 : 3))) || dy_pitch < K || (dy_pitch != K && (dy_pitch & (dy_dtype == UTV2_BF16 ? 7 : 3))))
-    return UTV2_EARG;
-  Wgrad16Args a;
-  a.x = x; a.dy = dy; a.ws = ws; a.rowinfo = (const int2*)rowinfo;
-  a.C = C; a.K = K; a.KH = KH; a.KW = KW; a.Kred = KH * KW * C; a.M = M; a.debug = 0; a.xs = x_pitch; a.groups = groups; a.dys = dy_pitch;
-  if (g_use_wgrad_w8 && x_dtype == UTV2_BF16 && dy_dtype == UTV2_BF16 && dy_pitch == K && wgrad16_w8_shape_ok(M, C, K, KH, KW, x_pitch, groups)) {
-    a.splits = wgrad16_w8_splits(M, K, a.Kred);
-    a.chunks_per_split = cdiv(cdiv(M, WGRAD_W8_BP), a.splits);
-    a.bias_ws = nullptr;
-    const size_t n = (size_t)K * a.Kred;
-    const int smem = 2 * 2 * WGRAD_W8_BP * 512;
-    static LdsOptIn pp_opt_in;
-    pp_opt_in({(const void*)conv_wgrad_bf16_pp}, smem);
-    hipLaunchKernelGGL(conv_wgrad_bf16_pp, dim3(wgrad16_w8_budget()), dim3(512), smem, stream, a);
-    int rb = cdiv((int64_t)n / 4, 256);
-    if (rb > 8192) rb = 8192;
-    if (pending) {
-      if (int rc = slab_fold_add(pending, 0, ws, dw, rowscale, n, a.splits, accumulate, a.Kred)) return rc;
-    } else
-      hipLaunchKernelGGL(reduce_slabs16_f32, dim3(rb), dim3(256), 0, stream, (const float*)ws, dw, n, a.splits, accumulate, rowscale,
-                         a.Kred);
-    if (db) {
-      float* part = ws + (size_t)a.splits * n;
-      int nb = cdiv(M, 64);
-      if (nb > WGRAD_W8_MAX_NB) nb = WGRAD_W8_MAX_NB;
-      const int rows = cdiv(M, nb);
-      nb = cdiv(M, rows);
-      hipLaunchKernelGGL(colsum_bf16_partial, dim3(nb), dim3(256), 0, stream, (const h16_t*)dy, part, M, K, rows);
-      if (pending) {
-        if (int rc = slab_fold_add(pending, 2, part, db, rowscale, (size_t)K, nb, accumulate, 1)) return rc;
-      } else
-        hipLaunchKernelGGL(colsum_final_f32, dim3(cdiv(K, 32)), dim3(256), 0, stream, (const float*)part, db, nb, K, accumulate, rowscale);
-    }
-    return utv2_launch_status();
-  }
-  a.splits = utv2_conv2d_wgrad_bf16_splits(M, K, a.Kred);
-  a.chunks_per_split = cdiv(cdiv(M, 32), a.splits);
-  const size_t n = (size_t)K * a.Kred;
-  a.bias_ws = db ? ws + (size_t)a.splits * n : nullptr;   // bias slabs sit behind the weight slabs
-  const int tiles = cdiv(K, 128) * cdiv(a.Kred, 128);
-  const dim3 g(tiles * a.splits), b(256);
-  if (x_dtype == UTV2_BF16) {
-    if (dy_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_wgrad_bf16<h16_t, h16_t>), g, b, 0, stream, a);
-    else hipLaunchKernelGGL((conv_wgrad_bf16<h16_t, float>), g, b, 0, stream, a);
-  } else {
-    if (dy_dtype == UTV2_BF16) hipLaunchKernelGGL((conv_wgrad_bf16<float, h16_t>), g, b, 0, stream, a);
-    else hipLaunchKernelGGL((conv_wgrad_bf16<float, float>), g, b, 0, stream, a);
-  }
-  int rb = cdiv((int64_t)n / 4, 256);   // n = K * Kred, both multiples of 8
-  if (rb > 8192) rb = 8192;
-  if (pending) {
-    if (int rc = slab_fold_add(pending, 0, ws, dw, rowscale, n, a.splits, accumulate, a.Kred)) return rc;
-    if (db)
-      if (int rc = slab_fold_add(pending, 1, a.bias_ws, db, rowscale, (size_t)K, a.splits, accumulate, 1)) return rc;
-    return utv2_launch_status();
-  }
-  hipLaunchKernelGGL(reduce_slabs16_f32, dim3(rb), dim3(256), 0, stream, (const float*)ws, dw, n, a.splits, accumulate, rowscale,
-                       a.Kred);
-  if (db)
-    hipLaunchKernelGGL(reduce_slabs16_scalar_f32, dim3(cdiv(K, 256)), dim3(256), 0, stream, (const float*)a.bias_ws, db, (size_t)K,
-                       a.splits, accumulate, rowscale);
   return utv2_launch_status();
 }
 

@@ -1039,12 +1039,10 @@ def conv2d_fwd_bf16(x, w16, scale=None, bias=None, residual=None, stride=1, pad=
         ri = rowinfo_nhwc(N, H, W, OH, OW, stride, pad, kh, kw, x.device)   # the table the weight gradient of this conv reads
     if relu_bits is not None:
         assert out.dtype == h16_dtype()
-        call("utv2_conv2d_nhwc_fwd_bf16_bits", _p(x), _dt(x), _p(w16), _p(out), _same_dt(out, residual, mask, post_mask), _p(scale), _p(bias),
-             _p(residual), _p(mask), _p(post_mask), N, H, W, C, K, kh, kw, stride, pad, in_dil, OH, OW, int(relu), int(accumulate), _p(ri),
-             _p(_bits_ok(relu_bits, out.shape)), c_p(0), c_p(0), _stream())
-        return out
-    call("utv2_conv2d_nhwc_fwd_bf16_ri", _p(x), _dt(x), _p(w16), _p(out), _same_dt(out, residual, mask, post_mask), _p(scale), _p(bias),
-         _p(residual), _p(mask), _p(post_mask), N, H, W, C, K, kh, kw, stride, pad, in_dil, OH, OW, int(relu), int(accumulate), _p(ri), _stream())
+        relu_bits = _bits_ok(relu_bits, out.shape)
+    call("utv2_conv2d_nhwc_fwd_bf16_bits", _p(x), _dt(x), _p(w16), _p(out), _same_dt(out, residual, mask, post_mask), _p(scale), _p(bias),
+         _p(residual), _p(mask), _p(post_mask), N, H, W, C, K, kh, kw, stride, pad, in_dil, OH, OW, int(relu), int(accumulate), _p(ri),
+         _p(relu_bits), None, None, _stream())
     return out
 
 
@@ -1081,13 +1079,11 @@ def conv2d_dgrad_bf16(dy, wt16, in_shape, stride, pad, kh, kw, out=None, out_dty
         ri = rowinfo_nhwc(N, OH, OW, H, W, 1, kh - 1 - pad, kh, kw, dy.device)   # dgrad = a stride-1 conv over dy with pad k-1-pad
     if mask_bits is not None or post_mask_bits is not None:
         assert out.dtype == h16_dtype() and (mask is None or mask_bits is None) and (post_mask is None or post_mask_bits is None)
-        call("utv2_conv2d_nhwc_fwd_bf16_bits", _p(dy), _dt(dy), _p(wt16), _p(out), _same_dt(out, residual, mask, post_mask), c_p(0), c_p(0),
-             _p(residual), _p(mask), _p(post_mask), N, OH, OW, K, C, kh, kw, 1, kh - 1 - pad, stride, H, W, 0, 0, _p(ri), c_p(0),
-             _p(_bits_ok(mask_bits, out.shape)) if mask_bits is not None else c_p(0),
-             _p(_bits_ok(post_mask_bits, out.shape)) if post_mask_bits is not None else c_p(0), _stream())
-        return out
-    call("utv2_conv2d_nhwc_fwd_bf16_ri", _p(dy), _dt(dy), _p(wt16), _p(out), _same_dt(out, residual, mask, post_mask), c_p(0), c_p(0),
-         _p(residual), _p(mask), _p(post_mask), N, OH, OW, K, C, kh, kw, 1, kh - 1 - pad, stride, H, W, 0, 0, _p(ri), _stream())
+        mask_bits = _bits_ok(mask_bits, out.shape) if mask_bits is not None else None
+        post_mask_bits = _bits_ok(post_mask_bits, out.shape) if post_mask_bits is not None else None
+    call("utv2_conv2d_nhwc_fwd_bf16_bits", _p(dy), _dt(dy), _p(wt16), _p(out), _same_dt(out, residual, mask, post_mask), None, None,
+         _p(residual), _p(mask), _p(post_mask), N, OH, OW, K, C, kh, kw, 1, kh - 1 - pad, stride, H, W, 0, 0, _p(ri), None,
+         _p(mask_bits), _p(post_mask_bits), _stream())
     return out
 
 
@@ -1139,14 +1135,12 @@ def conv2d_ml_fwd_bf16(x2d, w16, level_hw, N, scale=None, bias=None, residual=No
     if (_CONV_ROWINFO and k > 1 and x2d.dtype == h16_dtype() and C % 32 == 0 and K % 4 == 0 and xpitch % 8 == 0 and ypitch % 8 == 0
             and (groups == 1 or (K // groups) % 128 == 0) and P * xpitch < (1 << 31)):
         ri = rowinfo_ml(N, level_hw, pad, k, x2d.device)
-    if groups == 1 and xpitch == C and ypitch == K and gn_part is None and ri is None:
-        call("utv2_conv2d_ml_fwd_bf16", xp, _dt(x2d), _p(w16), yp, _same_dt(out, residual), _p(scale), _p(bias), _p(residual),
-             len(level_hw), ctypes.cast(H, c_p), ctypes.cast(W, c_p), N, C, K, k, k, pad, int(relu), 0, _stream())
-    else:
-        assert residual is None or (residual.stride(0) == ypitch and residual.stride(1) == 1)
-        call("utv2_conv2d_ml_fwd_bf16_g", xp, _dt(x2d), xpitch, _p(w16), yp, _same_dt(out, residual), ypitch, _p(scale), _p(bias),
-             c_p(residual.data_ptr()) if residual is not None else c_p(0), len(level_hw), ctypes.cast(H, c_p), ctypes.cast(W, c_p), N, C, K,
-             k, k, pad, int(relu), 0, int(groups), _p(gn_part), _p(ri), _stream())
+    rp = None
+    if residual is not None:   # y's rows: contiguous when y is dense, else the same column slice of a matrix of y's pitch
+        assert residual.stride(0) == ypitch and residual.stride(1) == 1
+        rp = _p(residual) if ypitch == K else residual.data_ptr()
+    call("utv2_conv2d_ml_fwd_bf16_g", xp, _dt(x2d), xpitch, _p(w16), yp, _same_dt(out, residual), ypitch, _p(scale), _p(bias), rp,
+         len(level_hw), ctypes.cast(H, c_p), ctypes.cast(W, c_p), N, C, K, k, k, pad, int(relu), 0, int(groups), _p(gn_part), _p(ri), _stream())
     return out
 
 
@@ -1267,22 +1261,18 @@ def conv2d_wgrad_bf16(x, dy2d, dw, rowinfo, C, kh, kw, accumulate=True, db=None,
     assert dy2d.stride(1) == 1
     dy_pitch = int(dy2d.stride(0))
     nws = load().utv2_conv2d_wgrad_bf16_workspace_floats(M, K, kh * kw * C)
+    pitch = int(x_pitch) if x_pitch is not None else groups * C
+    xp = _p(x) if pitch == C else x.data_ptr()            # a dense operand is a contiguous tensor; a slice of a wider matrix goes by its pitch
+    dyp = _p(dy2d) if dy_pitch == K else dy2d.data_ptr()
     lane = WGRAD_FOLD[0]
     if lane is not None:
         ws = lane.take(nws, dy2d.device, [dw.data_ptr()] + ([db.data_ptr()] if db is not None else []))
-        pitch = int(x_pitch) if x_pitch is not None else groups * C
-        call("utv2_conv2d_wgrad_bf16_d", c_p(x.data_ptr()), _dt(x), pitch, c_p(dy2d.data_ptr()), _dt(dy2d), dy_pitch, _p(dw), _p(db), _p(ws),
-             _p(rowinfo), _p(rowscale), M, C, K, kh, kw, int(accumulate), int(groups), ctypes.cast(lane.table, c_p), _stream())
-        return dw
-    ws = workspace(nws, dy2d.device, "wgrad")
-    if groups == 1 and (x_pitch is None or x_pitch == C) and dy_pitch == K:
-        call("utv2_conv2d_wgrad_bf16", _p(x), _dt(x), _p(dy2d), _dt(dy2d), _p(dw), _p(db), _p(ws), _p(rowinfo), _p(rowscale), M, C, K, kh,
-             kw, int(accumulate), _stream())
+        call("utv2_conv2d_wgrad_bf16_d", xp, _dt(x), pitch, dyp, _dt(dy2d), dy_pitch, _p(dw), _p(db), _p(ws), _p(rowinfo), _p(rowscale), M, C,
+             K, kh, kw, int(accumulate), int(groups), ctypes.cast(lane.table, c_p), _stream())
     else:
-        xp = c_p(x.data_ptr())
-        pitch = int(x_pitch) if x_pitch is not None else groups * C
-        call("utv2_conv2d_wgrad_bf16_g", xp, _dt(x), pitch, c_p(dy2d.data_ptr()), _dt(dy2d), dy_pitch, _p(dw), _p(db), _p(ws), _p(rowinfo),
-             _p(rowscale), M, C, K, kh, kw, int(accumulate), int(groups), _stream())
+        ws = workspace(nws, dy2d.device, "wgrad")
+        call("utv2_conv2d_wgrad_bf16_g", xp, _dt(x), pitch, dyp, _dt(dy2d), dy_pitch, _p(dw), _p(db), _p(ws), _p(rowinfo), _p(rowscale), M, C,
+             K, kh, kw, int(accumulate), int(groups), _stream())
     return dw
 
 
