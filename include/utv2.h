@@ -334,6 +334,33 @@ int utv2_fcos_decode(const long long* topkeys, int K, const float* logits, const
                      int N, int HW, int Wl, int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes,
                      float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
                      unsigned char* ovalid, utv2_stream_t stream);
+/* ---- the same for the CONTINUOUS regression head (MODEL.FCOS.REG_DISCRETE False: plain FCOS, fcos/fcos.py:294-297,363-364) ----
+ * box rows: [ltrb 4 | std 4 | ctr 1 | pad], the ltrb columns hold the Scale layer's output BEFORE the ReLU: every kernel here uses
+ * d = max(box[0:4], 0) (fcos_outputs.py:349-350,545-546,1107-1108) and the backward writes 0 where the stored value is <= 0 (torch's
+ * ReLU gradient at exactly 0 and at -0.0).  sums[8], flags, bvars / ts_better / ts_cert, coef / coef8 / gscale / accumulate and the row
+ * rules are those of utv2_fcos_loc_terms_fwd / _bwd / _bwd_acc above; the reduction is per-block partials summed in a fixed order.
+ * ws >= 4096 floats.
+ * Checked (UTV2_EARG otherwise, nothing is launched): non-null labels / box / reg_targets / sums / ws / coef / dbox, P >= 0,
+ * box_stride >= 9 and % 4 == 0, 0 <= flags < 32 with loc type 0..2.  P == 0: the forward writes sums = 0, the backward entries write
+ * nothing.  Rows are indexed in 64 bits.  Not checked (device data): labels (< 0 or == num_classes: no gradient), targets > 0. */
+int utv2_fcos_loc_terms_cont_fwd(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                 int64_t P, int num_classes, float ts_better, float ts_cert, int flags, float* sums, float* ws,
+                                 utv2_stream_t stream);
+int utv2_fcos_loc_terms_cont_bwd(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                 int64_t P, int num_classes, float ts_better, float ts_cert, int flags, const float* coef, float* dbox,
+                                 utv2_stream_t stream);
+int utv2_fcos_loc_terms_cont_bwd_acc(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                     int64_t P, int num_classes, float ts_better, float ts_cert, int flags, const float* coef8,
+                                     const float* gscale, float* dbox, int accumulate, utv2_stream_t stream);
+/* utv2_fcos_decode for those rows: ltrb = max(r, 0) * stride, every other output as there.  The ranking keys come from
+ * utv2_fcos_rank_keys with reg_max = 0 (it finds std / ctr at 4 * (reg_max + 1) = 4: this layout).
+ * Checked: non-null pointers (outputs included), box_stride >= 9 and % 4 == 0, K >= 0, 1 <= N <= 65535, HW, Wl, C, stride >= 1,
+ * Wl <= HW, HW * C < 2^32, method 0..3, slot0 >= 0, slot0 + K <= MAXC.  K == 0 writes nothing.  A key >= 0 whose index lies outside
+ * HW * C (no utv2_fcos_rank_keys output) becomes an empty slot. */
+int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
+                          int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
+                          float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid,
+                          utv2_stream_t stream);
 /* Scale layer fcos/fcos.py:22-28,356-357 on the first ncols columns of strided rows */
 int utv2_scale_cols(float* y, int64_t rows, int row_stride, int ncols, const float* s, utv2_stream_t stream);
 int utv2_scale_cols_bwd(float* g, const float* ypost, int64_t rows, int row_stride, int ncols, const float* s, float* dsum,

@@ -645,6 +645,193 @@ __global__ __launch_bounds__(128) void fcos_decode_kernel(const long long* __res
   ovalid[s] = 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same positive-location terms and decode for the CONTINUOUS regression head (MODEL.FCOS.REG_DISCRETE False: the plain FCOS head,
+// fcos/fcos.py:294-297,363-364; the scalar distances go straight into the losses, fcos_outputs.py:349-350,545-546, and into the
+// decode, :1107-1108).  box rows: [ltrb 4 | std 4 | ctr 1 | pad], row stride BS floats.  The buffer holds the Scale layer's output
+// BEFORE the ReLU: d_b = max(row[b], 0) is taken on read here, and the backward writes 0 where the stored value is <= 0 (torch's
+// convention at exactly 0, and at -0.0) - the conv epilogue and the Scale kernels are the discrete head's, unchanged.
+#define CT_STD 4
+#define CT_CTR 8
+#define CT_COLS 9
+
+__global__ __launch_bounds__(128) void fcos_loc_cont_fwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
+                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
+                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
+                                                              float* __restrict__ partial) {
+  __shared__ float red[2];
+  float acc[LT_NSUM];
+#pragma unroll
+  for (int k = 0; k < LT_NSUM; ++k) acc[k] = 0.f;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < P; i += stride) {
+    const int lab = labels[i];
+    if (lab < 0 || lab == num_classes) continue;
+    const float* row = box + i * BS;
+    float d[4], t[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { d[b] = fmaxf(row[b], 0.f); t[b] = reg_targets[i * 4 + b]; }
+    float ctr_t = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
+    float iou;
+    const float gl = giou_ltrb(d, t, &iou, nullptr, (flags >> LT_LOC_SHIFT) & 3);
+    if (flags & LT_QUALITY_IOU) ctr_t = iou;
+    float nll = 0.f;
+    const float* sp = row + CT_STD;
+    if (flags & LT_KLLOSS) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float n = fabsf(d[b] - t[b]);
+        nll += expf(-sp[b]) * (n < 1.f ? 0.5f * n * n : n - 0.5f) + 0.5f * sp[b];
+      }
+      iou = (flags & LT_KL_WCTR) ? ctr_t : 1.f;
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float sg = 1.f / (1.f + expf(-sp[b]));
+        const float sq = sg * sg;
+        const float df = t[b] - d[b];
+        nll += (df * df) / (2.f * sq) + 0.5f * logf(sq);
+      }
+      nll += 2.f * logf(2.f * 3.14159265358979323846f);
+    }
+    const float c = row[CT_CTR];
+    const float bce = fmaxf(c, 0.f) - c * ctr_t + log1pf(expf(-fabsf(c)));
+    acc[0] += 1.f;
+    acc[1] += ctr_t;
+    acc[2] += bce;
+    acc[3] += gl * ctr_t;
+    acc[4] += nll * iou;
+    if (bvars) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
+        const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
+        if (ct > ts_cert && ct > cs + ts_better) {
+          acc[5] += 1.f;
+          acc[6] += fabsf(d[b] - t[b]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < LT_NSUM; ++k) {
+    const float s = block_reduce_sum(acc[k], red);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * LT_NSUM + k] = s;
+  }
+}
+
+// coef / coef8 / gscale / accumulate: as fcos_loc_bwd_kernel.  One thread per row, the row's arithmetic in double and rounded once per
+// output element like the discrete kernel's (positive rows only: the fp64 rate does not show); the teacher-better selection in fp32,
+// bit for bit the forward's.
+__global__ __launch_bounds__(128) void fcos_loc_cont_bwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
+                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
+                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
+                                                              const float* __restrict__ coef, float* __restrict__ dbox,
+                                                              const float* __restrict__ gscale, int coef8, int accumulate) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const float gs = gscale ? gscale[0] : 1.f;
+  const float c_bce = coef[coef8 ? 2 : 0] * gs, c_giou = coef[coef8 ? 3 : 1] * gs, c_nll = coef[coef8 ? 4 : 2] * gs,
+              c_l1 = coef[coef8 ? 6 : 3] * gs;
+  const int lab = labels[i];
+  float* grow = dbox + i * BS;
+  if (lab < 0 || lab == num_classes) {
+    if (!accumulate)
+      for (int k = 0; k < BS; ++k) grow[k] = 0.f;
+    return;
+  }
+  const float* row = box + i * BS;
+  double d[4], t[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) { d[b] = (double)fmaxf(row[b], 0.f); t[b] = (double)reg_targets[i * 4 + b]; }
+  double ctr_t = sqrt((fmin(t[0], t[2]) / fmax(t[0], t[2])) * (fmin(t[1], t[3]) / fmax(t[1], t[3])));
+  double iou, gg[4];
+  giou_ltrb_f64(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
+  if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
+  const float* sp = row + CT_STD;
+  float gout[CT_COLS];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const double sg = 1.0 / (1.0 + exp(-(double)sp[b]));
+    const double df = t[b] - d[b];
+    double dd, ds;
+    if (flags & LT_KLLOSS) {
+      const double n = fabs(df), es = exp(-(double)sp[b]);
+      const double sgn = df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0);
+      const double wk = (flags & LT_KL_WCTR) ? ctr_t : 1.0;   // a detached target
+      dd = (double)c_giou * ctr_t * gg[b] + (double)c_nll * wk * es * fmin(n, 1.0) * sgn;
+      ds = (double)c_nll * wk * (0.5 - es * (n < 1.0 ? 0.5 * n * n : n - 0.5));
+    } else {
+      dd = (double)c_giou * ctr_t * gg[b] + (double)c_nll * iou * (-df / (sg * sg));
+      ds = (double)c_nll * iou * (1.0 - sg) * (1.0 - (df * df) / (sg * sg));
+    }
+    if (bvars) {
+      const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
+      const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
+      if (ct > ts_cert && ct > cs + ts_better) dd += (double)c_l1 * (df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0));
+    }
+    gout[b] = row[b] > 0.f ? (float)dd : 0.f;   // ReLU: no gradient at or below 0
+    gout[CT_STD + b] = (float)ds;
+  }
+  const double c = (double)row[CT_CTR];
+  gout[CT_CTR] = (float)((double)c_bce * (1.0 / (1.0 + exp(-c)) - ctr_t));
+  if (accumulate) {
+#pragma unroll
+    for (int k = 0; k < CT_COLS; ++k) grow[k] += gout[k];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < CT_COLS; ++k) grow[k] = gout[k];
+  for (int k = CT_COLS; k < BS; ++k) grow[k] = 0.f;
+}
+
+// fcos_decode_kernel for the continuous rows: ltrb = max(r, 0) * stride (fcos_outputs.py:1107-1108).  A key whose flat index lies outside
+// this level's HW * C (it cannot come from utv2_fcos_rank_keys) is written as an empty slot, never followed.
+__global__ __launch_bounds__(128) void fcos_decode_cont_kernel(const long long* __restrict__ topkeys, int K, const float* __restrict__ logits,
+                                                             const float* __restrict__ box, int BS, int HW, int Wl, int C, int stride,
+                                                             int level, int method, int MAXC, int slot0, float* __restrict__ oboxes,
+                                                             float* __restrict__ oscores, int* __restrict__ ocls, float* __restrict__ oloc,
+                                                             float* __restrict__ octr, float* __restrict__ oconf, float* __restrict__ ostd,
+                                                             int* __restrict__ olevel, unsigned char* __restrict__ ovalid) {
+  const int n = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const size_t s = (size_t)n * MAXC + slot0 + k;
+  const long long key = topkeys[(size_t)n * K + k];
+  const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFll);
+  if (key < 0 || (unsigned long long)flat >= (unsigned long long)HW * (unsigned long long)C) {
+    ovalid[s] = 0;
+    oscores[s] = -1.f;
+    ocls[s] = 0;
+    olevel[s] = level;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { oboxes[s * 4 + e] = 0.f; ostd[s * 4 + e] = 0.f; }
+    oloc[s * 2] = 0.f; oloc[s * 2 + 1] = 0.f; octr[s] = 0.f; oconf[s] = 0.f;
+    return;
+  }
+  const float rank = __uint_as_float((unsigned)(key >> 32));
+  const int hw = flat / C, c = flat - hw * C;
+  const size_t row = (size_t)n * HW + hw;
+  const float* br = box + row * BS;
+  const int y = hw / Wl, x = hw - y * Wl;
+  const float lx = (float)(x * stride) + (float)(stride / 2), ly = (float)(y * stride) + (float)(stride / 2);
+  const float fs = (float)stride;
+  oboxes[s * 4 + 0] = lx - fmaxf(br[0], 0.f) * fs;
+  oboxes[s * 4 + 1] = ly - fmaxf(br[1], 0.f) * fs;
+  oboxes[s * 4 + 2] = lx + fmaxf(br[2], 0.f) * fs;
+  oboxes[s * 4 + 3] = ly + fmaxf(br[3], 0.f) * fs;
+  oscores[s] = (method == 1 || method == 3) ? sqrtf(rank) : rank;
+  ocls[s] = c;
+  oloc[s * 2] = lx; oloc[s * 2 + 1] = ly;
+  octr[s] = 1.f / (1.f + expf(-br[CT_CTR]));
+  oconf[s] = 1.f / (1.f + expf(-logits[row * C + c]));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ostd[s * 4 + e] = br[CT_STD + e];
+  olevel[s] = level;
+  ovalid[s] = 1;
+}
+
 // in-place y[:, 0:ncols] *= s[0] on rows of stride BS (Scale layer, fcos/fcos.py:22-28,356-357)
 __global__ __launch_bounds__(256) void scale_cols_kernel(float* __restrict__ y, size_t rows, int BS, int ncols, const float* __restrict__ s) {
   const size_t total = rows * (size_t)ncols;
@@ -970,6 +1157,57 @@ int utv2_fcos_decode(const long long* topkeys, int K, const float* logits, const
   hipLaunchKernelGGL((fcos_decode_kernel<17>), dim3(cdiv(K, 128), N), dim3(128), 0, stream, topkeys, K, logits, box, box_stride,
                      HW, Wl, C, stride, level, method, MAXC, slot0, oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel,
                      ovalid);
+  return utv2_launch_status();
+}
+
+// ---- continuous regression head (REG_DISCRETE False): rows [ltrb 4 | std 4 | ctr 1 | pad] -------------------------------------------
+static bool loc_cont_args_bad(const void* labels, const void* box, int box_stride, const void* reg_targets, int64_t P, int flags) {
+  return !labels || !box || !reg_targets || flags < 0 || flags >= 32 || ((flags >> LT_LOC_SHIFT) & 3) > 2 || box_stride < CT_COLS ||
+         (box_stride & 3) || P < 0;
+}
+
+int utv2_fcos_loc_terms_cont_fwd(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                 int64_t P, int num_classes, float ts_better, float ts_cert, int flags, float* sums, float* ws,
+                                 hipStream_t stream) {
+  if (loc_cont_args_bad(labels, box, box_stride, reg_targets, P, flags) || !sums || !ws) return UTV2_EARG;
+  int nb = (int)(P < (int64_t)LOC_BLOCKS * 128 ? cdiv(P, 128) : LOC_BLOCKS);
+  if (nb < 1) nb = 1;   // P == 0: one block with no row writes the zero partials
+  hipLaunchKernelGGL(fcos_loc_cont_fwd_kernel, dim3(nb), dim3(128), 0, stream, labels, box, box_stride, reg_targets, bvars, (size_t)P,
+                     num_classes, ts_better, ts_cert, flags, ws);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(LT_NSUM), dim3(256), 0, stream, (const float*)ws, nb, LT_NSUM, sums);
+  return utv2_launch_status();
+}
+
+int utv2_fcos_loc_terms_cont_bwd(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                 int64_t P, int num_classes, float ts_better, float ts_cert, int flags, const float* coef, float* dbox,
+                                 hipStream_t stream) {
+  if (loc_cont_args_bad(labels, box, box_stride, reg_targets, P, flags) || !coef || !dbox || cdiv(P, 128) > 0x7fffffffll) return UTV2_EARG;
+  if (P == 0) return UTV2_OK;
+  hipLaunchKernelGGL(fcos_loc_cont_bwd_kernel, dim3((unsigned)cdiv(P, 128)), dim3(128), 0, stream, labels, box, box_stride, reg_targets,
+                     bvars, (size_t)P, num_classes, ts_better, ts_cert, flags, coef, dbox, (const float*)nullptr, 0, 0);
+  return utv2_launch_status();
+}
+
+int utv2_fcos_loc_terms_cont_bwd_acc(const int* labels, const float* box, int box_stride, const float* reg_targets, const float* bvars,
+                                     int64_t P, int num_classes, float ts_better, float ts_cert, int flags, const float* coef8,
+                                     const float* gscale, float* dbox, int accumulate, hipStream_t stream) {
+  if (loc_cont_args_bad(labels, box, box_stride, reg_targets, P, flags) || !coef8 || !dbox || cdiv(P, 128) > 0x7fffffffll) return UTV2_EARG;
+  if (P == 0) return UTV2_OK;
+  hipLaunchKernelGGL(fcos_loc_cont_bwd_kernel, dim3((unsigned)cdiv(P, 128)), dim3(128), 0, stream, labels, box, box_stride, reg_targets,
+                     bvars, (size_t)P, num_classes, ts_better, ts_cert, flags, coef8, dbox, gscale, 1, accumulate ? 1 : 0);
+  return utv2_launch_status();
+}
+
+int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
+                          int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
+                          float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid, hipStream_t stream) {
+  if (!topkeys || !logits || !box || !oboxes || !oscores || !ocls || !oloc || !octr || !oconf || !ostd || !olevel || !ovalid ||
+      box_stride < CT_COLS || (box_stride & 3) || K < 0 || N < 1 || N > 65535 || HW < 1 || Wl < 1 || Wl > HW || C < 1 || stride < 1 ||
+      method < 0 || method > 3 || slot0 < 0 || MAXC < 0 || (int64_t)slot0 + K > MAXC || (int64_t)HW * C > 0xFFFFFFFFll)
+    return UTV2_EARG;
+  if (K == 0) return UTV2_OK;
+  hipLaunchKernelGGL(fcos_decode_cont_kernel, dim3(cdiv(K, 128), N), dim3(128), 0, stream, topkeys, K, logits, box, box_stride, HW, Wl, C,
+                     stride, level, method, MAXC, slot0, oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel, ovalid);
   return utv2_launch_status();
 }
 

@@ -610,6 +610,47 @@ def fcos_decode(topkeys, logits, box, reg_max, N, HW, Wl, stride, level, method,
          _p(outs["cls_confid"]), _p(outs["reg_pred_std"]), _p(outs["fpn_levels"]), _p(outs["valid"]), _stream())
 
 
+# continuous regression head (MODEL.FCOS.REG_DISCRETE False): box rows [ltrb 4 | std 4 | ctr 1 | pad], ReLU taken on read.  The callers
+# (ops / modeling.fcos) name this mode by REG_CONT in the place of reg_max: 4 * (REG_CONT + 1) = 4 is where std starts, which is also
+# how utv2_fcos_rank_keys finds std / ctr in these rows.
+REG_CONT = 0
+
+
+def fcos_loc_terms_cont_fwd(labels, box, reg_targets, bvars, num_classes, ts_better, ts_cert, flags=0):
+    P, BS = box.shape
+    sums = torch.empty(8, dtype=torch.float32, device=box.device)
+    ws = workspace(4096, box.device, "loss")
+    call("utv2_fcos_loc_terms_cont_fwd", _p(labels), _p(box), BS, _p(reg_targets), _p(bvars), P, num_classes, float(ts_better),
+         float(ts_cert), int(flags), _p(sums), _p(ws), _stream())
+    return sums
+
+
+def fcos_loc_terms_cont_bwd(labels, box, reg_targets, bvars, num_classes, ts_better, ts_cert, coef, out=None, flags=0):
+    P, BS = box.shape
+    if out is None:
+        out = torch.empty_like(box)
+    call("utv2_fcos_loc_terms_cont_bwd", _p(labels), _p(box), BS, _p(reg_targets), _p(bvars), P, num_classes, float(ts_better),
+         float(ts_cert), int(flags), _p(coef), _p(out), _stream())
+    return out
+
+
+def fcos_loc_terms_cont_bwd_acc(labels, box, reg_targets, bvars, num_classes, ts_better, ts_cert, coef8, gscale, out, accumulate, flags=0):
+    P, BS = box.shape
+    call("utv2_fcos_loc_terms_cont_bwd_acc", _p(labels), _p(box), BS, _p(reg_targets), _p(bvars), P, num_classes, float(ts_better),
+         float(ts_cert), int(flags), _p(coef8), _p(gscale), _p(out), int(bool(accumulate)), _stream())
+    return out
+
+
+def fcos_decode_cont(topkeys, logits, box, N, HW, Wl, stride, level, method, slot0, outs):
+    K = topkeys.shape[1]
+    C = logits.shape[-1]
+    BS = box.shape[-1]
+    MAXC = outs["scores"].shape[1]
+    call("utv2_fcos_decode_cont", _p(topkeys), K, _p(logits), _p(box), BS, N, HW, Wl, C, stride, level, method, MAXC, slot0,
+         _p(outs["boxes"]), _p(outs["scores"]), _p(outs["classes"]), _p(outs["locations"]), _p(outs["centerness"]),
+         _p(outs["cls_confid"]), _p(outs["reg_pred_std"]), _p(outs["fpn_levels"]), _p(outs["valid"]), _stream())
+
+
 def scale_cols(y2d, ncols, s):
     rows, BS = y2d.shape
     call("utv2_scale_cols", _p(y2d), rows, BS, ncols, _p(s), _stream())

@@ -7,6 +7,7 @@ arguments, re-laid-out for MI355X:
   * head outputs of all levels are written by the convs straight into two level-first
     [P, 80] buffers (cls logits; box = 68 reg bins | 4 std | 1 ctr | 7 pad): the reference's
     permute/reshape/cat (fcos_outputs.py:261-290) never exists;
+    With MODEL.FCOS.REG_DISCRETE False (plain FCOS) the box buffer is [P, 16]: 4 ltrb (pre-ReLU) | 4 std | 1 ctr | 7 pad;
   * bbox_pred / bbox_pred_std / ctrness share one fused 256->80 conv (their weights are adjacent
     rows of one arena matrix; state_dict still exposes the three reference tensors);
   * targets, focal, and the positive-location losses are dense kernels over all locations with
@@ -28,6 +29,10 @@ from .backbone import _nchw_view
 INF = 100000000
 METHODS = {"cls": 0, "cls_n_ctr": 1, "ctr": 2, "cls_n_loc": 3}
 BOX_STRIDE = 80  # 4*(REG_MAX+1) + 4 + 1 = 73 -> padded to 80 (multiple of 16 for the dgrad fast path)
+# MODEL.FCOS.REG_DISCRETE False (the plain FCOS head): 4 ltrb + 4 std + 1 ctr = 9 -> 16, the smallest width every conv entry point the
+# box head goes through takes as it is (channels % 8 in the 16-bit forward, dgrad and weight gradient; the fp32 dgrad reads the gradient
+# as a conv input and asks for % 16) - see DESIGN.md "Continuous box regression"
+BOX_STRIDE_CONT = 16
 
 
 class PaddedBoxes:
@@ -218,6 +223,7 @@ class RawOutput(dict):
     def __init__(self, head_out, level_hw, image_sizes, strides, reg_max):
         super().__init__(head_out=head_out, level_hw=level_hw, image_sizes=image_sizes)
         self._strides, self._nreg = list(strides), 4 * (reg_max + 1)
+        self._cont = reg_max == hip.REG_CONT   # continuous head: the buffer holds the pre-ReLU distances, `reg_pred` shows F.relu of them
 
     def __missing__(self, key):
         if key not in self._LAZY:
@@ -231,6 +237,8 @@ class RawOutput(dict):
             v = nchw(ho["logits"], 0, ho["logits"].shape[1])
         elif key == "reg_pred":
             v = nchw(ho["box"], 0, R)
+            if self._cont:      # fcos/fcos.py:364 (a copy: the only place the post-ReLU tensor exists)
+                v = [torch.relu(x) for x in v]
         elif key == "reg_pred_std":
             v = nchw(ho["box"], R, R + 4)
         elif key == "ctrness_pred":
@@ -259,12 +267,16 @@ class FCOSHead:
     def __init__(self, cfg, store, in_channels, prefix):
         fc = cfg.MODEL.FCOS
         assert fc.NORM == "GN", "only the GN towers of the shipped configs are built"
-        assert fc.REG_DISCRETE and fc.REG_MAX == 16, "UTv2 FCOS configs: REG_DISCRETE, REG_MAX 16"
+        assert not fc.REG_DISCRETE or fc.REG_MAX == 16, "the discrete (GFocal) head is built for REG_MAX 16"
+        # REG_DISCRETE False (the config default; plain FCOS, fcos/fcos.py:294-297,363-364): bbox_pred is a 256 -> 4 conv followed by
+        # Scale and ReLU.  Fused row [ltrb 4 | std 4 | ctr 1 | pad 7]; conv epilogue and Scale are the discrete head's, the ReLU is taken
+        # by the loss / decode kernels when they read the row (utv2_fcos_loc_terms_cont_*, utv2_fcos_decode_cont).
+        self.reg_discrete = bool(fc.REG_DISCRETE)
         # KL_LOSS False (config-reachable, fcos.py:300-307 then builds no bbox_pred_std): the fused box conv keeps its 4 std channels so
         # the [reg | std | ctr] row layout is one layout; they then receive zero gradient and no consumer reads them.
         assert not fc.USE_DEFORMABLE
         self.num_classes = fc.NUM_CLASSES
-        self.reg_max = fc.REG_MAX
+        self.reg_max = fc.REG_MAX if self.reg_discrete else hip.REG_CONT
         self.num_levels = len(fc.FPN_STRIDES)
         C = in_channels
         self.C = C
@@ -344,10 +356,16 @@ class FCOSHead:
         R4 = 4 * (self.reg_max + 1)
         self.R4 = R4
 
+        bs = BOX_STRIDE if self.reg_discrete else BOX_STRIDE_CONT
+        # the continuous head without KL_LOSS has no bbox_pred_std in the reference (fcos.py:299-302): its 4 rows stay in the fused
+        # matrix (one row layout), zero, unexported and without a draw from the random stream
+        has_std = self.reg_discrete or fc.KL_LOSS
+
         def init_box(t):
             t.zero_()
             t[:R4].normal_(0.0, 0.01)
-            t[R4:R4 + 4].normal_(0.0, 0.0001)
+            if has_std:
+                t[R4:R4 + 4].normal_(0.0, 0.0001)
             t[R4 + 4:R4 + 5].normal_(0.0, 0.01)
 
         def rows(r0, r1):
@@ -355,15 +373,18 @@ class FCOSHead:
                 return t[r0:r1].view(r1 - r0, 3, 3, C).permute(0, 3, 1, 2)
             return fn
 
-        wb = store.new((BOX_STRIDE, 9 * C), "decay", init_box)
+        wb = store.new((bs, 9 * C), "decay", init_box)
         wb.export(prefix + ".bbox_pred.weight", rows(0, R4))
-        wb.export(prefix + ".bbox_pred_std.weight", rows(R4, R4 + 4))
+        if has_std:
+            wb.export(prefix + ".bbox_pred_std.weight", rows(R4, R4 + 4))
         wb.export(prefix + ".ctrness.weight", rows(R4 + 4, R4 + 5))
-        bb = store.new((BOX_STRIDE,), "decay", lambda t: t.zero_())
+        bb = store.new((bs,), "decay", lambda t: t.zero_())
         bb.export(prefix + ".bbox_pred.bias", lambda t: t[0:R4])
-        bb.export(prefix + ".bbox_pred_std.bias", lambda t: t[R4:R4 + 4])
+        if has_std:
+            bb.export(prefix + ".bbox_pred_std.bias", lambda t: t[R4:R4 + 4])
         bb.export(prefix + ".ctrness.bias", lambda t: t[R4 + 4:R4 + 5])
-        self.box_head = ops.Conv(wb, C, BOX_STRIDE, 3, 1, 1, bias=bb, colscale=R4, out_fp32=True)
+        self.box_head = ops.Conv(wb, C, bs, 3, 1, 1, bias=bb, colscale=R4, out_fp32=True)
+        self.box_head.dgrad_pad_small = not self.reg_discrete    # 16 -> 32 gradient columns for the 16-bit dgrad, as 80 -> 96 in the discrete head
         self.scales = None
         if fc.USE_SCALE:
             self.scales = [store.new((1,), "decay", lambda t: t.fill_(1.0)).export("%s.scales.%d.scale" % (prefix, l))
@@ -414,7 +435,8 @@ class FCOSOutputs:
         self.strides = list(fc.FPN_STRIDES)
         assert not cfg.SEMISUPNET.SOFT_CLS_LABEL
         assert cfg.SEMISUPNET.CLS_LOSS_METHOD == "focal"
-        self.reg_max = fc.REG_MAX
+        # the mode of the box rows as the kernels are told it: REG_MAX (16) for the discrete head, hip.REG_CONT for REG_DISCRETE False
+        self.reg_max = fc.REG_MAX if fc.REG_DISCRETE else hip.REG_CONT
         self.unify_ctrcls = fc.UNIFY_CTRCLS
         # config-reachable variants (fcos_outputs.py:165-186): the positive-location kernels take them as flags
         self.kl_loss, self.kl_loss_type = fc.KL_LOSS, fc.KL_LOSS_TYPE
@@ -680,8 +702,11 @@ class FCOSOutputs:
             slot0 = 0
             for l, (h, w) in enumerate(level_hw):
                 r0, r1 = meta.rows[l]
-                hip.fcos_decode(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], self.reg_max, N, h * w, w, self.strides[l], l, method, slot0,
-                                outs_m)
+                if self.reg_max == hip.REG_CONT:
+                    hip.fcos_decode_cont(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], N, h * w, w, self.strides[l], l, method, slot0, outs_m)
+                else:
+                    hip.fcos_decode(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], self.reg_max, N, h * w, w, self.strides[l], l, method,
+                                    slot0, outs_m)
                 slot0 += ks[l]
         keep, cnt = hip.nms_batched(outs["boxes"], outs["scores"], outs["classes"], outs["valid"], self.nms_thresh,
                                     class_aware=True, post_topk=post, max_out=max_det)
@@ -734,7 +759,7 @@ class FCOS:
         self.fcos_head = FCOSHead(cfg, store, in_channels, prefix + ".fcos_head")
         self.fcos_head.yield_bbox_towers = self.yield_proposal
         self.fcos_outputs = FCOSOutputs(cfg)
-        # Integral.project is a persistent buffer in the reference (fcos_outputs.py:61-63): keep the key.
+        # Integral.project is a persistent buffer in the reference (fcos_outputs.py:61-63, built at :208 whatever REG_DISCRETE says): keep the key.
         self.project = store.new((fc.REG_MAX + 1,), "buffer",
                                  lambda t: t.copy_(torch.linspace(0, fc.REG_MAX, fc.REG_MAX + 1))).export(
             prefix + ".fcos_outputs.integral.project")

@@ -374,6 +374,9 @@ class Conv:
         self.kred = kred if kred is not None else k * k * cin
         self.colscale = colscale  # (Handle scalar, ncols): Scale layer on the first ncols output channels
         self.out_fp32 = out_fp32  # AMP: keep this layer's output fp32 (loss-side head outputs, RoIAlign inputs)
+        self.dgrad_pad_small = False  # set by the model builder: a layer of at most 32 output channels pads its 16-bit dgrad operand too (the
+        #                               16-channel box head of the continuous FCOS head: its dgrad writes into a column half of the paired
+        #                               towers' gradient, which the kernel only does from a 16-bit input of a multiple of 32 channels)
         self.premask_input = False  # set by the model builder: the input is a fused bottleneck's ReLU output (see premask_on)
         self.bias_by_gn = False     # set by pair_conv_gn(): the GroupNorm that consumes this conv's output produces its bias gradient
         self.gn_cpg = 0             # set by pair_conv_gn(): channels per group of that GroupNorm
@@ -409,7 +412,7 @@ class Conv:
         """output channels of the bf16 dgrad weight image: the multi-level 3x3 layers whose cout is no multiple of 32 (the 80-channel
         prediction convs) run their dgrad on a zero-padded bf16 copy of the gradient - the LDS-DMA kernel stages 32-channel chunks; the
         generic kernel took 318 us per launch on them against ~100"""
-        if self.k == 3 and self.stride == 1 and self.cout % 32 and self.cout % 8 == 0 and self.cout > 32:
+        if self.k == 3 and self.stride == 1 and self.cout % 32 and self.cout % 8 == 0 and (self.cout > 32 or self.dgrad_pad_small):
             return (self.cout + 31) // 32 * 32
         return self.cout
 
@@ -1171,6 +1174,19 @@ def focal_loss_sum(logits, labels, alpha, gamma):
     return _FocalSumFn.apply(logits, labels, alpha, gamma)
 
 
+def _loc_fwd(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, flags):
+    """the positive-location sums of the head's mode: reg_max == hip.REG_CONT names the continuous rows (REG_DISCRETE False)"""
+    if reg_max == hip.REG_CONT:
+        return hip.fcos_loc_terms_cont_fwd(labels, box, reg_targets, bvars, nc, tsb, tsc, flags=flags)
+    return hip.fcos_loc_terms_fwd(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, flags=flags)
+
+
+def _loc_bwd_acc(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, coef8, gscale, out, accumulate, flags):
+    if reg_max == hip.REG_CONT:
+        return hip.fcos_loc_terms_cont_bwd_acc(labels, box, reg_targets, bvars, nc, tsb, tsc, coef8, gscale, out, accumulate, flags=flags)
+    return hip.fcos_loc_terms_bwd_acc(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, coef8, gscale, out, accumulate, flags=flags)
+
+
 class _LocTermsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, box, labels, reg_targets, bvars, args):
@@ -1178,15 +1194,18 @@ class _LocTermsFn(torch.autograd.Function):
         ctx.has_bv = bvars is not None
         ctx.save_for_backward(box, labels, reg_targets, bvars if bvars is not None else labels)
         nc, reg_max, tsb, tsc = args[:4]
-        return hip.fcos_loc_terms_fwd(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, flags=args[4] if len(args) > 4 else 0)
+        return _loc_fwd(labels, box, reg_targets, bvars, nc, reg_max, tsb, tsc, args[4] if len(args) > 4 else 0)
 
     @staticmethod
     def backward(ctx, gsums):
         box, labels, reg_targets, bv = ctx.saved_tensors
         nc, reg_max, tsb, tsc = ctx.args[:4]
         coef = torch.stack((gsums[2], gsums[3], gsums[4], gsums[6])).contiguous().float()
-        d = hip.fcos_loc_terms_bwd(labels, box, reg_targets, bv if ctx.has_bv else None, nc, reg_max, tsb, tsc, coef,
-                                   flags=ctx.args[4] if len(ctx.args) > 4 else 0)
+        flags = ctx.args[4] if len(ctx.args) > 4 else 0
+        if reg_max == hip.REG_CONT:
+            d = hip.fcos_loc_terms_cont_bwd(labels, box, reg_targets, bv if ctx.has_bv else None, nc, tsb, tsc, coef, flags=flags)
+        else:
+            d = hip.fcos_loc_terms_bwd(labels, box, reg_targets, bv if ctx.has_bv else None, nc, reg_max, tsb, tsc, coef, flags=flags)
         return d, None, None, None, None
 
 
@@ -1226,10 +1245,10 @@ class _FcosJointLossFn(torch.autograd.Function):
         alpha, gamma, nc, rm, flags_s, flags_p, tsb, tsc, world, cflags, klw, wmul, wdiv = consts
         lg, bx = logits.detach(), box.detach()
         focal_s = hip.sigmoid_focal_fwd(lg, lab_s, alpha, gamma)
-        sums_s = hip.fcos_loc_terms_fwd(lab_s, bx, reg_s, None, nc, rm, 0.0, 0.0, flags=flags_s)
+        sums_s = _loc_fwd(lab_s, bx, reg_s, None, nc, rm, 0.0, 0.0, flags_s)
         focal_c = hip.sigmoid_focal_fwd(lg, lab_c, alpha, gamma)
-        sums_c = hip.fcos_loc_terms_fwd(lab_c, bx, reg_c, None, nc, rm, 0.0, 0.0, flags=flags_p)
-        sums_r = hip.fcos_loc_terms_fwd(lab_r, bx, reg_r, bv_r, nc, rm, tsb, tsc, flags=flags_p)
+        sums_c = _loc_fwd(lab_c, bx, reg_c, None, nc, rm, 0.0, 0.0, flags_p)
+        sums_r = _loc_fwd(lab_r, bx, reg_r, bv_r, nc, rm, tsb, tsc, flags_p)
         norm = norm_fn(sums_s, sums_c, sums_r)
         rec, coef = hip.fcos_loss_combine(focal_s, sums_s, focal_c, sums_c, sums_r, norm, world, cflags, klw, wmul, wdiv)
         ctx.consts = consts
@@ -1246,9 +1265,9 @@ class _FcosJointLossFn(torch.autograd.Function):
         dlg, dbx = torch.empty_like(lg), torch.empty_like(bx)
         hip.sigmoid_focal_bwd_acc(lg, lab_s, alpha, gamma, coef[0:1], gs, dlg, False)
         hip.sigmoid_focal_bwd_acc(lg, lab_c, alpha, gamma, coef[9:10], gs, dlg, True)
-        hip.fcos_loc_terms_bwd_acc(lab_s, bx, reg_s, None, nc, rm, 0.0, 0.0, coef[1:9], gs, dbx, False, flags=flags_s)
-        hip.fcos_loc_terms_bwd_acc(lab_c, bx, reg_c, None, nc, rm, 0.0, 0.0, coef[10:18], gs, dbx, True, flags=flags_p)
-        hip.fcos_loc_terms_bwd_acc(lab_r, bx, reg_r, bv_r if ctx.has_bv else None, nc, rm, tsb, tsc, coef[18:26], gs, dbx, True, flags=flags_p)
+        _loc_bwd_acc(lab_s, bx, reg_s, None, nc, rm, 0.0, 0.0, coef[1:9], gs, dbx, False, flags_s)
+        _loc_bwd_acc(lab_c, bx, reg_c, None, nc, rm, 0.0, 0.0, coef[10:18], gs, dbx, True, flags_p)
+        _loc_bwd_acc(lab_r, bx, reg_r, bv_r if ctx.has_bv else None, nc, rm, tsb, tsc, coef[18:26], gs, dbx, True, flags_p)
         return dlg, dbx, None, None, None
 
 
