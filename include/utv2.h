@@ -442,6 +442,20 @@ int utv2_roi_infer_gather(const int64_t* top, const float* boxes, int N, int P, 
 int utv2_roi_infer_pack(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows, const float* stdl,
                         int N, int P, int k, int D, float* oboxes, float* oscores, int* ocls, float* ostd, int64_t* orows, unsigned char* ovalid,
                         utv2_stream_t stream);
+/* Per-class regression (MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False; fast_rcnn.py:1162-1185): deltas [N*P][4K], one box per
+ * (proposal, class).  keys_pc: boxes [N][P][K][4], keys as above (same flat index p*K + c); a proposal with ANY non-finite decoded box or
+ * probability loses all its K candidates (D2 fast_rcnn_inference_single_image filters rows).  gather_pc: boxes [N][P][K][4], cb = the box
+ * of (row, class); top must hold keys that keys_pc wrote (flat index < P*K).  pack_pc: stdl [N*P][4*nbox] -> ostd [N][D][4*nbox], the kept
+ * row's std logits of every class (fast_rcnn.py:1123).  Checks as the three above, and P*K < 2^32 (keys, gather), nbox >= 1 (pack).
+ * Layout contract, NOT checked: every array is dense (no row pitch) and deltas, prop, whwh, boxes, cb, stdl, oboxes, ostd are 16-byte
+ * aligned - the kernels move them as float4. */
+int utv2_roi_infer_keys_pc(const float* probs, const float* deltas, const float* prop, const unsigned char* valid, const float* whwh, int N,
+                           int P, int K, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, utv2_stream_t stream);
+int utv2_roi_infer_gather_pc(const int64_t* top, const float* boxes, int N, int P, int K, int k, float thr, float* sc, int64_t* rows, int* cls,
+                             float* cb, unsigned char* valid, utv2_stream_t stream);
+int utv2_roi_infer_pack_pc(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows,
+                           const float* stdl, int N, int P, int k, int D, int nbox, float* oboxes, float* oscores, int* ocls, float* ostd,
+                           int64_t* orows, unsigned char* ovalid, utv2_stream_t stream);
 /* PseudoLabRPN.losses on the sampled anchors (proposal_generator/rpn.py:153-225): sums[0] = sum of BCE-with-logits over the sampled
  * positives (pos_idx [N][npos], int64 anchor indices, pos_valid) and negatives (neg_idx [N][nneg]) - every term times the score of the
  * anchor's matched pseudo box when gt_scores is given, zero when the image has no gt (has_gt [N]) -, sums[1] = sum over the valid
@@ -499,6 +513,18 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
 int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
                       const float* gstd, int R, int num_classes, int mode, float wx, float wy, float scale_clamp, float ts_better,
                       float t_cert, float* sum, float* gdeltas, float* gstd_out, utv2_stream_t stream);
+/* utv2_roi_box_loss with 4 * nbox delta and std columns per row (CLS_AGNOSTIC_BBOX_REG False: nbox = num_classes): a foreground row
+ * reads columns 4*cls .. 4*cls+3 of deltas and of stdl (fast_rcnn.py:950-959, :1036-1045).  mode 0 (nlloss), 1 (smooth_l1), 3 (pseudo
+ * smooth_l1); mode 2 (tsbetter) has no per-class form in the reference: UTV2_EARG.  Writes sum[0] and gdeltas / gstd_out [R][4*nbox]:
+ * the derivatives in the selected four columns, 0 everywhere else (background and empty rows: all 0) - every element is written by this
+ * launch.  Same arithmetic, row order and summation tree as utv2_roi_box_loss: on the pre-gathered four columns that entry gives the
+ * same bits.  Accepted: R >= 0 (R == 0: sum 0), nbox == num_classes or nbox == 1, ld >= 4*nbox; anything else: UTV2_EARG.
+ * The caller's contract, NOT checked: cls (device data) in [-1, num_classes] (a value outside is treated as background); prop, gtb,
+ * gdeltas and gstd_out are dense and 16-byte aligned (float4 accesses) - deltas / stdl are read as scalars: any 4-byte aligned
+ * address and any pitch ld >= 4*nbox. */
+int utv2_roi_box_loss_pc(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb, int R,
+                         int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float* sum, float* gdeltas,
+                         float* gstd_out, utv2_stream_t stream);
 /* roi_heads/fast_rcnn.py:925-936 + FocalLoss :1405-1429 (softmax CE focal, gamma 1.5), summed.  Accepted: R >= 0, any C >= 1 (one wave
  * strides over the row); R < 0 or C < 1: UTV2_EARG.  The caller's contract, NOT checked (device data): target in [-1, C) (-1 = row
  * skipped) - a target >= C reads past the row. */

@@ -84,7 +84,10 @@ def _make(base):
                         _, proposals_rpn_unsup_k, proposals_roih_unsup_k, _ = self.model_teacher(unlabel_data_k, branch="unsup_data_weak")
                     pseudo, _ = self.process_pseudo_label(proposals_roih_unsup_k, S.BBOX_THRESHOLD, "roih", "thresholding")
                     # student ground truth fields
-                    extra = {"pred_boxes_std": pseudo["pred_boxes_std"]} if "pred_boxes_std" in pseudo else {}   # trainer.py:743-746: when there is one
+                    # trainer.py:743-746: when there is one.  Per-class regression ([., 4K] std logits): its only reader is the refused
+                    # `tsbetter` loss, so the pseudo ground truth does not carry it
+                    extra = ({"pred_boxes_std": pseudo["pred_boxes_std"]}
+                             if "pred_boxes_std" in pseudo and pseudo["pred_boxes_std"].shape[-1] == 4 else {})
                     gt = PaddedBoxes(pseudo.image_sizes, boxes=pseudo["boxes"], classes=pseudo["classes"], valid=pseudo["valid"],
                                      scores=pseudo["scores"], **extra)
                     if overlap:

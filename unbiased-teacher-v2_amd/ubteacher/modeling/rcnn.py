@@ -9,7 +9,7 @@ and the Detectron2 pieces they inherit from [D2-recall, SURVEY appendix C], re-l
     no nonzero()/item() host syncs); random subsampling uses per-slot random keys (the k smallest
     keys of a class == randperm[:k] in distribution; tests inject the keys);
   * RPN objectness + anchor deltas are one fused 1x1 conv (16 ch: 3 | 12 | pad); the box predictor's
-    cls_score / bbox_pred / bbox_pred_std are one fused 1024->96 GEMM; FC layers run on the same
+    cls_score / bbox_pred / bbox_pred_std are one fused 1024->96 GEMM (1024->728 with per-class box regression); FC layers run on the same
     MFMA implicit-GEMM kernel as the convs; fc1 consumes the NHWC RoIAlign output directly.
 """
 import math
@@ -137,6 +137,11 @@ class _RoiBoxLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, deltas, std, cls, prop, gtb, gstd, pred, mode):
         t = pred.box2box_transform
+        if pred.nbox > 1:   # per-class regression: the four columns of each foreground row's class (utv2_roi_box_loss_pc)
+            out, gd, gs = hip.roi_box_loss_pc(deltas.detach(), std.detach(), cls, prop, gtb, pred.num_classes, pred.nbox, mode, t.weights[0],
+                                              t.weights[1], t.scale_clamp)
+            ctx.save_for_backward(gd, gs)
+            return out
         out, gd, gs = hip.roi_box_loss(deltas.detach(), std.detach(), cls, prop, gtb, gstd, pred.num_classes, mode, t.weights[0], t.weights[1],
                                        t.scale_clamp, pred.ts_better, pred.t_cert)
         ctx.save_for_backward(gd, gs)
@@ -444,25 +449,35 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
 
     def __init__(self, cfg, store, in_dim, prefix):
         rh, bh = cfg.MODEL.ROI_HEADS, cfg.MODEL.ROI_BOX_HEAD
-        assert bh.CLS_AGNOSTIC_BBOX_REG, "shipped UTv2 configs are class-agnostic (…sup1_run0.yaml:18)"
         self.num_classes = rh.NUM_CLASSES
         K = self.num_classes
         self.K = K
+        # fast_rcnn.py:761-766: bbox_pred / bbox_pred_std are Linear(input, nbox * 4).  One fused weight: rows [0, K+1) scores, the next
+        # 4 * nbox the deltas, the next 4 * nbox the std logits, padded to a multiple of 8 (nbox == 1: the 96 rows of PRED_CH)
+        self.nbox = 1 if bh.CLS_AGNOSTIC_BBOX_REG else K
+        nb = 4 * self.nbox
+        self.ch = PRED_CH if (self.nbox == 1 and K + 9 <= PRED_CH) else (K + 1 + 2 * nb + 7) // 8 * 8
+        if self.nbox > 1 and bh.BBOX_PSEUDO_REG_LOSS_TYPE == "tsbetter":
+            raise NotImplementedError(
+                "MODEL.ROI_BOX_HEAD.BBOX_PSEUDO_REG_LOSS_TYPE 'tsbetter' with MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False: the reference "
+                "fails on its first unsupervised step in this mode - its inference attaches all 4K std columns of a kept row to the pseudo "
+                "boxes (fast_rcnn.py:1123) and box_reg_pseudo_loss compares that [nfg, 4K] tensor with a [nfg, 4] one (:1061-1069), a shape "
+                "error for K >= 2; use BBOX_PSEUDO_REG_LOSS_TYPE 'smooth_l1' or CLS_AGNOSTIC_BBOX_REG True")
 
         def init_pred(t):
             t.zero_()
             t[:K + 1].normal_(0.0, 0.01)
-            t[K + 1:K + 5].normal_(0.0, 0.001)
-            t[K + 5:K + 9].normal_(0.0, 0.0001)
-        w = store.new((PRED_CH, in_dim), "decay", init_pred)
+            t[K + 1:K + 1 + nb].normal_(0.0, 0.001)
+            t[K + 1 + nb:K + 1 + 2 * nb].normal_(0.0, 0.0001)
+        w = store.new((self.ch, in_dim), "decay", init_pred)
         w.export(prefix + ".cls_score.weight", lambda t: t[0:K + 1])
-        w.export(prefix + ".bbox_pred.weight", lambda t: t[K + 1:K + 5])
-        w.export(prefix + ".bbox_pred_std.weight", lambda t: t[K + 5:K + 9])
-        b = store.new((PRED_CH,), "decay", lambda t: t.zero_())
+        w.export(prefix + ".bbox_pred.weight", lambda t: t[K + 1:K + 1 + nb])
+        w.export(prefix + ".bbox_pred_std.weight", lambda t: t[K + 1 + nb:K + 1 + 2 * nb])
+        b = store.new((self.ch,), "decay", lambda t: t.zero_())
         b.export(prefix + ".cls_score.bias", lambda t: t[0:K + 1])
-        b.export(prefix + ".bbox_pred.bias", lambda t: t[K + 1:K + 5])
-        b.export(prefix + ".bbox_pred_std.bias", lambda t: t[K + 5:K + 9])
-        self.linear = ops.Conv(w, in_dim, PRED_CH, 1, 1, 0, bias=b, out_fp32=True)
+        b.export(prefix + ".bbox_pred.bias", lambda t: t[K + 1:K + 1 + nb])
+        b.export(prefix + ".bbox_pred_std.bias", lambda t: t[K + 1 + nb:K + 1 + 2 * nb])
+        self.linear = ops.Conv(w, in_dim, self.ch, 1, 1, 0, bias=b, out_fp32=True)
         self.box2box_transform = Box2BoxXYXYTransform(tuple(bh.BBOX_REG_WEIGHTS))
         self.smooth_l1_beta = bh.SMOOTH_L1_BETA
         self.test_score_thresh = rh.SCORE_THRESH_TEST
@@ -479,9 +494,9 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             raise ValueError("Invalid bbox pseudo reg loss type '{}'".format(self.box_pseudo_reg_loss_type))
 
     def __call__(self, x2d):
-        y = self.linear(x2d.view(x2d.shape[0], 1, 1, -1)).view(x2d.shape[0], PRED_CH)
-        K = self.K
-        return y[:, :K + 1], y[:, K + 1:K + 5], y[:, K + 5:K + 9]
+        y = self.linear(x2d.view(x2d.shape[0], 1, 1, -1)).view(x2d.shape[0], self.ch)
+        K, nb = self.K, 4 * self.nbox
+        return y[:, :K + 1], y[:, K + 1:K + 1 + nb], y[:, K + 1 + nb:K + 1 + 2 * nb]
 
     def losses(self, predictions, sampled, branch, raw=False):
         scores, deltas, std = predictions
@@ -515,6 +530,8 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             if len(cache) >= 16:
                 cache.clear()
             hwt = cache[ck] = torch.tensor([[s[1], s[0], s[1], s[0]] for s in proposals.image_sizes], dtype=torch.float32, device=pb.device)[:, None, :]
+        if self.nbox > 1:
+            return self._inference_per_class(scores, deltas, std, proposals, hwt, cache, max_cand)
         if os.environ.get("UTV2_FUSED_ROI_INFERENCE", "1") != "0" and scores.dtype == deltas.dtype == std.dtype == torch.float32 and P * K < (1 << 32):
             # round 4: decode + clip + candidate keys, the gather behind the top-k and the packing of the NMS survivors as three launches
             # (utv2_roi_infer_*) around softmax / topk / utv2_nms_batched - the chain below is ~55 ATen launches per teacher pass.
@@ -562,6 +579,56 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
                           scores=torch.gather(sc, 1, ix).contiguous(),
                           classes=torch.gather(c, 1, ix).contiguous(),
                           pred_boxes_std=torch.gather(std.view(N, P, 4), 1, keep_rows[:, :, None].expand(-1, -1, 4)).contiguous(),
+                          valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
+        return out, keep_rows
+
+    def _inference_per_class(self, scores, deltas, std, proposals, hwt, cache, max_cand):
+        """inference() with per-class regression (fast_rcnn.py:1162-1185): K decoded boxes per proposal, a candidate (row, class) takes the
+        box of its class, a proposal with any non-finite decoded box is dropped (D2 fast_rcnn_inference_single_image filters rows), and
+        pred_boxes_std is the kept row's full [4K] std logits (fast_rcnn.py:1123).  Same candidate keys and order as the class-agnostic
+        chain; the fused kernels (utv2_roi_infer_*_pc) and the ATen chain below them give identical detections."""
+        N, P = proposals["valid"].shape
+        K = self.K
+        pb = proposals["boxes"]
+        D = self.test_topk_per_image
+        kk = min(max_cand, P * K)
+        if os.environ.get("UTV2_FUSED_ROI_INFERENCE", "1") != "0" and scores.dtype == deltas.dtype == std.dtype == torch.float32 and P * K < (1 << 32):
+            pr = F.softmax(scores, dim=-1).contiguous()
+            wx, wy = self.box2box_transform.weights[0], self.box2box_transform.weights[1]
+            dec, keys = hip.roi_infer_keys_pc(pr, deltas.contiguous(), pb.contiguous(), proposals["valid"].contiguous(), hwt.view(N, 4), K, wx, wy,
+                                              self.box2box_transform.scale_clamp, self.test_score_thresh)
+            if os.environ.get("UTV2_ROI_TOPK", "1") != "0" and kk <= 8192:
+                ro = cache.get(("row_off", N, P * K, str(pb.device)))
+                if ro is None:
+                    ro = cache[("row_off", N, P * K, str(pb.device))] = (torch.arange(N + 1, dtype=torch.int64) * (P * K)).to(pb.device)
+                top = hip.topk_rows(keys.view(-1), ro, N, P * K, kk)
+            else:
+                top = torch.topk(keys, kk, dim=1, sorted=True).values
+            sc, r, c, cb, valid = hip.roi_infer_gather_pc(top, dec, K, self.test_score_thresh)
+            kidx, cnt = hip.nms_batched(cb, sc, c, valid, self.test_nms_thresh, class_aware=True, post_topk=-1, max_out=D)
+            ob, osc, oc, ostd, keep_rows, ov = hip.roi_infer_pack_pc(kidx, cnt, cb, sc, c, r, std.contiguous(), P, D, K)
+            return PaddedBoxes(proposals.image_sizes, boxes=ob, scores=osc, classes=oc, pred_boxes_std=ostd, valid=ov, count=cnt), keep_rows
+        boxes = self.box2box_transform.apply_deltas(deltas.view(N, P, K, 4), pb[:, :, None, :])      # [N, P, K, 4]
+        probs = F.softmax(scores, dim=-1).view(N, P, K + 1)[:, :, :K]
+        ok = proposals["valid"].bool() & torch.isfinite(boxes).all(dim=3).all(dim=2) & torch.isfinite(probs).all(dim=2)
+        boxes = torch.minimum(boxes.clamp(min=0), hwt[:, :, None, :])
+        cand = (probs > self.test_score_thresh) & ok[:, :, None]
+        flat = torch.where(cand, probs, torch.full_like(probs, -1.0)).reshape(N, P * K)
+        top = torch.topk(float_order_key(flat), kk, dim=1, sorted=True).values
+        idx = 4294967295 - (top & 4294967295)
+        sc = torch.gather(flat, 1, idx)
+        r, c = idx // K, (idx % K).to(torch.int32)
+        cb = torch.gather(boxes.reshape(N, P * K, 4), 1, idx[:, :, None].expand(-1, -1, 4)).contiguous()     # the box of (row, class)
+        valid = (sc > self.test_score_thresh).to(torch.uint8)
+        kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), self.test_nms_thresh,
+                                    class_aware=True, post_topk=-1, max_out=D)
+        ix = kidx.clamp(min=0).long()
+        keep_rows = torch.gather(r, 1, ix)
+        out = PaddedBoxes(proposals.image_sizes,
+                          boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
+                          scores=torch.gather(sc, 1, ix).contiguous(),
+                          classes=torch.gather(c, 1, ix).contiguous(),
+                          pred_boxes_std=torch.gather(std.reshape(N, P, 4 * K), 1, keep_rows[:, :, None].expand(-1, -1, 4 * K)).contiguous(),
                           valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
         return out, keep_rows
 
@@ -861,10 +928,10 @@ class TwoStagePseudoLabGeneralizedRCNN(ArenaModel):
             sc = torch.zeros((len(insts), M)); st = torch.zeros((len(insts), M, 4))
             for i, x in enumerate(insts):
                 sc[i, :len(x)] = x.scores.detach().float().cpu()
-                if x.has("pred_boxes_std"):
+                if x.has("pred_boxes_std") and x.pred_boxes_std.shape[-1] == 4:
                     st[i, :len(x)] = x.pred_boxes_std.detach().float().cpu()
             gt.f["scores"] = sc.to(self.device)
-            if insts[0].has("pred_boxes_std"):
+            if insts[0].has("pred_boxes_std") and insts[0].pred_boxes_std.shape[-1] == 4:   # per-class [., 4K] std: read by nothing
                 gt.f["pred_boxes_std"] = st.to(self.device)
         return gt
 
