@@ -424,38 +424,32 @@ int utv2_rpn_rank_keys(const float* head, int num_levels, const int* hw_host, in
 int utv2_rpn_decode(const int64_t* top, int maxk, const float* head, const float* anchors, const float* image_hw, int num_levels,
                     const int* hw_host, const int* k_host, int N, int A, int ch, const float* weights_host, float scale_clamp,
                     float min_size, float* boxes, float* scores, int* lvls, unsigned char* keep, utv2_stream_t stream);
-/* The predictor's inference (roi_heads/fast_rcnn.py:1094-1125,1162-1225; D2 fast_rcnn_inference) around the top-k and the NMS:
- * keys:   probs [N*P][K+1] (softmax), deltas [N*P][4], prop [N][P][4], valid [N][P], whwh [N][4] = (w, h, w, h) of the image ->
- *         boxes [N][P][4] = Box2BoxXYXYTransform.apply_deltas (weights wx, wy; clamp +-scale_clamp) clipped to the image, and
- *         keys [N][P*K]: per foreground class (order-preserving bits of its probability) << 32 | (2^32 - 1 - (p*K + c)), the key of
- *         -1 when prob <= thr / the slot is invalid / box or probabilities are not finite.  Descending key order = (prob desc, index asc).
- * gather: top [N][k] (the k largest keys of each image, descending) -> sc, rows (proposal index, int64), cls, cb [N][k][4], valid (sc > thr)
- * pack:   kidx [N][D] / cnt [N] of utv2_nms_batched on (cb, sc, cls, valid) -> the padded detections + stdl [N*P][4] of their rows */
 /* the survivors of utv2_nms_batched (kidx [N][D], -1 padded; cnt [N]) gathered into padded outputs: oboxes [N][D][4], oscores [N][D],
  * ovalid [N][D] = slot < cnt (slots beyond the count repeat candidate 0) - the tail of D2 find_top_rpn_proposals in one launch */
 int utv2_nms_pack(const int* kidx, const int* cnt, const float* boxes, const float* scores, int N, int M, int D, float* oboxes, float* oscores,
                   unsigned char* ovalid, utv2_stream_t stream);
+/* The predictor's inference (roi_heads/fast_rcnn.py:1094-1125,1162-1225; D2 fast_rcnn_inference) around the top-k and the NMS.
+ * nbox = 1 (class-agnostic regression: one box per proposal) or K (MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False, fast_rcnn.py:1162-1185:
+ * one box per (proposal, class)).
+ * keys:   probs [N*P][K+1] (softmax), deltas [N*P][4*nbox], prop [N][P][4], valid [N][P], whwh [N][4] = (w, h, w, h) of the image ->
+ *         boxes [N][P][nbox][4] = Box2BoxXYXYTransform.apply_deltas (weights wx, wy; clamp +-scale_clamp) clipped to the image, and
+ *         keys [N][P*K]: per foreground class (order-preserving bits of its probability) << 32 | (2^32 - 1 - (p*K + c)), the key of
+ *         -1 when prob <= thr / the slot is invalid / ANY decoded box or foreground probability of the proposal is not finite (D2
+ *         fast_rcnn_inference_single_image filters rows).  Descending key order = (prob desc, index asc).
+ * gather: top [N][k] (the k largest keys of each image, descending; keys that `keys` wrote: flat index < P*K) -> sc, rows (proposal
+ *         index, int64), cls, cb [N][k][4] = boxes[n][row][nbox == 1 ? 0 : cls], valid (sc > thr)
+ * pack:   kidx [N][D] / cnt [N] of utv2_nms_batched on (cb, sc, cls, valid) -> the padded detections + ostd [N][D][4*nbox], the kept
+ *         rows' std logits of stdl [N*P][4*nbox] (fast_rcnn.py:1118-1123); slots beyond the count repeat candidate 0
+ * Accepted: N, P, K, k, D >= 1, nbox == K or nbox == 1 (keys, gather), P*K < 2^32 (keys, gather), nbox >= 1 (pack); anything else:
+ * UTV2_EARG.  Layout contract, NOT checked: every array is dense (no row pitch) and deltas, prop, whwh, boxes, cb, stdl, oboxes, ostd are
+ * 16-byte aligned - the kernels move them as float4. */
 int utv2_roi_infer_keys(const float* probs, const float* deltas, const float* prop, const unsigned char* valid, const float* whwh, int N, int P,
-                        int K, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, utv2_stream_t stream);
-int utv2_roi_infer_gather(const int64_t* top, const float* boxes, int N, int P, int K, int k, float thr, float* sc, int64_t* rows, int* cls,
-                          float* cb, unsigned char* valid, utv2_stream_t stream);
+                        int K, int nbox, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, utv2_stream_t stream);
+int utv2_roi_infer_gather(const int64_t* top, const float* boxes, int N, int P, int K, int nbox, int k, float thr, float* sc, int64_t* rows,
+                          int* cls, float* cb, unsigned char* valid, utv2_stream_t stream);
 int utv2_roi_infer_pack(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows, const float* stdl,
-                        int N, int P, int k, int D, float* oboxes, float* oscores, int* ocls, float* ostd, int64_t* orows, unsigned char* ovalid,
-                        utv2_stream_t stream);
-/* Per-class regression (MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False; fast_rcnn.py:1162-1185): deltas [N*P][4K], one box per
- * (proposal, class).  keys_pc: boxes [N][P][K][4], keys as above (same flat index p*K + c); a proposal with ANY non-finite decoded box or
- * probability loses all its K candidates (D2 fast_rcnn_inference_single_image filters rows).  gather_pc: boxes [N][P][K][4], cb = the box
- * of (row, class); top must hold keys that keys_pc wrote (flat index < P*K).  pack_pc: stdl [N*P][4*nbox] -> ostd [N][D][4*nbox], the kept
- * row's std logits of every class (fast_rcnn.py:1123).  Checks as the three above, and P*K < 2^32 (keys, gather), nbox >= 1 (pack).
- * Layout contract, NOT checked: every array is dense (no row pitch) and deltas, prop, whwh, boxes, cb, stdl, oboxes, ostd are 16-byte
- * aligned - the kernels move them as float4. */
-int utv2_roi_infer_keys_pc(const float* probs, const float* deltas, const float* prop, const unsigned char* valid, const float* whwh, int N,
-                           int P, int K, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, utv2_stream_t stream);
-int utv2_roi_infer_gather_pc(const int64_t* top, const float* boxes, int N, int P, int K, int k, float thr, float* sc, int64_t* rows, int* cls,
-                             float* cb, unsigned char* valid, utv2_stream_t stream);
-int utv2_roi_infer_pack_pc(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows,
-                           const float* stdl, int N, int P, int k, int D, int nbox, float* oboxes, float* oscores, int* ocls, float* ostd,
-                           int64_t* orows, unsigned char* ovalid, utv2_stream_t stream);
+                        int N, int P, int k, int D, int nbox, float* oboxes, float* oscores, int* ocls, float* ostd, int64_t* orows,
+                        unsigned char* ovalid, utv2_stream_t stream);
 /* PseudoLabRPN.losses on the sampled anchors (proposal_generator/rpn.py:153-225): sums[0] = sum of BCE-with-logits over the sampled
  * positives (pos_idx [N][npos], int64 anchor indices, pos_valid) and negatives (neg_idx [N][nneg]) - every term times the score of the
  * anchor's matched pseudo box when gt_scores is given, zero when the image has no gt (has_gt [N]) -, sums[1] = sum over the valid
@@ -505,26 +499,23 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
                     int G, float iou_thr, int num_classes, int batch, int nfg_max, float* out_boxes, int64_t* out_classes,
                     float* out_gt_boxes, unsigned char* out_valid, int64_t* out_idx, float* out_conf, float* out_std, utv2_stream_t stream);
 /* box_reg_loss / box_reg_pseudo_loss of the boundary-variance predictor (roi_heads/fast_rcnn.py:938-1090) on R sampled ROIs, summed:
- * deltas / stdl = the predicted boundary deltas and std logits (row pitch ld floats), cls [R] int64 (-1 = empty slot, foreground =
- * [0, num_classes)), prop / gtb [R][4] proposal and matched gt boxes, gstd [R][4] the pseudo boxes' std logits or NULL.
+ * deltas / stdl = the predicted boundary deltas and std logits, 4 * nbox columns per row (row pitch ld floats): nbox = 1 (class-agnostic)
+ * or num_classes (CLS_AGNOSTIC_BBOX_REG False: a foreground row reads columns 4*cls .. 4*cls+3 of both, fast_rcnn.py:950-959,
+ * :1036-1045); cls [R] int64 (-1 = empty slot, foreground = [0, num_classes)), prop / gtb [R][4] proposal and matched gt boxes, gstd
+ * [R][4] the pseudo boxes' std logits or NULL (read in mode 2 only, like ts_better and t_cert).
  * mode 0: nlloss (L1 + 0.05 sum NLL * IoU, gradient through the IoU), 1: smooth_l1 at beta 0, 2: tsbetter, 3: pseudo smooth_l1.
- * Writes sum[0] and the derivatives gdeltas / gstd_out [R][4] (Box2BoxXYXYTransform weights wx, wy and clamp).
- * Accepted: R >= 0 (R == 0: sum 0), ld >= 4 (the pitch of deltas and of stdl), mode 0..3; anything else: UTV2_EARG. */
-int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
-                      const float* gstd, int R, int num_classes, int mode, float wx, float wy, float scale_clamp, float ts_better,
-                      float t_cert, float* sum, float* gdeltas, float* gstd_out, utv2_stream_t stream);
-/* utv2_roi_box_loss with 4 * nbox delta and std columns per row (CLS_AGNOSTIC_BBOX_REG False: nbox = num_classes): a foreground row
- * reads columns 4*cls .. 4*cls+3 of deltas and of stdl (fast_rcnn.py:950-959, :1036-1045).  mode 0 (nlloss), 1 (smooth_l1), 3 (pseudo
- * smooth_l1); mode 2 (tsbetter) has no per-class form in the reference: UTV2_EARG.  Writes sum[0] and gdeltas / gstd_out [R][4*nbox]:
- * the derivatives in the selected four columns, 0 everywhere else (background and empty rows: all 0) - every element is written by this
- * launch.  Same arithmetic, row order and summation tree as utv2_roi_box_loss: on the pre-gathered four columns that entry gives the
- * same bits.  Accepted: R >= 0 (R == 0: sum 0), nbox == num_classes or nbox == 1, ld >= 4*nbox; anything else: UTV2_EARG.
+ * Writes sum[0] and gdeltas / gstd_out [R][4*nbox] (Box2BoxXYXYTransform weights wx, wy and clamp): the derivatives in the selected four
+ * columns, 0 everywhere else (background and empty rows: all 0) - every element is written by this launch.  One workgroup sums in a
+ * fixed order, the same for both layouts: nbox = num_classes on the full matrix and nbox = 1 on the pre-gathered four columns give the
+ * same bits in the sum and on every foreground row (a background row's zeros are signed, sign(d - t) * 0, when nbox == 1).
+ * Accepted: R >= 0 (R == 0: sum 0), num_classes >= 1, nbox == num_classes or nbox == 1, ld >= 4*nbox (the pitch of deltas and of stdl),
+ * mode 0..3, and mode 2 with nbox == 1 only (tsbetter has no per-class form in the reference); anything else: UTV2_EARG.
  * The caller's contract, NOT checked: cls (device data) in [-1, num_classes] (a value outside is treated as background); prop, gtb,
  * gdeltas and gstd_out are dense and 16-byte aligned (float4 accesses) - deltas / stdl are read as scalars: any 4-byte aligned
  * address and any pitch ld >= 4*nbox. */
-int utv2_roi_box_loss_pc(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb, int R,
-                         int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float* sum, float* gdeltas,
-                         float* gstd_out, utv2_stream_t stream);
+int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
+                      const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
+                      float t_cert, float* sum, float* gdeltas, float* gstd_out, utv2_stream_t stream);
 /* roi_heads/fast_rcnn.py:925-936 + FocalLoss :1405-1429 (softmax CE focal, gamma 1.5), summed.  Accepted: R >= 0, any C >= 1 (one wave
  * strides over the row); R < 0 or C < 1: UTV2_EARG.  The caller's contract, NOT checked (device data): target in [-1, C) (-1 = row
  * skipped) - a target >= C reads past the row. */

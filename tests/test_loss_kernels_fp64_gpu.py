@@ -462,5 +462,5 @@ def test_unsupported_arguments_are_refused():
     H.call("utv2_softmax_focal_fwd", p(bx), p(lb), 0, 80, 1.5, p(sums), p(ws), st)
     assert float(sums.cpu()[0]) == 0.0
     cls = torch.zeros(1, dtype=torch.int64, device=DEV)
-    H.call("utv2_roi_box_loss", p(bx), p(bx), 8, p(cls), p(bx), p(bx), None, 0, 80, 0, 10.0, 5.0, 62.5, 0.1, 0.5, p(sums), p(out), p(out), st)
+    H.call("utv2_roi_box_loss", p(bx), p(bx), 8, p(cls), p(bx), p(bx), None, 0, 80, 1, 0, 10.0, 5.0, 62.5, 0.1, 0.5, p(sums), p(out), p(out), st)
     assert float(sums.cpu()[0]) == 0.0                                                                            # R == 0: sum 0

@@ -1,6 +1,6 @@
 """Per-class box regression of the boundary-variance ROI predictor (MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False) on the GPU: the
-utv2_roi_box_loss_pc kernel against fp64 autograd (tests/loss_ref64_percls.py) and against the class-agnostic kernel on the pre-gathered
-columns, the predictor's losses / head gradients / inference against the executed reference (tests/golden/rcnn_percls.npz), the fused
+utv2_roi_box_loss kernel with nbox = K against fp64 autograd (tests/loss_ref64_percls.py) and against itself with nbox = 1 on the
+pre-gathered columns, the predictor's losses / head gradients / inference against the executed reference (tests/golden/rcnn_percls.npz), the fused
 inference kernels against the ATen chain, and whole semi-supervised steps (fp16 AMP, hipGraph replay)."""
 import math
 import os
@@ -43,14 +43,14 @@ def cfg_of(K=80, *over):
 
 
 def raw_loss_pc(H, de, st, cls, prop, gtb, K, nbox, mode, ld=None, R=None):
-    """utv2_roi_box_loss_pc on output buffers pre-filled with NaN: every element must be written by the launch itself"""
+    """utv2_roi_box_loss (gstd null) on output buffers pre-filled with NaN: every element must be written by the launch itself"""
     R = de.shape[0] if R is None else R
     out = torch.full((1,), float("nan"), device=DEV)
     gd = torch.full((max(R, 1), 4 * nbox), float("nan"), device=DEV)
     gs = torch.full((max(R, 1), 4 * nbox), float("nan"), device=DEV)
     wx, wy = L64.ROI_W
-    H.call("utv2_roi_box_loss_pc", de.data_ptr(), st.data_ptr(), de.stride(0) if ld is None else ld, cls.data_ptr(), prop.data_ptr(),
-           gtb.data_ptr(), R, K, nbox, mode, wx, wy, L64.ROI_CLAMP, out.data_ptr(), gd.data_ptr(), gs.data_ptr(), H._stream())
+    H.call("utv2_roi_box_loss", de.data_ptr(), st.data_ptr(), de.stride(0) if ld is None else ld, cls.data_ptr(), prop.data_ptr(),
+           gtb.data_ptr(), None, R, K, nbox, mode, wx, wy, L64.ROI_CLAMP, 0.0, 0.0, out.data_ptr(), gd.data_ptr(), gs.data_ptr(), H._stream())
     return out, gd, gs
 
 
@@ -60,8 +60,8 @@ def raw_loss_pc(H, de, st, cls, prop, gtb, K, nbox, mode, ld=None, R=None):
 def test_roi_box_loss_pc_vs_fp64_and_vs_the_agnostic_kernel(mode, K, pitch):
     """R = 37 rows (no multiple of a wave).  Bound: the ROI box loss's of test_loss_kernels_fp64_gpu.py (M (max(|r32 - r64|, u |r64|) + u s),
     M = 16, no absolute tolerance; the sum: (L + D + 2 M) u sum |terms|, L = 5 ceil(R / 256), D = 8).  Outside the selected columns every
-    gradient element is exactly 0.0 (the buffers start as NaN).  The class-agnostic kernel on the pre-gathered columns gives the same
-    bits - the sum, and the gradients of every foreground row: the reduction order is fixed and the arithmetic restated line by line."""
+    gradient element is exactly 0.0 (the buffers start as NaN).  nbox = 1 on the pre-gathered columns gives the same bits - the sum, and
+    the gradients of every foreground row: the reduction order is fixed and the row body is the same - the check of the column selection."""
     from ubteacher import hip as H
     R = 37
     c = P64.percls_case(R, K, 900 + K)
@@ -81,7 +81,7 @@ def test_roi_box_loss_pc_vs_fp64_and_vs_the_agnostic_kernel(mode, K, pitch):
         assert de.stride(0) == 8 * K + 5
     cls, prop, gtb = c["cls"].to(DEV), c["prop"].to(DEV), c["gtb"].to(DEV)
     o1 = raw_loss_pc(H, de, st, cls, prop, gtb, K, K, mode)
-    o2 = H.roi_box_loss_pc(de, st, cls, prop, gtb, K, K, mode, wx, wy, L64.ROI_CLAMP)
+    o2 = H.roi_box_loss(de, st, cls, prop, gtb, None, K, mode, wx, wy, L64.ROI_CLAMP, 0.0, 0.0, nbox=K)
     for x1, x2 in zip(o1, o2):
         assert same_bits(x1, x2)
     tag = "roi_pc m%d K%d %s" % (mode, K, pitch)
@@ -93,12 +93,12 @@ def test_roi_box_loss_pc_vs_fp64_and_vs_the_agnostic_kernel(mode, K, pitch):
         assert torch.all(gk[~sel] == 0.0) and not torch.isnan(gk).any()
     if mode != 0:
         assert torch.all(o1[2].cpu() == 0.0)
-    # the class-agnostic kernel on the gathered four columns
+    # nbox = 1 on the gathered four columns
     col = c["col"].to(DEV)
     ag = H.roi_box_loss(torch.gather(de, 1, col).contiguous(), torch.gather(st, 1, col).contiguous(), cls, prop, gtb, None, K, mode, wx, wy,
                         L64.ROI_CLAMP, 0.0, 0.0)
     assert same_bits(ag[0], o1[0])
-    # the selected columns exist on foreground rows: same bits there.  A background / empty row has none - both kernels give zeros, the
+    # the selected columns exist on foreground rows: same bits there.  A background / empty row has none - both layouts give zeros, the
     # class-agnostic one signed ones (-0.0 = sign(d - t) * 0), the per-class one the +0.0 its zero-filling workgroups write
     fg = ((c["cls"] >= 0) & (c["cls"] < K)).to(DEV)
     for a_, p_ in ((ag[1], torch.gather(o1[1], 1, col)), (ag[2], torch.gather(o1[2], 1, col))):
@@ -109,7 +109,7 @@ def test_roi_box_loss_pc_vs_fp64_and_vs_the_agnostic_kernel(mode, K, pitch):
 def test_roi_box_loss_pc_zero_fill_grid_stride():
     """R * K = 3300 * 80 = 264 000 groups of four > 1024 workgroups x 256 threads: the zero-filling workgroups take more than one group
     each (the 4 + 4 training step has 4096 x 80).  Outputs start as NaN: every element is written, the unselected ones 0.0, the selected
-    ones with the class-agnostic kernel's bits."""
+    ones with the bits of nbox = 1 on the gathered columns."""
     from ubteacher import hip as H
     R, K = 3300, 80
     assert R * K > 1024 * 256
@@ -151,7 +151,7 @@ def test_roi_box_loss_pc_arguments():
         raw_loss_pc(H, de, st, cls, prop, gtb, K, K, 1, ld=4 * K - 1)        # pitch below 4 * nbox
     with pytest.raises(RuntimeError, match=EARG):
         raw_loss_pc(H, de, st, cls, prop, gtb, K, K, 1, R=-1)
-    # nbox == 1: the class-agnostic layout through the new entry
+    # nbox == 1: the raw call and the wrapper's default
     o = raw_loss_pc(H, de[:, :4].contiguous(), st[:, :4].contiguous(), cls, prop, gtb, K, 1, 0)
     wx, wy = L64.ROI_W
     ag = H.roi_box_loss(de[:, :4].contiguous(), st[:, :4].contiguous(), cls, prop, gtb, None, K, 0, wx, wy, L64.ROI_CLAMP, 0.0, 0.0)
@@ -226,6 +226,52 @@ def test_inference_fused_equals_aten_and_the_reference(gold, K, monkeypatch):
         close(da["pred_boxes_std"][i, :n], gold[q + "bstd"])
     assert int(gold[p + "_bad_row"]) not in ra[0, :int(da["count"][0])].tolist()
     assert 49 not in ra[1, :int(da["count"][1])].tolist()
+
+
+@pytest.mark.parametrize("nbox", [1, 70])
+def test_roi_infer_keys_both_layouts_vs_torch_ops(nbox):
+    """hip.roi_infer_keys alone, N = 2, P = 5 (10 waves: a partially filled last workgroup of four), K = 70 (a second lane trip of 6
+    classes), class-agnostic and per-class deltas, against the ATen chain's ops on the same device: keys and boxes equal bit for bit.
+    Injected: a NaN probability at class 69 of row (0, 1), written into probs; a NaN delta in the box of class 65 (nbox = 1: in the only
+    box) of row (1, 2); the invalid slot (1, 4); a probability exactly thr at (0, 3), class 10.  One bad box or probability drops the
+    whole row: all 70 keys of the three bad rows are the key of -1, and so is the one of the probability equal to thr.  Where the
+    expected box is NaN - only in the row with the NaN delta - the stored box is unspecified and left out of the comparison."""
+    from ubteacher import hip as H
+    from ubteacher.modeling.rcnn import Box2BoxXYXYTransform, float_order_key
+    N, P, K, thr = 2, 5, 70, 0.015625                             # (2^-6: the same number in fp32 and in Python)
+    g = torch.Generator().manual_seed(700 + nbox)
+    probs = torch.softmax(torch.randn(N * P, K + 1, generator=g) * 2, dim=1)
+    deltas = torch.randn(N * P, 4 * nbox, generator=g) * 3
+    deltas[4] *= 40.0                                            # beyond the clamp
+    xy = torch.rand(N, P, 2, generator=g) * 150
+    prop = torch.cat((xy, xy + torch.rand(N, P, 2, generator=g) * 80 + 2), 2)
+    valid = torch.ones(N, P, dtype=torch.uint8)
+    whwh = torch.tensor([[200.0, 150.0, 200.0, 150.0], [120.0, 180.0, 120.0, 180.0]])
+    probs[0 * P + 1, 69] = float("nan")
+    deltas[1 * P + 2, 4 * (65 if nbox > 1 else 0) + 2] = float("nan")
+    valid[1, 4] = 0
+    probs[0 * P + 3, 10] = thr
+    bad = [(0, 1), (1, 2), (1, 4)]
+    probs, deltas, prop, valid, whwh = (t.to(DEV) for t in (probs, deltas, prop, valid, whwh))
+    wx, wy = L64.ROI_W
+    boxes, keys = H.roi_infer_keys(probs, deltas, prop, valid, whwh, K, wx, wy, L64.ROI_CLAMP, thr, nbox=nbox)
+    assert tuple(boxes.shape) == ((N, P, 4) if nbox == 1 else (N, P, nbox, 4)) and tuple(keys.shape) == (N, P * K)
+    eb = Box2BoxXYXYTransform((wx, wy), L64.ROI_CLAMP).apply_deltas(deltas.view(N, P, nbox, 4), prop[:, :, None, :])
+    pk = probs.view(N, P, K + 1)[:, :, :K]
+    ok = valid.bool() & torch.isfinite(eb).all(dim=3).all(dim=2) & torch.isfinite(pk).all(dim=2)
+    eb = torch.minimum(eb.clamp(min=0), whwh[:, None, None, :])
+    flat = torch.where((pk > thr) & ok[:, :, None], pk, torch.full_like(pk, -1.0)).reshape(N, P * K)
+    assert torch.equal(keys, float_order_key(flat))
+    minus1 = float_order_key(torch.full((1, P * K), -1.0, device=DEV)).view(P, K)
+    kv = keys.view(N, P, K)
+    for n, p in bad:
+        assert torch.equal(kv[n, p], minus1[p])
+    assert int(kv[0, 3, 10]) == int(minus1[3, 10]) and float(probs[3, 10]) == thr
+    assert int((kv != minus1[None]).sum()) > 20                  # the good rows hold real candidates
+    keep = ~torch.isnan(eb).any(dim=3)                           # [N, P, nbox]
+    dropped = (~keep).any(dim=2).nonzero().tolist()
+    assert len(dropped) <= 2 and all(tuple(x) in [(1, 2)] for x in dropped)
+    assert torch.equal(boxes.view(N, P, nbox, 4)[keep], eb[keep])
 
 
 def _fixed_keys(seed):
@@ -354,7 +400,7 @@ def _step_golden_setup():
 
 
 def test_per_class_step_vs_reference_trainer_golden():
-    """One full per-class Faster-RCNN UTv2 iteration in fp32 - the 1024 -> 728 Linear forward and backward, utv2_roi_box_loss_pc in both
+    """One full per-class Faster-RCNN UTv2 iteration in fp32 - the 1024 -> 728 Linear forward and backward, utv2_roi_box_loss (nbox = K) in both
     branches, the per-class teacher inference - against the reference's own UBRCNNTeacherTrainer.run_step_full_semisup around the
     reference's executed predictor (tests/golden/gen_golden_rcnn_percls.py).  The bounds of test_rcnn_step_vs_reference_trainer_golden:
     record_dict within 1e-3 (2e-2 for the weight-0 loss_rpn_loc_pseudo), the same pseudo-label set, teacher after EMA bit exact,

@@ -960,17 +960,36 @@ __global__ __launch_bounds__(512) void roi_sample_kernel(const float* __restrict
 // deltas and std logits.  mode 0: L1 + 0.05 * sum(NLL * IoU(gt, decoded box)) with the gradient flowing through the IoU;
 // 1: L1; 2: L1 on the boundaries where the teacher is more certain than the student by ts_better and above t_cert; 3: L1.
 // Box2BoxXYXYTransform (box_regression.py:11-129): get_deltas divides by (side + 1), apply_deltas multiplies by the side (B3 kept).
-// One workgroup, fixed summation order.
-// roi_box_loss_pc_kernel below restates modes 0 / 1 / 3 of this kernel line by line (per-class columns): a change here belongs there too -
-// tests/test_rcnn_percls_gpu.py holds the two to the same bits.
+// Layout: 4 * nbox delta / std columns per row, nbox = 1 (class-agnostic) or num_classes (CLS_AGNOSTIC_BBOX_REG False): a foreground row
+// reads - and its derivatives go to - the four columns of its class, 4 * cls .. 4 * cls + 3 (fast_rcnn.py:950-959, :1036-1045); gd / gs
+// are [R][4 * nbox].  Workgroup 0 is the loss: 256 threads, thread t takes rows t, t + 256, ..., one LDS tree - a fixed summation order -
+// and writes the four selected columns of every foreground row (nbox == 1: of every row, a background row's as the signed zeros
+// sign(d - t) * 0).  Workgroups 1.. (nbox > 1 only) write the zeros of every other (row, class) group of four, one float4 per thread and
+// array: every element is written exactly once by this launch, none twice.  PER_CLASS = nbox > 1, known at compile time: with the column
+// offset a constant 0, the class-agnostic instance loads deltas / std logits without waiting for the row's class.
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+template <bool PER_CLASS>
 __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restrict__ deltas, const float* __restrict__ stdl, long long ld,
                                                          const long long* __restrict__ cls, const float* __restrict__ prop,
                                                          const float* __restrict__ gtb, const float* __restrict__ gstd, int R,
-                                                         int num_classes, int mode, float wx, float wy, float clampv, float ts_better,
-                                                         float t_cert, float* __restrict__ sum, float* __restrict__ gd,
+                                                         int num_classes, int nbox, int mode, float wx, float wy, float clampv,
+                                                         float ts_better, float t_cert, float* __restrict__ sum, float* __restrict__ gd,
                                                          float* __restrict__ gs) {
+  if (!PER_CLASS) nbox = 1;
+  if (PER_CLASS && blockIdx.x != 0) {
+    const long long groups = (long long)R * nbox, step = (long long)(gridDim.x - 1) * blockDim.x;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long g = (long long)(blockIdx.x - 1) * blockDim.x + threadIdx.x; g < groups; g += step) {
+      const long long r = g / nbox, b = g - r * nbox, c = cls[r];
+      const long long sel = (c >= 0 && c < num_classes) ? c : -1;
+      if (b != sel) {
+        *(float4*)(gd + g * 4) = z;
+        *(float4*)(gs + g * 4) = z;
+      }
+    }
+    return;
+  }
   __shared__ float red[256];
   float acc = 0.f;
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
@@ -981,13 +1000,16 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
       pb = *(const float4*)(prop + (size_t)r * 4);
       gb = *(const float4*)(gtb + (size_t)r * 4);
     }
-    const float d[4] = {deltas[(size_t)r * ld], deltas[(size_t)r * ld + 1], deltas[(size_t)r * ld + 2], deltas[(size_t)r * ld + 3]};
-    const float sl[4] = {stdl[(size_t)r * ld], stdl[(size_t)r * ld + 1], stdl[(size_t)r * ld + 2], stdl[(size_t)r * ld + 3]};
+    const size_t co = (fg && PER_CLASS) ? (size_t)c * 4 : 0;   // a background / empty row reads columns 0..3: its terms are all masked
+    const float* dr = deltas + (size_t)r * ld + co;
+    const float* sr = stdl + (size_t)r * ld + co;
+    const float d[4] = {dr[0], dr[1], dr[2], dr[3]};
+    const float sl[4] = {sr[0], sr[1], sr[2], sr[3]};
     const float sw = pb.z - pb.x + 1.f, sh = pb.w - pb.y + 1.f;
     const float t[4] = {wx * (gb.x - pb.x) / sw, wx * (gb.z - pb.z) / sw, wy * (gb.y - pb.y) / sh, wy * (gb.w - pb.w) / sh};
     float g_d[4] = {0.f, 0.f, 0.f, 0.f}, g_s[4] = {0.f, 0.f, 0.f, 0.f};
     const float fgf = fg ? 1.f : 0.f;
-    if (mode == 2) {
+    if (!PER_CLASS && mode == 2) {   // (the entry point refuses the per-class form)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float ct = 1.f - sigmoidf_(gstd ? gstd[(size_t)r * 4 + k] : 0.f), cs = 1.f - sigmoidf_(sl[k]);
@@ -1050,119 +1072,7 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
         }
       }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      gd[(size_t)r * 4 + k] = g_d[k];
-      gs[(size_t)r * 4 + k] = g_s[k];
-    }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sum[0] = red[0];
-}
-
-// Per-class regression (CLS_AGNOSTIC_BBOX_REG False): 4 * nbox delta / std columns per row; a foreground row reads - and its derivatives
-// go to - the four columns of its class, 4 * cls .. 4 * cls + 3 (fast_rcnn.py:950-959, :1036-1045); gd / gs are [R][4 * nbox].  Workgroup 0
-// is the loss: roi_box_loss_kernel's modes 0 / 1 / 3 restated line by line (a shared body changed that kernel's register allocation, so it
-// is kept apart) - same expressions, same row -> thread assignment, same summation tree, so the two give the same bits on the same four
-// columns - and writes the selected columns of every foreground row.  Workgroups 1.. write the zeros of every other (row, class) group of
-// four, one float4 per thread and array: every element is written exactly once by this launch, none twice.
-__global__ __launch_bounds__(256) void roi_box_loss_pc_kernel(const float* __restrict__ deltas, const float* __restrict__ stdl, long long ld,
-                                                            const long long* __restrict__ cls, const float* __restrict__ prop,
-                                                            const float* __restrict__ gtb, int R, int num_classes, int nbox, int mode,
-                                                            float wx, float wy, float clampv, float* __restrict__ sum,
-                                                            float* __restrict__ gd, float* __restrict__ gs) {
-  if (blockIdx.x != 0) {
-    const long long groups = (long long)R * nbox, step = (long long)(gridDim.x - 1) * blockDim.x;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long g = (long long)(blockIdx.x - 1) * blockDim.x + threadIdx.x; g < groups; g += step) {
-      const long long r = g / nbox, b = g - r * nbox, c = cls[r];
-      const long long sel = nbox == 1 ? 0 : ((c >= 0 && c < num_classes) ? c : -1);
-      if (b != sel) {
-        *(float4*)(gd + g * 4) = z;
-        *(float4*)(gs + g * 4) = z;
-      }
-    }
-    return;
-  }
-  __shared__ float red[256];
-  float acc = 0.f;
-  for (int r = threadIdx.x; r < R; r += blockDim.x) {
-    const long long c = cls[r];
-    const bool fg = c >= 0 && c < num_classes;
-    float4 pb = make_float4(0.f, 0.f, 1.f, 1.f), gb = pb;
-    if (fg) {
-      pb = *(const float4*)(prop + (size_t)r * 4);
-      gb = *(const float4*)(gtb + (size_t)r * 4);
-    }
-    const size_t co = (fg && nbox > 1) ? (size_t)c * 4 : 0;   // a background / empty row reads columns 0..3: its terms are all masked
-    const float* dr = deltas + (size_t)r * ld + co;
-    const float* sr = stdl + (size_t)r * ld + co;
-    const float d[4] = {dr[0], dr[1], dr[2], dr[3]};
-    const float sl[4] = {sr[0], sr[1], sr[2], sr[3]};
-    const float sw = pb.z - pb.x + 1.f, sh = pb.w - pb.y + 1.f;
-    const float t[4] = {wx * (gb.x - pb.x) / sw, wx * (gb.z - pb.z) / sw, wy * (gb.y - pb.y) / sh, wy * (gb.w - pb.w) / sh};
-    float g_d[4] = {0.f, 0.f, 0.f, 0.f}, g_s[4] = {0.f, 0.f, 0.f, 0.f};
-    const float fgf = fg ? 1.f : 0.f;
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float df = d[k] - t[k];
-        if (fg) acc += fabsf(df);
-        g_d[k] = (df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * fgf;
-      }
-      if (mode == 0) {
-        const float w = pb.z - pb.x, h = pb.w - pb.y;
-        const float wd[4] = {wx, wx, wy, wy};
-        const float side[4] = {w, w, h, h};
-        float q[4], dq[4];   // clamped delta / weight and its derivative w.r.t. the delta
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float v = d[k] / wd[k];
-          q[k] = v > clampv ? clampv : v < -clampv ? -clampv : v;   // NaN stays NaN like torch.clamp
-          dq[k] = (v >= -clampv && v <= clampv) ? side[k] / wd[k] : 0.f;
-        }
-        const float px1 = q[0] * w + pb.x, px2 = q[1] * w + pb.z, py1 = q[2] * h + pb.y, py2 = q[3] * h + pb.w;
-        const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
-        const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
-        const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
-        const float I = whx * why, U = a1 + a2 - I;
-        const float iou = fg ? I / U : 0.f;
-        float nll = 0.f, sig[4], sq[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sig[k] = sigmoidf_(sl[k]);
-          sq[k] = sig[k] * sig[k];
-          const float df = t[k] - d[k];
-          nll += df * df / (2.f * sq[k]) + 0.5f * logf(sq[k]);
-        }
-        nll += 2.f * 1.8378770664093453f;  // 2 log(2 pi)
-        // (foreground rows only, as the reference indexes them: on a background row a std logit below -88 makes nll = inf - inf, and
-        // NaN * 0 would put a NaN into the loss VALUE - the gradients below were always guarded)
-        if (fg) acc += 0.05f * (nll * iou);
-        if (fg) {
-          // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
-          const float cx = (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = (rby - lty) >= 0.f ? 1.f : 0.f;
-          const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-          const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-          // order of the deltas: x1, x2, y1, y2
-          const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
-          const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float diou = (dI[k] * (U + I) - I * dA[k]) / (U * U) * dq[k];
-            const float df = d[k] - t[k];
-            g_d[k] += 0.05f * (iou * df / sq[k] + nll * diou);
-            g_s[k] = 0.05f * iou * (1.f - sig[k]) * (1.f - df * df / sq[k]);
-          }
-        }
-      }
-    }
-    if (fg || nbox == 1) {
+    if (fg || !PER_CLASS) {
       *(float4*)(gd + (size_t)r * 4 * nbox + co) = make_float4(g_d[0], g_d[1], g_d[2], g_d[3]);
       *(float4*)(gs + (size_t)r * 4 * nbox + co) = make_float4(g_s[0], g_s[1], g_s[2], g_s[3]);
     }
@@ -1179,13 +1089,18 @@ __global__ __launch_bounds__(256) void roi_box_loss_pc_kernel(const float* __res
 // ---------------------------------------------------------------------------------------------
 // The predictor's inference chain (roi_heads/fast_rcnn.py:1094-1125,1162-1225 + D2 fast_rcnn_inference [D2-recall]) around the exact
 // top-k and the class-aware NMS: three launches in place of ~55 ATen ops per teacher pass.
-//   keys:   one thread per (image, proposal): Box2BoxXYXYTransform.apply_deltas (box_regression.py:88-128: divide by the weight, clamp to
-//           +-scale_clamp, scale by the proposal's width / height, add to its corner), clip to the image, and for every foreground
-//           class a sortable 63-bit key of its probability - (order-preserving float bits) << 32 | (2^32 - 1 - flat index) - or the
-//           key of -1 when the class is not a candidate (probability <= thr, invalid slot, non-finite box or probabilities).
+// Layout: deltas [N*P][4 * nbox], nbox = 1 (class-agnostic: one decoded box per proposal) or K (CLS_AGNOSTIC_BBOX_REG False: one per
+// (proposal, class), fast_rcnn.py:1162-1185); boxes [N][P][nbox][4].
+//   keys:   one WAVE per (image, proposal), lane l takes boxes / classes l, l + 64, ...: Box2BoxXYXYTransform.apply_deltas
+//           (box_regression.py:88-128: divide by the weight, clamp to +-scale_clamp, scale by the proposal's width / height, add to its
+//           corner), clip to the image, and for every foreground class a sortable 63-bit key of its probability - (order-preserving
+//           float bits) << 32 | (2^32 - 1 - flat index p*K + c) - or the key of -1 when the class is not a candidate (probability <= thr,
+//           invalid slot, non-finite box or probabilities).  D2 fast_rcnn_inference_single_image filters ROWS: one non-finite decoded box
+//           (any class) or probability drops all K candidates of the proposal - the wave votes.
 //           Descending key order == (probability desc, flat (proposal, class) index asc): the tie rule of the ATen chain it replaces.
-//   gather: the k best keys of an image -> probability (recovered from the key), proposal row, class, decoded box, candidate flag
-//   pack:   the NMS survivors -> padded detections (+ the raw std logits of their proposal rows, fast_rcnn.py:1118-1123)
+//   gather: the k best keys of an image -> probability (recovered from the key), proposal row, class, the decoded box of (row, class) -
+//           nbox == 1: of the row -, candidate flag
+//   pack:   the NMS survivors -> padded detections (+ the 4 * nbox raw std logits of their proposal rows, fast_rcnn.py:1118-1123)
 __device__ __forceinline__ long long order_key_f32(float v, unsigned flat) {
   const int i = __float_as_int(v);
   const long long mono = (long long)(i ^ ((i >> 31) & 0x7FFFFFFF));
@@ -1194,81 +1109,8 @@ __device__ __forceinline__ long long order_key_f32(float v, unsigned flat) {
 
 __global__ __launch_bounds__(256) void roi_infer_keys_kernel(const float* __restrict__ probs, const float* __restrict__ deltas,
                                                            const float* __restrict__ prop, const unsigned char* __restrict__ valid,
-                                                           const float* __restrict__ whwh, int N, int P, int K, float wx, float wy,
+                                                           const float* __restrict__ whwh, int N, int P, int K, int nbox, float wx, float wy,
                                                            float clampv, float thr, float* __restrict__ boxes, long long* __restrict__ keys) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)N * P) return;
-  const int n = (int)(t / P), p = (int)(t - (long long)n * P);
-  const float4 b = *(const float4*)(prop + t * 4);
-  const float4 d = *(const float4*)(deltas + t * 4);
-  const float w = b.z - b.x, h = b.w - b.y;
-  auto cl = [clampv](float v) { return v < -clampv ? -clampv : (v > clampv ? clampv : v); };   // a NaN stays a NaN (torch.clamp)
-  // ATen divides a tensor by a host scalar as a multiplication by its fp32 reciprocal: the same here, so that the boxes are bit-identical
-  // to the op chain this replaces (a true division differs in the last bit for weights like 10)
-  const float iwx = 1.f / wx, iwy = 1.f / wy;
-  const float dl = cl(d.x * iwx), dr = cl(d.y * iwx), dd = cl(d.z * iwy), du = cl(d.w * iwy);
-  float4 o;
-  o.x = dl * w + b.x; o.y = dd * h + b.y; o.z = dr * w + b.z; o.w = du * h + b.w;
-  bool ok = valid[t] != 0 && isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(o.w);
-  const float4 lim = *(const float4*)(whwh + n * 4);
-  o.x = fminf(fmaxf(o.x, 0.f), lim.x); o.y = fminf(fmaxf(o.y, 0.f), lim.y); o.z = fminf(fmaxf(o.z, 0.f), lim.z); o.w = fminf(fmaxf(o.w, 0.f), lim.w);
-  *(float4*)(boxes + t * 4) = o;
-  const float* pr = probs + t * (K + 1);
-  for (int c = 0; c < K; ++c) ok = ok && isfinite(pr[c]);
-  long long* kr = keys + (long long)n * P * K + (long long)p * K;
-  for (int c = 0; c < K; ++c) {
-    const float v = pr[c];
-    kr[c] = order_key_f32((ok && v > thr) ? v : -1.f, (unsigned)(p * K + c));
-  }
-}
-
-__global__ __launch_bounds__(256) void roi_infer_gather_kernel(const long long* __restrict__ top, const float* __restrict__ boxes, int N,
-                                                             int P, int K, int k, float thr, float* __restrict__ sc, long long* __restrict__ rows,
-                                                             int* __restrict__ cls, float* __restrict__ cb, unsigned char* __restrict__ valid) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)N * k) return;
-  const int n = (int)(t / k);
-  const long long key = top[t];
-  const unsigned flat = 4294967295u - (unsigned)(key & 0xFFFFFFFFll);
-  const int mono = (int)(key >> 32);
-  const float v = __int_as_float(mono ^ ((mono >> 31) & 0x7FFFFFFF));
-  const unsigned r = flat / (unsigned)K;
-  sc[t] = v;
-  rows[t] = (long long)r;
-  cls[t] = (int)(flat - r * (unsigned)K);
-  *(float4*)(cb + t * 4) = *(const float4*)(boxes + ((long long)n * P + r) * 4);
-  valid[t] = v > thr ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void roi_infer_pack_kernel(const int* __restrict__ kidx, const int* __restrict__ cnt, const float* __restrict__ cb,
-                                                           const float* __restrict__ sc, const int* __restrict__ cls, const long long* __restrict__ rows,
-                                                           const float* __restrict__ stdl, int N, int P, int k, int D, float* __restrict__ oboxes,
-                                                           float* __restrict__ oscores, int* __restrict__ ocls, float* __restrict__ ostd,
-                                                           long long* __restrict__ orows, unsigned char* __restrict__ ovalid) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= N * D) return;
-  const int n = t / D, d = t - n * D;
-  int ix = kidx[t];
-  ix = ix < 0 ? 0 : ix;
-  const long long src = (long long)n * k + ix;
-  *(float4*)(oboxes + (long long)t * 4) = *(const float4*)(cb + src * 4);
-  oscores[t] = sc[src];
-  ocls[t] = cls[src];
-  const long long r = rows[src];
-  orows[t] = r;
-  *(float4*)(ostd + (long long)t * 4) = *(const float4*)(stdl + ((long long)n * P + r) * 4);
-  ovalid[t] = d < cnt[n] ? 1 : 0;
-}
-
-// Per-class regression (CLS_AGNOSTIC_BBOX_REG False): deltas [N*P][4K], one decoded box per (proposal, class) (fast_rcnn.py:1162-1185).
-//   keys:   one WAVE per (image, proposal), lane l takes classes l, l + 64, ...: boxes [N][P][K][4]; the candidate key and its flat index
-//           p*K + c are those of the class-agnostic kernel.  D2 fast_rcnn_inference_single_image filters ROWS: one non-finite decoded box
-//           (any class) or probability drops all K candidates of the proposal - the wave votes.
-//   gather: cb = the box of (row, class);  pack: the kept row's 4K std logits (fast_rcnn.py:1123)
-__global__ __launch_bounds__(256) void roi_infer_keys_pc_kernel(const float* __restrict__ probs, const float* __restrict__ deltas,
-                                                              const float* __restrict__ prop, const unsigned char* __restrict__ valid,
-                                                              const float* __restrict__ whwh, int N, int P, int K, float wx, float wy,
-                                                              float clampv, float thr, float* __restrict__ boxes, long long* __restrict__ keys) {
   const long long t = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
   const int lane = threadIdx.x & 63;
   if (t >= (long long)N * P) return;
@@ -1277,18 +1119,21 @@ __global__ __launch_bounds__(256) void roi_infer_keys_pc_kernel(const float* __r
   const float4 lim = *(const float4*)(whwh + n * 4);
   const float w = b.z - b.x, h = b.w - b.y;
   auto cl = [clampv](float v) { return v < -clampv ? -clampv : (v > clampv ? clampv : v); };   // a NaN stays a NaN (torch.clamp)
-  const float iwx = 1.f / wx, iwy = 1.f / wy;   // (see roi_infer_keys_kernel: ATen's division by a host scalar)
+  // ATen divides a tensor by a host scalar as a multiplication by its fp32 reciprocal: the same here, so that the boxes are bit-identical
+  // to the op chain this replaces (a true division differs in the last bit for weights like 10)
+  const float iwx = 1.f / wx, iwy = 1.f / wy;
   const float* pr = probs + t * (K + 1);
   bool fin = true;
-  for (int c = lane; c < K; c += 64) {
-    const float4 d = *(const float4*)(deltas + (t * K + c) * 4);
+  for (int c = lane; c < nbox; c += 64) {
+    const float4 d = *(const float4*)(deltas + (t * nbox + c) * 4);
     const float dl = cl(d.x * iwx), dr = cl(d.y * iwx), dd = cl(d.z * iwy), du = cl(d.w * iwy);
     float4 o;
     o.x = dl * w + b.x; o.y = dd * h + b.y; o.z = dr * w + b.z; o.w = du * h + b.w;
-    fin = fin && isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(o.w) && isfinite(pr[c]);
+    fin = fin && isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(o.w);
     o.x = fminf(fmaxf(o.x, 0.f), lim.x); o.y = fminf(fmaxf(o.y, 0.f), lim.y); o.z = fminf(fmaxf(o.z, 0.f), lim.z); o.w = fminf(fmaxf(o.w, 0.f), lim.w);
-    *(float4*)(boxes + (t * K + c) * 4) = o;
+    *(float4*)(boxes + (t * nbox + c) * 4) = o;
   }
+  for (int c = lane; c < K; c += 64) fin = fin && isfinite(pr[c]);
   const bool ok = valid[t] != 0 && __all(fin ? 1 : 0);
   long long* kr = keys + (long long)n * P * K + (long long)p * K;
   for (int c = lane; c < K; c += 64) {
@@ -1297,32 +1142,32 @@ __global__ __launch_bounds__(256) void roi_infer_keys_pc_kernel(const float* __r
   }
 }
 
-__global__ __launch_bounds__(256) void roi_infer_gather_pc_kernel(const long long* __restrict__ top, const float* __restrict__ boxes, int N,
-                                                                int P, int K, int k, float thr, float* __restrict__ sc,
-                                                                long long* __restrict__ rows, int* __restrict__ cls, float* __restrict__ cb,
-                                                                unsigned char* __restrict__ valid) {
+__global__ __launch_bounds__(256) void roi_infer_gather_kernel(const long long* __restrict__ top, const float* __restrict__ boxes, int N,
+                                                             int P, int K, int nbox, int k, float thr, float* __restrict__ sc,
+                                                             long long* __restrict__ rows, int* __restrict__ cls, float* __restrict__ cb,
+                                                             unsigned char* __restrict__ valid) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)N * k) return;
   const int n = (int)(t / k);
   const long long key = top[t];
-  const unsigned flat = 4294967295u - (unsigned)(key & 0xFFFFFFFFll);   // < P*K for every key utv2_roi_infer_keys_pc wrote
+  const unsigned flat = 4294967295u - (unsigned)(key & 0xFFFFFFFFll);   // < P*K for every key utv2_roi_infer_keys wrote
   const int mono = (int)(key >> 32);
   const float v = __int_as_float(mono ^ ((mono >> 31) & 0x7FFFFFFF));
-  const unsigned r = flat / (unsigned)K;
+  const unsigned r = flat / (unsigned)K, c = flat - r * (unsigned)K;
   sc[t] = v;
   rows[t] = (long long)r;
-  cls[t] = (int)(flat - r * (unsigned)K);
-  *(float4*)(cb + t * 4) = *(const float4*)(boxes + ((long long)n * P * K + flat) * 4);
+  cls[t] = (int)c;
+  *(float4*)(cb + t * 4) = *(const float4*)(boxes + (((long long)n * P + r) * nbox + (nbox == 1 ? 0u : c)) * 4);
   valid[t] = v > thr ? 1 : 0;
 }
 
-// one thread per (image, detection slot, group of four std logits): nstd = 4 * nbox floats per kept row
-__global__ __launch_bounds__(256) void roi_infer_pack_pc_kernel(const int* __restrict__ kidx, const int* __restrict__ cnt, const float* __restrict__ cb,
-                                                              const float* __restrict__ sc, const int* __restrict__ cls,
-                                                              const long long* __restrict__ rows, const float* __restrict__ stdl, int N, int P,
-                                                              int k, int D, int nbox, float* __restrict__ oboxes, float* __restrict__ oscores,
-                                                              int* __restrict__ ocls, float* __restrict__ ostd, long long* __restrict__ orows,
-                                                              unsigned char* __restrict__ ovalid) {
+// one thread per (image, detection slot, group of four std logits): 4 * nbox floats per kept row
+__global__ __launch_bounds__(256) void roi_infer_pack_kernel(const int* __restrict__ kidx, const int* __restrict__ cnt, const float* __restrict__ cb,
+                                                           const float* __restrict__ sc, const int* __restrict__ cls,
+                                                           const long long* __restrict__ rows, const float* __restrict__ stdl, int N, int P,
+                                                           int k, int D, int nbox, float* __restrict__ oboxes, float* __restrict__ oscores,
+                                                           int* __restrict__ ocls, float* __restrict__ ostd, long long* __restrict__ orows,
+                                                           unsigned char* __restrict__ ovalid) {
   const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= (long long)N * D * nbox) return;
   const long long t = u / nbox;
@@ -1586,54 +1431,32 @@ static int fill_rpn_levels(RpnLevels& L, int num_levels, int N, const int* hw_ho
 }
 
 int utv2_roi_infer_keys(const float* probs, const float* deltas, const float* prop, const unsigned char* valid, const float* whwh, int N, int P,
-                        int K, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, hipStream_t stream) {
-  if (!probs || !deltas || !prop || !valid || !whwh || !boxes || !keys || N < 1 || P < 1 || K < 1 || (int64_t)P * K >= (1ll << 32)) return UTV2_EARG;
-  hipLaunchKernelGGL(roi_infer_keys_kernel, dim3((unsigned)cdiv((long long)N * P, 256)), dim3(256), 0, stream, probs, deltas, prop, valid, whwh, N,
-                     P, K, wx, wy, scale_clamp, thr, boxes, (long long*)keys);
+                        int K, int nbox, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, hipStream_t stream) {
+  if (!probs || !deltas || !prop || !valid || !whwh || !boxes || !keys || N < 1 || P < 1 || K < 1 || (nbox != K && nbox != 1) ||
+      (int64_t)P * K >= (1ll << 32))
+    return UTV2_EARG;
+  hipLaunchKernelGGL(roi_infer_keys_kernel, dim3((unsigned)cdiv((long long)N * P, 4)), dim3(256), 0, stream, probs, deltas, prop, valid, whwh, N,
+                     P, K, nbox, wx, wy, scale_clamp, thr, boxes, (long long*)keys);
   return utv2_launch_status();
 }
 
-int utv2_roi_infer_gather(const int64_t* top, const float* boxes, int N, int P, int K, int k, float thr, float* sc, int64_t* rows, int* cls,
-                          float* cb, unsigned char* valid, hipStream_t stream) {
-  if (!top || !boxes || !sc || !rows || !cls || !cb || !valid || N < 1 || P < 1 || K < 1 || k < 1) return UTV2_EARG;
+int utv2_roi_infer_gather(const int64_t* top, const float* boxes, int N, int P, int K, int nbox, int k, float thr, float* sc, int64_t* rows,
+                          int* cls, float* cb, unsigned char* valid, hipStream_t stream) {
+  if (!top || !boxes || !sc || !rows || !cls || !cb || !valid || N < 1 || P < 1 || K < 1 || (nbox != K && nbox != 1) || k < 1 ||
+      (int64_t)P * K >= (1ll << 32))
+    return UTV2_EARG;
   hipLaunchKernelGGL(roi_infer_gather_kernel, dim3((unsigned)cdiv((long long)N * k, 256)), dim3(256), 0, stream, (const long long*)top, boxes, N, P,
-                     K, k, thr, sc, (long long*)rows, cls, cb, valid);
+                     K, nbox, k, thr, sc, (long long*)rows, cls, cb, valid);
   return utv2_launch_status();
 }
 
 int utv2_roi_infer_pack(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows, const float* stdl,
-                        int N, int P, int k, int D, float* oboxes, float* oscores, int* ocls, float* ostd, int64_t* orows, unsigned char* ovalid,
-                        hipStream_t stream) {
-  if (!kidx || !cnt || !cb || !sc || !cls || !rows || !stdl || !oboxes || !oscores || !ocls || !ostd || !orows || !ovalid || N < 1 || D < 1)
-    return UTV2_EARG;
-  hipLaunchKernelGGL(roi_infer_pack_kernel, dim3((unsigned)cdiv((long long)N * D, 256)), dim3(256), 0, stream, kidx, cnt, cb, sc, cls,
-                     (const long long*)rows, stdl, N, P, k, D, oboxes, oscores, ocls, ostd, (long long*)orows, ovalid);
-  return utv2_launch_status();
-}
-
-int utv2_roi_infer_keys_pc(const float* probs, const float* deltas, const float* prop, const unsigned char* valid, const float* whwh, int N,
-                           int P, int K, float wx, float wy, float scale_clamp, float thr, float* boxes, int64_t* keys, hipStream_t stream) {
-  if (!probs || !deltas || !prop || !valid || !whwh || !boxes || !keys || N < 1 || P < 1 || K < 1 || (int64_t)P * K >= (1ll << 32)) return UTV2_EARG;
-  hipLaunchKernelGGL(roi_infer_keys_pc_kernel, dim3((unsigned)cdiv((long long)N * P, 4)), dim3(256), 0, stream, probs, deltas, prop, valid, whwh,
-                     N, P, K, wx, wy, scale_clamp, thr, boxes, (long long*)keys);
-  return utv2_launch_status();
-}
-
-int utv2_roi_infer_gather_pc(const int64_t* top, const float* boxes, int N, int P, int K, int k, float thr, float* sc, int64_t* rows, int* cls,
-                             float* cb, unsigned char* valid, hipStream_t stream) {
-  if (!top || !boxes || !sc || !rows || !cls || !cb || !valid || N < 1 || P < 1 || K < 1 || k < 1 || (int64_t)P * K >= (1ll << 32)) return UTV2_EARG;
-  hipLaunchKernelGGL(roi_infer_gather_pc_kernel, dim3((unsigned)cdiv((long long)N * k, 256)), dim3(256), 0, stream, (const long long*)top, boxes, N,
-                     P, K, k, thr, sc, (long long*)rows, cls, cb, valid);
-  return utv2_launch_status();
-}
-
-int utv2_roi_infer_pack_pc(const int* kidx, const int* cnt, const float* cb, const float* sc, const int* cls, const int64_t* rows,
-                           const float* stdl, int N, int P, int k, int D, int nbox, float* oboxes, float* oscores, int* ocls, float* ostd,
-                           int64_t* orows, unsigned char* ovalid, hipStream_t stream) {
+                        int N, int P, int k, int D, int nbox, float* oboxes, float* oscores, int* ocls, float* ostd, int64_t* orows,
+                        unsigned char* ovalid, hipStream_t stream) {
   if (!kidx || !cnt || !cb || !sc || !cls || !rows || !stdl || !oboxes || !oscores || !ocls || !ostd || !orows || !ovalid || N < 1 || D < 1 ||
       nbox < 1)
     return UTV2_EARG;
-  hipLaunchKernelGGL(roi_infer_pack_pc_kernel, dim3((unsigned)cdiv((long long)N * D * nbox, 256)), dim3(256), 0, stream, kidx, cnt, cb, sc, cls,
+  hipLaunchKernelGGL(roi_infer_pack_kernel, dim3((unsigned)cdiv((long long)N * D * nbox, 256)), dim3(256), 0, stream, kidx, cnt, cb, sc, cls,
                      (const long long*)rows, stdl, N, P, k, D, nbox, oboxes, oscores, ocls, ostd, (long long*)orows, ovalid);
   return utv2_launch_status();
 }
@@ -1771,23 +1594,15 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
 }
 
 int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
-                      const float* gstd, int R, int num_classes, int mode, float wx, float wy, float scale_clamp, float ts_better,
+                      const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
                       float t_cert, float* sum, float* gdeltas, float* gstd_out, hipStream_t stream) {
-  if (!deltas || !stdl || !cls || !prop || !gtb || !sum || !gdeltas || !gstd_out || R < 0 || ld < 4 || mode < 0 || mode > 3) return UTV2_EARG;
-  hipLaunchKernelGGL(roi_box_loss_kernel, dim3(1), dim3(256), 0, stream, deltas, stdl, (long long)ld, (const long long*)cls, prop, gtb, gstd, R,
-                     num_classes, mode, wx, wy, scale_clamp, ts_better, t_cert, sum, gdeltas, gstd_out);
-  return utv2_launch_status();
-}
-
-int utv2_roi_box_loss_pc(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb, int R,
-                         int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float* sum, float* gdeltas,
-                         float* gstd_out, hipStream_t stream) {
   if (!deltas || !stdl || !cls || !prop || !gtb || !sum || !gdeltas || !gstd_out || R < 0 || num_classes < 1 ||
-      (nbox != num_classes && nbox != 1) || ld < 4 * (int64_t)nbox || (mode != 0 && mode != 1 && mode != 3))
+      (nbox != num_classes && nbox != 1) || ld < 4 * (int64_t)nbox || mode < 0 || mode > 3 || (mode == 2 && nbox > 1))
     return UTV2_EARG;
-  const long long fill = nbox > 1 ? cdiv((long long)R * nbox, 256) : 0;
-  hipLaunchKernelGGL(roi_box_loss_pc_kernel, dim3(1 + (unsigned)(fill < 1024 ? fill : 1024)), dim3(256), 0, stream, deltas, stdl, (long long)ld,
-                     (const long long*)cls, prop, gtb, R, num_classes, nbox, mode, wx, wy, scale_clamp, sum, gdeltas, gstd_out);
+  const long long fill = nbox > 1 ? cdiv((long long)R * nbox, 256) : 0;   // the zero-filling workgroups
+  hipLaunchKernelGGL(nbox > 1 ? roi_box_loss_kernel<true> : roi_box_loss_kernel<false>, dim3(1 + (unsigned)(fill < 1024 ? fill : 1024)), dim3(256), 0,
+                     stream, deltas, stdl, (long long)ld, (const long long*)cls, prop, gtb, gstd, R, num_classes, nbox, mode, wx, wy, scale_clamp,
+                     ts_better, t_cert, sum, gdeltas, gstd_out);
   return utv2_launch_status();
 }
 

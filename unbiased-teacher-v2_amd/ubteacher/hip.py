@@ -910,100 +910,51 @@ def nms_pack(kidx, cnt, boxes, scores):
     return ob, osc, ov
 
 
-def roi_infer_keys(probs, deltas, prop, valid, whwh, K, wx, wy, scale_clamp, thr):
-    """-> (decoded + clipped boxes [N, P, 4], sortable keys [N, P*K]) - see utv2_roi_infer_keys"""
+def roi_infer_keys(probs, deltas, prop, valid, whwh, K, wx, wy, scale_clamp, thr, nbox=1):
+    """deltas [N*P, 4*nbox] -> (decoded + clipped boxes [N, P, 4] - nbox > 1: [N, P, nbox, 4] -, sortable keys [N, P*K]) - see
+    utv2_roi_infer_keys"""
     N, P = valid.shape
-    boxes = torch.empty((N, P, 4), dtype=torch.float32, device=probs.device)
+    assert tuple(deltas.shape) == (N * P, 4 * nbox)
+    boxes = torch.empty((N, P, 4) if nbox == 1 else (N, P, nbox, 4), dtype=torch.float32, device=probs.device)
     keys = torch.empty((N, P * K), dtype=torch.int64, device=probs.device)
-    call("utv2_roi_infer_keys", _p(probs), _p(deltas), _p(prop), _p(valid), _p(whwh), N, P, K, float(wx), float(wy), float(scale_clamp), float(thr),
-         _p(boxes), _p(keys), _stream())
-    return boxes, keys
-
-
-def roi_infer_gather(top, boxes, K, thr):
-    N, k = top.shape
-    P = boxes.shape[1]
-    dev = top.device
-    sc = torch.empty((N, k), dtype=torch.float32, device=dev)
-    rows = torch.empty((N, k), dtype=torch.int64, device=dev)
-    cls = torch.empty((N, k), dtype=torch.int32, device=dev)
-    cb = torch.empty((N, k, 4), dtype=torch.float32, device=dev)
-    valid = torch.empty((N, k), dtype=torch.uint8, device=dev)
-    call("utv2_roi_infer_gather", _p(top), _p(boxes), N, P, K, k, float(thr), _p(sc), _p(rows), _p(cls), _p(cb), _p(valid), _stream())
-    return sc, rows, cls, cb, valid
-
-
-def roi_infer_pack(kidx, cnt, cb, sc, cls, rows, std, P, D):
-    N, k = sc.shape
-    dev = sc.device
-    ob = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
-    osc = torch.empty((N, D), dtype=torch.float32, device=dev)
-    oc = torch.empty((N, D), dtype=torch.int32, device=dev)
-    ostd = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
-    orows = torch.empty((N, D), dtype=torch.int64, device=dev)
-    ov = torch.empty((N, D), dtype=torch.uint8, device=dev)
-    call("utv2_roi_infer_pack", _p(kidx), _p(cnt), _p(cb), _p(sc), _p(cls), _p(rows), _p(std), N, P, k, D, _p(ob), _p(osc), _p(oc), _p(ostd),
-         _p(orows), _p(ov), _stream())
-    return ob, osc, oc, ostd, orows, ov
-
-
-def roi_box_loss(deltas, std, cls, prop, gtb, gstd, num_classes, mode, wx, wy, scale_clamp, ts_better, t_cert):
-    """(sum [1], d sum / d deltas [R,4], d sum / d std [R,4]); deltas / std may be column slices of the predictor output (row pitch = stride(0))"""
-    R = deltas.shape[0]
-    assert deltas.dtype == torch.float32 and std.dtype == torch.float32 and deltas.stride(1) == 1 and std.stride(1) == 1
-    assert deltas.stride(0) == std.stride(0) and cls.dtype == torch.int64
-    dev = deltas.device
-    out = torch.empty(1, dtype=torch.float32, device=dev)
-    gd = torch.empty((R, 4), dtype=torch.float32, device=dev)
-    gs = torch.empty((R, 4), dtype=torch.float32, device=dev)
-    call("utv2_roi_box_loss", c_p(deltas.data_ptr()), c_p(std.data_ptr()), deltas.stride(0), _p(cls), _p(prop), _p(gtb), _p(gstd), R, num_classes,
-         mode, float(wx), float(wy), float(scale_clamp), float(ts_better), float(t_cert), _p(out), _p(gd), _p(gs), _stream())
-    return out, gd, gs
-
-
-def roi_infer_keys_pc(probs, deltas, prop, valid, whwh, K, wx, wy, scale_clamp, thr):
-    """per-class regression: deltas [N*P, 4K] -> (decoded + clipped boxes [N, P, K, 4], sortable keys [N, P*K]) - see utv2_roi_infer_keys_pc"""
-    N, P = valid.shape
-    assert tuple(deltas.shape) == (N * P, 4 * K) and deltas.is_contiguous()
-    boxes = torch.empty((N, P, K, 4), dtype=torch.float32, device=probs.device)
-    keys = torch.empty((N, P * K), dtype=torch.int64, device=probs.device)
-    call("utv2_roi_infer_keys_pc", _p(probs), _p(deltas), _p(prop), _p(valid), _p(whwh), N, P, K, float(wx), float(wy), float(scale_clamp),
+    call("utv2_roi_infer_keys", _p(probs), _p(deltas), _p(prop), _p(valid), _p(whwh), N, P, K, nbox, float(wx), float(wy), float(scale_clamp),
          float(thr), _p(boxes), _p(keys), _stream())
     return boxes, keys
 
 
-def roi_infer_gather_pc(top, boxes, K, thr):
+def roi_infer_gather(top, boxes, K, thr):
+    """boxes [N, P, 4] (class-agnostic) or [N, P, K, 4] (per-class: the candidate takes the box of its class)"""
     N, k = top.shape
     P = boxes.shape[1]
-    assert tuple(boxes.shape) == (N, P, K, 4)
+    nbox = 1 if boxes.dim() == 3 else boxes.shape[2]
     dev = top.device
     sc = torch.empty((N, k), dtype=torch.float32, device=dev)
     rows = torch.empty((N, k), dtype=torch.int64, device=dev)
     cls = torch.empty((N, k), dtype=torch.int32, device=dev)
     cb = torch.empty((N, k, 4), dtype=torch.float32, device=dev)
     valid = torch.empty((N, k), dtype=torch.uint8, device=dev)
-    call("utv2_roi_infer_gather_pc", _p(top), _p(boxes), N, P, K, k, float(thr), _p(sc), _p(rows), _p(cls), _p(cb), _p(valid), _stream())
+    call("utv2_roi_infer_gather", _p(top), _p(boxes), N, P, K, nbox, k, float(thr), _p(sc), _p(rows), _p(cls), _p(cb), _p(valid), _stream())
     return sc, rows, cls, cb, valid
 
 
-def roi_infer_pack_pc(kidx, cnt, cb, sc, cls, rows, std, P, D, nbox):
+def roi_infer_pack(kidx, cnt, cb, sc, cls, rows, std, P, D, nbox=1):
     N, k = sc.shape
     dev = sc.device
-    assert std.is_contiguous() and std.numel() == N * P * 4 * nbox
+    assert std.numel() == N * P * 4 * nbox
     ob = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
     osc = torch.empty((N, D), dtype=torch.float32, device=dev)
     oc = torch.empty((N, D), dtype=torch.int32, device=dev)
     ostd = torch.empty((N, D, 4 * nbox), dtype=torch.float32, device=dev)
     orows = torch.empty((N, D), dtype=torch.int64, device=dev)
     ov = torch.empty((N, D), dtype=torch.uint8, device=dev)
-    call("utv2_roi_infer_pack_pc", _p(kidx), _p(cnt), _p(cb), _p(sc), _p(cls), _p(rows), _p(std), N, P, k, D, nbox, _p(ob), _p(osc), _p(oc),
+    call("utv2_roi_infer_pack", _p(kidx), _p(cnt), _p(cb), _p(sc), _p(cls), _p(rows), _p(std), N, P, k, D, nbox, _p(ob), _p(osc), _p(oc),
          _p(ostd), _p(orows), _p(ov), _stream())
     return ob, osc, oc, ostd, orows, ov
 
 
-def roi_box_loss_pc(deltas, std, cls, prop, gtb, num_classes, nbox, mode, wx, wy, scale_clamp):
-    """(sum [1], d sum / d deltas [R, 4*nbox], d sum / d std [R, 4*nbox]) with a foreground row's four columns chosen by its class;
-    deltas / std may be column slices of the predictor output (row pitch = stride(0))"""
+def roi_box_loss(deltas, std, cls, prop, gtb, gstd, num_classes, mode, wx, wy, scale_clamp, ts_better, t_cert, nbox=1):
+    """(sum [1], d sum / d deltas [R, 4*nbox], d sum / d std [R, 4*nbox]); nbox > 1: a foreground row's four columns are chosen by its
+    class.  deltas / std may be column slices of the predictor output (row pitch = stride(0))"""
     R = deltas.shape[0]
     assert deltas.dtype == torch.float32 and std.dtype == torch.float32 and deltas.stride(1) == 1 and std.stride(1) == 1
     assert deltas.stride(0) == std.stride(0) and cls.dtype == torch.int64
@@ -1012,8 +963,8 @@ def roi_box_loss_pc(deltas, std, cls, prop, gtb, num_classes, nbox, mode, wx, wy
     out = torch.empty(1, dtype=torch.float32, device=dev)
     gd = torch.empty((R, 4 * nbox), dtype=torch.float32, device=dev)
     gs = torch.empty((R, 4 * nbox), dtype=torch.float32, device=dev)
-    call("utv2_roi_box_loss_pc", c_p(deltas.data_ptr()), c_p(std.data_ptr()), deltas.stride(0), _p(cls), _p(prop), _p(gtb), R, num_classes,
-         nbox, mode, float(wx), float(wy), float(scale_clamp), _p(out), _p(gd), _p(gs), _stream())
+    call("utv2_roi_box_loss", c_p(deltas.data_ptr()), c_p(std.data_ptr()), deltas.stride(0), _p(cls), _p(prop), _p(gtb), _p(gstd), R, num_classes,
+         nbox, mode, float(wx), float(wy), float(scale_clamp), float(ts_better), float(t_cert), _p(out), _p(gd), _p(gs), _stream())
     return out, gd, gs
 
 

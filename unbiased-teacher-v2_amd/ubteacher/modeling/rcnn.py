@@ -136,14 +136,9 @@ class _RoiBoxLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, deltas, std, cls, prop, gtb, gstd, pred, mode):
-        t = pred.box2box_transform
-        if pred.nbox > 1:   # per-class regression: the four columns of each foreground row's class (utv2_roi_box_loss_pc)
-            out, gd, gs = hip.roi_box_loss_pc(deltas.detach(), std.detach(), cls, prop, gtb, pred.num_classes, pred.nbox, mode, t.weights[0],
-                                              t.weights[1], t.scale_clamp)
-            ctx.save_for_backward(gd, gs)
-            return out
+        t = pred.box2box_transform   # (pred.nbox > 1, per-class regression: the four columns of each foreground row's class)
         out, gd, gs = hip.roi_box_loss(deltas.detach(), std.detach(), cls, prop, gtb, gstd, pred.num_classes, mode, t.weights[0], t.weights[1],
-                                       t.scale_clamp, pred.ts_better, pred.t_cert)
+                                       t.scale_clamp, pred.ts_better, pred.t_cert, pred.nbox)
         ctx.save_for_backward(gd, gs)
         return out
 
@@ -518,11 +513,17 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
 
     @torch.no_grad()
     def inference(self, predictions, proposals, max_cand=8192):
-        """fast_rcnn.py:1094-1125 + D2 fast_rcnn_inference: softmax, score > thr, class-aware NMS, top-k."""
+        """fast_rcnn.py:1094-1125 + D2 fast_rcnn_inference: softmax, score > thr, class-aware NMS, top-k.  Per-class regression
+        (nbox = K, fast_rcnn.py:1162-1185): K decoded boxes per proposal, a candidate (row, class) takes the box of its class, and
+        pred_boxes_std is the kept row's full [4K] std logits (fast_rcnn.py:1123).  Either way a proposal with any non-finite decoded box
+        or probability is dropped (D2 fast_rcnn_inference_single_image filters rows); the fused kernels and the ATen chain below them
+        give identical detections."""
         scores, deltas, std = predictions
         N, P = proposals["valid"].shape
-        K = self.K
+        K, nbox = self.K, self.nbox
         pb = proposals["boxes"]
+        D = self.test_topk_per_image
+        kk = min(max_cand, P * K)
         cache = self.__dict__.setdefault("_hwt_cache", {})   # a fresh torch.tensor(..., device=cuda) is a synchronizing pageable copy
         ck = (tuple(proposals.image_sizes), str(pb.device))
         hwt = cache.get(ck)
@@ -530,8 +531,6 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             if len(cache) >= 16:
                 cache.clear()
             hwt = cache[ck] = torch.tensor([[s[1], s[0], s[1], s[0]] for s in proposals.image_sizes], dtype=torch.float32, device=pb.device)[:, None, :]
-        if self.nbox > 1:
-            return self._inference_per_class(scores, deltas, std, proposals, hwt, cache, max_cand)
         if os.environ.get("UTV2_FUSED_ROI_INFERENCE", "1") != "0" and scores.dtype == deltas.dtype == std.dtype == torch.float32 and P * K < (1 << 32):
             # round 4: decode + clip + candidate keys, the gather behind the top-k and the packing of the NMS survivors as three launches
             # (utv2_roi_infer_*) around softmax / topk / utv2_nms_batched - the chain below is ~55 ATen launches per teacher pass.
@@ -539,11 +538,10 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             pr = F.softmax(scores, dim=-1).contiguous()
             wx, wy = self.box2box_transform.weights[0], self.box2box_transform.weights[1]
             dec, keys = hip.roi_infer_keys(pr, deltas.contiguous(), pb.contiguous(), proposals["valid"].contiguous(), hwt.view(N, 4), K, wx, wy,
-                                           self.box2box_transform.scale_clamp, self.test_score_thresh)
+                                           self.box2box_transform.scale_clamp, self.test_score_thresh, nbox=nbox)
             # the (probability desc, flat index asc) top candidates of every image: the exact radix select of the FCOS / RPN top-k
             # (utv2_topk_rows_i64, 9 launches) - torch.topk on an [N, P*K = 80 000] matrix with k = 8192 is ~40 launches (multi-block radix
             # select + segmented sort); same keys, same order (distinct keys: the selected set and its order are unique)
-            kk = min(max_cand, P * K)
             if os.environ.get("UTV2_ROI_TOPK", "1") != "0" and kk <= 8192:
                 ro = cache.get(("row_off", N, P * K, str(pb.device)))
                 if ro is None:
@@ -552,63 +550,10 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             else:
                 top = torch.topk(keys, kk, dim=1, sorted=True).values
             sc, r, c, cb, valid = hip.roi_infer_gather(top, dec, K, self.test_score_thresh)
-            D = self.test_topk_per_image
             kidx, cnt = hip.nms_batched(cb, sc, c, valid, self.test_nms_thresh, class_aware=True, post_topk=-1, max_out=D)
-            ob, osc, oc, ostd, keep_rows, ov = hip.roi_infer_pack(kidx, cnt, cb, sc, c, r, std.contiguous(), P, D)
+            ob, osc, oc, ostd, keep_rows, ov = hip.roi_infer_pack(kidx, cnt, cb, sc, c, r, std.contiguous(), P, D, nbox=nbox)
             return PaddedBoxes(proposals.image_sizes, boxes=ob, scores=osc, classes=oc, pred_boxes_std=ostd, valid=ov, count=cnt), keep_rows
-        boxes = self.box2box_transform.apply_deltas(deltas.view(N, P, 4), pb)
-        probs = F.softmax(scores, dim=-1).view(N, P, K + 1)[:, :, :K]
-        ok = proposals["valid"].bool() & torch.isfinite(boxes).all(dim=2) & torch.isfinite(probs).all(dim=2)
-        boxes = torch.minimum(boxes.clamp(min=0), hwt)
-        cand = (probs > self.test_score_thresh) & ok[:, :, None]
-        flat = torch.where(cand, probs, torch.full_like(probs, -1.0)).reshape(N, P * K)
-        k = min(max_cand, P * K)
-        top = torch.topk(float_order_key(flat), k, dim=1, sorted=True).values
-        idx = 4294967295 - (top & 4294967295)
-        sc = torch.gather(flat, 1, idx)
-        r, c = idx // K, (idx % K).to(torch.int32)
-        cb = torch.gather(boxes, 1, r[:, :, None].expand(-1, -1, 4)).contiguous()
-        valid = (sc > self.test_score_thresh).to(torch.uint8)
-        D = self.test_topk_per_image
-        kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), self.test_nms_thresh,
-                                    class_aware=True, post_topk=-1, max_out=D)
-        ix = kidx.clamp(min=0).long()
-        keep_rows = torch.gather(r, 1, ix)
-        out = PaddedBoxes(proposals.image_sizes,
-                          boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
-                          scores=torch.gather(sc, 1, ix).contiguous(),
-                          classes=torch.gather(c, 1, ix).contiguous(),
-                          pred_boxes_std=torch.gather(std.view(N, P, 4), 1, keep_rows[:, :, None].expand(-1, -1, 4)).contiguous(),
-                          valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
-        return out, keep_rows
-
-    def _inference_per_class(self, scores, deltas, std, proposals, hwt, cache, max_cand):
-        """inference() with per-class regression (fast_rcnn.py:1162-1185): K decoded boxes per proposal, a candidate (row, class) takes the
-        box of its class, a proposal with any non-finite decoded box is dropped (D2 fast_rcnn_inference_single_image filters rows), and
-        pred_boxes_std is the kept row's full [4K] std logits (fast_rcnn.py:1123).  Same candidate keys and order as the class-agnostic
-        chain; the fused kernels (utv2_roi_infer_*_pc) and the ATen chain below them give identical detections."""
-        N, P = proposals["valid"].shape
-        K = self.K
-        pb = proposals["boxes"]
-        D = self.test_topk_per_image
-        kk = min(max_cand, P * K)
-        if os.environ.get("UTV2_FUSED_ROI_INFERENCE", "1") != "0" and scores.dtype == deltas.dtype == std.dtype == torch.float32 and P * K < (1 << 32):
-            pr = F.softmax(scores, dim=-1).contiguous()
-            wx, wy = self.box2box_transform.weights[0], self.box2box_transform.weights[1]
-            dec, keys = hip.roi_infer_keys_pc(pr, deltas.contiguous(), pb.contiguous(), proposals["valid"].contiguous(), hwt.view(N, 4), K, wx, wy,
-                                              self.box2box_transform.scale_clamp, self.test_score_thresh)
-            if os.environ.get("UTV2_ROI_TOPK", "1") != "0" and kk <= 8192:
-                ro = cache.get(("row_off", N, P * K, str(pb.device)))
-                if ro is None:
-                    ro = cache[("row_off", N, P * K, str(pb.device))] = (torch.arange(N + 1, dtype=torch.int64) * (P * K)).to(pb.device)
-                top = hip.topk_rows(keys.view(-1), ro, N, P * K, kk)
-            else:
-                top = torch.topk(keys, kk, dim=1, sorted=True).values
-            sc, r, c, cb, valid = hip.roi_infer_gather_pc(top, dec, K, self.test_score_thresh)
-            kidx, cnt = hip.nms_batched(cb, sc, c, valid, self.test_nms_thresh, class_aware=True, post_topk=-1, max_out=D)
-            ob, osc, oc, ostd, keep_rows, ov = hip.roi_infer_pack_pc(kidx, cnt, cb, sc, c, r, std.contiguous(), P, D, K)
-            return PaddedBoxes(proposals.image_sizes, boxes=ob, scores=osc, classes=oc, pred_boxes_std=ostd, valid=ov, count=cnt), keep_rows
-        boxes = self.box2box_transform.apply_deltas(deltas.view(N, P, K, 4), pb[:, :, None, :])      # [N, P, K, 4]
+        boxes = self.box2box_transform.apply_deltas(deltas.view(N, P, nbox, 4), pb[:, :, None, :])      # [N, P, nbox, 4]
         probs = F.softmax(scores, dim=-1).view(N, P, K + 1)[:, :, :K]
         ok = proposals["valid"].bool() & torch.isfinite(boxes).all(dim=3).all(dim=2) & torch.isfinite(probs).all(dim=2)
         boxes = torch.minimum(boxes.clamp(min=0), hwt[:, :, None, :])
@@ -618,7 +563,8 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
         idx = 4294967295 - (top & 4294967295)
         sc = torch.gather(flat, 1, idx)
         r, c = idx // K, (idx % K).to(torch.int32)
-        cb = torch.gather(boxes.reshape(N, P * K, 4), 1, idx[:, :, None].expand(-1, -1, 4)).contiguous()     # the box of (row, class)
+        # the box of the row (nbox == 1) or of (row, class)
+        cb = torch.gather(boxes.reshape(N, P * nbox, 4), 1, (r if nbox == 1 else idx)[:, :, None].expand(-1, -1, 4)).contiguous()
         valid = (sc > self.test_score_thresh).to(torch.uint8)
         kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), self.test_nms_thresh,
                                     class_aware=True, post_topk=-1, max_out=D)
@@ -628,7 +574,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
                           boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
                           scores=torch.gather(sc, 1, ix).contiguous(),
                           classes=torch.gather(c, 1, ix).contiguous(),
-                          pred_boxes_std=torch.gather(std.reshape(N, P, 4 * K), 1, keep_rows[:, :, None].expand(-1, -1, 4 * K)).contiguous(),
+                          pred_boxes_std=torch.gather(std.reshape(N, P, 4 * nbox), 1, keep_rows[:, :, None].expand(-1, -1, 4 * nbox)).contiguous(),
                           valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
         return out, keep_rows
 
