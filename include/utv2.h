@@ -396,8 +396,34 @@ int utv2_match_boxes(const float* boxes, int64_t box_img_stride, int N, int P, c
 int utv2_match_lowq(const float* boxes, int64_t box_img_stride, int N, int P, const float* gt_boxes,
                     const unsigned char* gt_valid, int G, const unsigned* gt_max_bits, unsigned char* lowq,
                     utv2_stream_t stream);
-/* torchvision roi_align(aligned=True, sampling_ratio=0) through D2 ROIPooler level assignment
- * (roi_heads/roi_heads.py:28-45,118).  feats_host / dfeats_host: HOST arrays of device pointers. */
+/* The ROI pooler (D2 ROIPooler, roi_heads/roi_heads.py:28-45,118: level assignment with canonical size 224 at level 4) in the three
+ * forms of MODEL.ROI_BOX_HEAD.POOLER_TYPE.  feats_host / dfeats_host: HOST arrays of device pointers.
+ *   UTV2_POOLER_ALIGN_V2  "ROIAlignV2": torchvision roi_align, aligned=True (half-pixel shift, empty boxes pool nothing)
+ *   UTV2_POOLER_ALIGN     "ROIAlign":   torchvision roi_align, aligned=False (no shift, sides floored at one pixel)
+ *   UTV2_POOLER_MAX       "ROIPool":    torchvision roi_pool (rounded corners, maximum per bin)
+ * sampling_ratio (RoIAlign only; ignored by UTV2_POOLER_MAX): samples per bin and axis, 0 = ceil(bin size in pixels).
+ * argmax (UTV2_POOLER_MAX only, otherwise NULL) [R][PH][PW][C] int32: written by fwd, read by bwd - per output element the index
+ * y * W + x of its maximum inside the ROI's (level, image) map, -1 where the bin's window is empty or the slot invalid.
+ * fwd: features / out are `dtype`.  bwd: fp32 atomic scatter into zero-filled dfeats, any ROI order.  bwd_tiled: deterministic gather
+ * over 8 x 8 pixel tiles, the ROIs of image n are rois[n*rois_per_image .. (n+1)*rois_per_image), C <= 256, PH, PW <= 7; every element
+ * of every dfeats[l] ([N][H_l][W_l][C], element type out_dtype) is written - no zero-fill, no atomics. */
+#define UTV2_POOLER_ALIGN_V2 0
+#define UTV2_POOLER_ALIGN 1
+#define UTV2_POOLER_MAX 2
+int utv2_roi_pooler_fwd(int pooler, int sampling_ratio, int num_levels, int min_level, const void* const* feats_host,
+                        const int* H_host, const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
+                        const unsigned char* roi_valid, int R, int C, int PH, int PW, void* out, int* argmax, int dtype,
+                        utv2_stream_t stream);
+int utv2_roi_pooler_bwd(int pooler, int sampling_ratio, int num_levels, int min_level, float* const* dfeats_host, const int* H_host,
+                        const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
+                        const unsigned char* roi_valid, int R, int C, int PH, int PW, const void* dy, const int* argmax, int dtype,
+                        utv2_stream_t stream);
+int utv2_roi_pooler_bwd_tiled(int pooler, int sampling_ratio, int num_levels, int min_level, void* const* dfeats_host,
+                              const int* H_host, const int* W_host, const float* scales_host, const float* rois,
+                              const unsigned char* roi_valid, int N, int rois_per_image, int C, int PH, int PW, const void* dy,
+                              const int* argmax, int dy_dtype, int out_dtype, utv2_stream_t stream);
+/* the same three entry points at (UTV2_POOLER_ALIGN_V2, 0), the shipped configs' pooler:
+ * torchvision roi_align(aligned=True, sampling_ratio=0) */
 int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_host, const int* H_host,
                        const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
                        const unsigned char* roi_valid, int R, int C, int PH, int PW, void* out, int dtype,

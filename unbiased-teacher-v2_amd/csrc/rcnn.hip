@@ -98,16 +98,47 @@ static bool env_on(const char* name) {   // A/B switches, read once per process:
 }
 
 // ---------------------------------------------------------------------------------------------
-// Multi-level RoIAlign, aligned=True, sampling_ratio=0 (torchvision.ops.roi_align via D2 ROIPooler,
-// roi_heads/roi_heads.py:28-45,118 [D2-recall]).  Features NHWC per level, output [R][PH][PW][C].
+// Multi-level ROI pooler (D2 ROIPooler, roi_heads/roi_heads.py:28-45,118 [D2-recall]): torchvision.ops.roi_align with aligned=True
+// (POOLER_TYPE "ROIAlignV2", the shipped configs) or aligned=False ("ROIAlign"), sampling_ratio 0 (adaptive) or fixed, and
+// torchvision.ops.roi_pool ("ROIPool", further down).  Features NHWC per level, output [R][PH][PW][C].
 // Level: clamp(floor(canonical_level + log2(sqrt(area)/canonical_size + 1e-8)), min_level, max_level).
+// pooler codes of the C-ABI (include/utv2.h)
+#define UTV2_POOLER_ALIGN_V2 0
+#define UTV2_POOLER_ALIGN 1
+#define UTV2_POOLER_MAX 2
+
 struct RoiLevels {
   const void* feat[4];   // element type = the launch's T
   float* dfeat[4];
   int H[4], W[4];
   float scale[4];
   int num_levels, min_level;
+  int aligned, ratio;    // RoIAlign: half-pixel shift on / off, samples per bin and axis (0 = ceil(bin size))
 };
+
+// RoIAlign geometry of one ROI on its level.  aligned: the box is shifted by half a pixel and may be empty (then no samples);
+// not aligned (Detectron v1): no shift, and width / height are floored at one pixel.  Samples per bin and axis: the fixed ratio, or
+// ceil(bin size) in pixels.
+struct RoiGeom {
+  float x1, y1, bw, bh, cnt;
+  int gh, gw;
+};
+
+__device__ __forceinline__ RoiGeom roi_geom(const float4& b, float sc, int PH, int PW, int aligned, int ratio) {
+  const float off = aligned ? 0.5f : 0.f;
+  RoiGeom g;
+  g.x1 = b.x * sc - off;
+  g.y1 = b.y * sc - off;
+  const float x2 = b.z * sc - off, y2 = b.w * sc - off;
+  float rw = x2 - g.x1, rh = y2 - g.y1;
+  if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
+  g.bw = rw / (float)PW;
+  g.bh = rh / (float)PH;
+  g.gh = ratio > 0 ? ratio : (int)ceilf(rh / (float)PH);
+  g.gw = ratio > 0 ? ratio : (int)ceilf(rw / (float)PW);
+  g.cnt = fmaxf((float)(g.gh * g.gw), 1.f);
+  return g;
+}
 
 __device__ __forceinline__ int roi_level(const float4& b, const RoiLevels& L) {
   const float area = (b.z - b.x) * (b.w - b.y);
@@ -119,6 +150,12 @@ __device__ __forceinline__ int roi_level(const float4& b, const RoiLevels& L) {
 // The gh x gw bilinear samples of a bin are SEPARABLE: sample (iy, ix) puts weight wy(iy, Y) * wx(ix, X) on pixel (Y, X) and is
 // skipped iff its y or its x is out of range, so the total weight of a pixel is WY[Y] * WX[X] with WY / WX summed per axis.
 // A bin therefore touches (rows x cols) pixels once - (gh+1)(gw+1) loads / atomics instead of 4*gh*gw.
+// Table size: the g samples of a bin lie inside the bin, so they touch at most floor(bin size) + 2 pixels of an axis whatever g is.
+// Adaptive grid (g = ceil(bin size)): the level assignment keeps sqrt(area) of a ROI below 2 * 224 / 16 = 28 pixels of its level, the
+// bin below 28 / PH, except on the coarsest level, where an image-sized ROI of a 1333 x 800 input has bins of 42 / PH <= 8.4 pixels
+// at PH >= 5: <= 10 pixels.  Fixed ratio: the g samples carry at most 2 * g distinct taps (P * 2 * ratio per axis and ROI), but they
+// spread over the same floor(bin size) + 2 pixels, and the table is indexed by pixel, so the bound on the bin size is the same.
+// A bin of more than ROI_MAXT - 2 = 16 pixels (a box far longer than wide) takes the sample-by-sample path below, in every mode.
 #define ROI_MAXT 18  // taps per axis kept in registers; larger bins (never with the D2 level assignment) take the slow path
 struct AxisTaps {
   int lo, n;            // first pixel index, number of pixels
@@ -179,11 +216,9 @@ __global__ __launch_bounds__(64) void roi_align_kernel(RoiLevels L, const float*
   const int li = roi_level(b, L);
   const int H = L.H[li], W = L.W[li];
   const float sc = L.scale[li];
-  const float x1 = b.x * sc - 0.5f, y1 = b.y * sc - 0.5f, x2 = b.z * sc - 0.5f, y2 = b.w * sc - 0.5f;
-  const float rw = x2 - x1, rh = y2 - y1;
-  const float bw = rw / (float)PW, bh = rh / (float)PH;
-  const int gh = (int)ceilf(rh / (float)PH), gw = (int)ceilf(rw / (float)PW);
-  const float cnt = fmaxf((float)(gh * gw), 1.f);
+  const RoiGeom q = roi_geom(b, sc, PH, PW, L.aligned, L.ratio);
+  const float x1 = q.x1, y1 = q.y1, bw = q.bw, bh = q.bh, cnt = q.cnt;
+  const int gh = q.gh, gw = q.gw;
   const int n = roi_batch[r];
   const T* f = (const T*)L.feat[li] + (size_t)n * H * W * C;
   float* df = BWD ? L.dfeat[li] + (size_t)n * H * W * C : nullptr;
@@ -306,11 +341,9 @@ __global__ __launch_bounds__(256) void roi_align_fwd_roi_kernel(RoiLevels L, con
   const int li = roi_level(b, L);
   const int H = L.H[li], W = L.W[li];
   const float sc = L.scale[li];
-  const float x1 = b.x * sc - 0.5f, y1 = b.y * sc - 0.5f, x2 = b.z * sc - 0.5f, y2 = b.w * sc - 0.5f;
-  const float rw = x2 - x1, rh = y2 - y1;
-  const float bw = rw / (float)PW, bh = rh / (float)PH;
-  const int gh = (int)ceilf(rh / (float)PH), gw = (int)ceilf(rw / (float)PW);
-  const float cnt = fmaxf((float)(gh * gw), 1.f);
+  const RoiGeom q = roi_geom(b, sc, PH, PW, L.aligned, L.ratio);
+  const float x1 = q.x1, y1 = q.y1, bw = q.bw, bh = q.bh, cnt = q.cnt;
+  const int gh = q.gh, gw = q.gw;
   const T* f = (const T*)L.feat[li] + (size_t)roi_batch[r] * H * W * C;
   if (tid == 0) all_fit = 1;
   __syncthreads();
@@ -416,6 +449,7 @@ struct RoiBwdArgs {
   float scale[4];
   int tile_start[5];    // first block of each level (tiles_y * tiles_x * N blocks per level)
   int num_levels, min_level, N, P, C, PH, PW;
+  int aligned, ratio;   // RoIAlign mode (see RoiLevels)
 };
 
 template <typename TI, typename TO>
@@ -458,7 +492,10 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
       if (!roi_valid || roi_valid[r]) {
         const float4 bx = ((const float4*)rois)[r];
         if (roi_level(bx, LV) == li) {
-          const float y1 = bx.y * sc - 0.5f, y2 = bx.w * sc - 0.5f, x1 = bx.x * sc - 0.5f, x2 = bx.z * sc - 0.5f;
+          const float off = a.aligned ? 0.5f : 0.f;
+          const float y1 = bx.y * sc - off, x1 = bx.x * sc - off;
+          float y2 = bx.w * sc - off, x2 = bx.z * sc - off;
+          if (!a.aligned) { y2 = fmaxf(y2, y1 + 1.f); x2 = fmaxf(x2, x1 + 1.f); }   // sides floored at one pixel
           // pixels a sample in [lo, hi] can put weight on: floor(max(lo, 0)) .. floor(hi) + 1 (a superset is harmless)
           const int ylo = (int)floorf(fmaxf(y1, 0.f)), yhi = (int)floorf(fmaxf(y2, 0.f)) + 1;
           const int xlo = (int)floorf(fmaxf(x1, 0.f)), xhi = (int)floorf(fmaxf(x2, 0.f)) + 1;
@@ -481,10 +518,9 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
     for (int k = 0; k < total; ++k) {
       const int r = n * a.P + list[k];
       const float4 bx = ((const float4*)rois)[r];
-      const float x1 = bx.x * sc - 0.5f, y1 = bx.y * sc - 0.5f, x2 = bx.z * sc - 0.5f, y2 = bx.w * sc - 0.5f;
-      const float rw = x2 - x1, rh = y2 - y1;
-      const float bw = rw / (float)a.PW, bh = rh / (float)a.PH;
-      const int gh = (int)ceilf(rh / (float)a.PH), gw = (int)ceilf(rw / (float)a.PW);
+      const RoiGeom q = roi_geom(bx, sc, a.PH, a.PW, a.aligned, a.ratio);
+      const float x1 = q.x1, y1 = q.y1, bw = q.bw, bh = q.bh;
+      const int gh = q.gh, gw = q.gw;
       // weight tables: thread (axis, p, t) sums the taps of the bin's samples on tile row / column t
       if (tid < 2 * 7 * RB_T) {
         const int axis = tid / (7 * RB_T), rem = tid - axis * 7 * RB_T, pb = rem / RB_T, t = rem - pb * RB_T;
@@ -508,7 +544,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
       }
       __syncthreads();
       if (cok) {
-        const float inv = 1.f / fmaxf((float)(gh * gw), 1.f);
+        const float inv = 1.f / q.cnt;
         const TI* g0 = dy + (size_t)r * a.PH * a.PW * a.C;
         for (int ph = 0; ph < a.PH; ++ph) {
           const float w0 = wy[ph * RB_T + 2 * wid], w1 = wy[ph * RB_T + 2 * wid + 1];
@@ -542,6 +578,232 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int y = ty0 + 2 * wid + r;
+      if (y >= H) continue;
+#pragma unroll
+      for (int x = 0; x < RB_T; ++x) {
+        if (tx0 + x >= W) continue;
+        st4(out + ((size_t)y * W + tx0 + x) * a.C, lane, acc[r][x]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// RoIPool (torchvision.ops.roi_pool; POOLER_TYPE "ROIPool"): the box corners are ROUNDED to pixels of the ROI's level (roundf: halves
+// away from zero), the box is at least one pixel wide and high, and bin (ph, pw) is the maximum over the pixel window
+//   rows floor(ph * bin_h) + y1 .. ceil((ph + 1) * bin_h) + y1, clipped to [0, H)     (columns alike, bin_h = roi_h / PH in float)
+// scanned row-major with a strict `>`: the first maximum wins.  argmax [R][PH][PW][C] int32 is that pixel's index y * W + x inside the
+// (level, image) map, -1 (and output 0) for an empty window or an invalid slot.  The gradient of an output goes to its argmax pixel.
+struct PoolBox {
+  int x1, y1;
+  float bw, bh;
+};
+
+__device__ __forceinline__ PoolBox pool_box(const float4& b, float sc, int PH, int PW) {
+  // corners far outside the map are pulled to +-2^24 pixels before the cast: the windows they give are clipped to the map anyway
+  const float lim = 16777216.f;
+  PoolBox p;
+  p.x1 = (int)fminf(fmaxf(roundf(b.x * sc), -lim), lim);
+  p.y1 = (int)fminf(fmaxf(roundf(b.y * sc), -lim), lim);
+  const int x2 = (int)fminf(fmaxf(roundf(b.z * sc), -lim), lim), y2 = (int)fminf(fmaxf(roundf(b.w * sc), -lim), lim);
+  p.bw = (float)max(x2 - p.x1 + 1, 1) / (float)PW;
+  p.bh = (float)max(y2 - p.y1 + 1, 1) / (float)PH;
+  return p;
+}
+
+__device__ __forceinline__ void pool_window(int p, float bin, int first, int size, int& lo, int& hi) {
+  lo = min(max((int)floorf((float)p * bin) + first, 0), size);
+  hi = min(max((int)ceilf((float)(p + 1) * bin) + first, 0), size);
+}
+
+// forward: one 256-thread workgroup per ROI, a thread takes (bin, 16-byte channel group) items and scans the bin's window with one
+// 16-byte load per pixel.  The maximum is taken on values widened to float, so a 16-bit output is one of its inputs, exactly.
+template <typename T>
+__global__ __launch_bounds__(256) void roi_pool_fwd_kernel(RoiLevels L, const float* __restrict__ rois, const int* __restrict__ roi_batch,
+                                                         const unsigned char* __restrict__ roi_valid, int C, int PH, int PW,
+                                                         T* __restrict__ out, int* __restrict__ argmax) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int CQ = C / V, items = PH * PW * CQ;
+  T* o = out + (size_t)r * PH * PW * C;
+  int* am = argmax + (size_t)r * PH * PW * C;
+  const bool ok = roi_valid ? roi_valid[r] != 0 : true;
+  const float4 b = ((const float4*)rois)[r];
+  const int li = ok ? roi_level(b, L) : 0;
+  const int H = L.H[li], W = L.W[li];
+  const PoolBox pb = pool_box(b, L.scale[li], PH, PW);
+  const T* f = (const T*)L.feat[li] + (size_t)(ok ? roi_batch[r] : 0) * H * W * C;
+  for (int it = tid; it < items; it += 256) {
+    const int bin = it / CQ, cq = it - bin * CQ;
+    const int ph = bin / PW, pw = bin - ph * PW;
+    int hs = 0, he = 0, ws = 0, we = 0;
+    if (ok) {
+      pool_window(ph, pb.bh, pb.y1, H, hs, he);
+      pool_window(pw, pb.bw, pb.x1, W, ws, we);
+    }
+    const bool empty = he <= hs || we <= ws;
+    float mx[V];
+    int ix[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) { mx[e] = empty ? 0.f : -3.402823466e+38f; ix[e] = -1; }
+    if (!empty) {
+      for (int h = hs; h < he; ++h)
+        for (int w = ws; w < we; ++w) {
+          const T* src = f + ((size_t)h * W + w) * C + cq * V;
+          float v[V];
+          if constexpr (sizeof(T) == 2) {
+            const bf16x8_t t = *(const bf16x8_t*)src;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+          } else {
+            const f32x4 t = *(const f32x4*)src;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = t[e];
+          }
+#pragma unroll
+          for (int e = 0; e < V; ++e)
+            if (v[e] > mx[e]) { mx[e] = v[e]; ix[e] = h * W + w; }
+        }
+    }
+    T* dst = o + (size_t)bin * C + cq * V;
+    int* adst = am + (size_t)bin * C + cq * V;
+    if constexpr (sizeof(T) == 2) {
+      bf16x8_t ov;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ov[e] = (h16_t)mx[e];
+      *(bf16x8_t*)dst = ov;
+    } else {
+      *(f32x4*)dst = f32x4{mx[0], mx[1], mx[2], mx[3]};
+    }
+#pragma unroll
+    for (int e = 0; e < V; e += 4) *(int4*)(adst + e) = int4{ix[e], ix[e + 1], ix[e + 2], ix[e + 3]};
+  }
+}
+
+// backward, general ROI layout: one wave per (roi, bin) adds dy to the argmax pixels with fp32 atomics (dfeats zero-filled by the caller)
+template <typename T>
+__global__ __launch_bounds__(64) void roi_pool_bwd_kernel(RoiLevels L, const float* __restrict__ rois, const int* __restrict__ roi_batch,
+                                                        const unsigned char* __restrict__ roi_valid, int C, int PH, int PW,
+                                                        const T* __restrict__ dy, const int* __restrict__ argmax) {
+  const int r = blockIdx.x / (PH * PW);
+  if (roi_valid && roi_valid[r] == 0) return;
+  const float4 b = ((const float4*)rois)[r];
+  const int li = roi_level(b, L);
+  const int HW = L.H[li] * L.W[li];
+  float* df = L.dfeat[li] + (size_t)roi_batch[r] * HW * C;
+  const int C4 = C >> 2;
+  const T* g0 = dy + (size_t)blockIdx.x * C;
+  const int* a0 = argmax + (size_t)blockIdx.x * C;
+  for (int c = threadIdx.x; c < C4; c += 64) {
+    const f32x4 g = ld4(g0, c);
+    const int4 am = ((const int4*)a0)[c];
+    const int idx[4] = {am.x, am.y, am.z, am.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (idx[e] >= 0 && idx[e] < HW) atomicAdd(df + (size_t)idx[e] * C + 4 * c + e, g[e]);
+  }
+}
+
+// backward as a deterministic gather, the layout of roi_align_bwd_tiled: a workgroup owns an 8 x 8 pixel tile (lane -> 4 channels,
+// wave w -> tile rows 2w, 2w + 1), lists the image's ROIs whose (rounded, clipped) box meets the tile, and walks their bins in fixed
+// (roi, ph, pw) order; of a bin whose window meets the wave's rows and the tile's columns it reads argmax and dy once and adds dy to the
+// pixel the argmax names.  Every element of every gradient map is written, in its final type.
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const float* __restrict__ rois, const unsigned char* __restrict__ roi_valid,
+                                                         const TI* __restrict__ dy, const int* __restrict__ argmax) {
+  __shared__ int list[256];
+  __shared__ int wcount[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int li = 0;
+#pragma unroll
+  for (int l = 1; l < 4; ++l)
+    if (l < a.num_levels && (int)blockIdx.x >= a.tile_start[l]) li = l;
+  const int H = a.H[li], W = a.W[li];
+  const int tx_n = (W + RB_T - 1) / RB_T, ty_n = (H + RB_T - 1) / RB_T;
+  int b = blockIdx.x - a.tile_start[li];
+  const int n = b / (tx_n * ty_n);
+  b -= n * tx_n * ty_n;
+  const int ty0 = (b / tx_n) * RB_T, tx0 = (b % tx_n) * RB_T;
+  const float sc = a.scale[li];
+  const int C4 = a.C >> 2;
+  const bool cok = lane < C4;
+  const int r0 = ty0 + 2 * wid;      // this wave's two rows
+
+  f32x4 acc[2][RB_T];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int x = 0; x < RB_T; ++x) acc[r][x] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  RoiLevels LV;   // only for roi_level()
+  LV.num_levels = a.num_levels;
+  LV.min_level = a.min_level;
+  for (int base = 0; base < a.P; base += 256) {
+    const int slot = base + tid;
+    bool hit = false;
+    if (slot < a.P) {
+      const int r = n * a.P + slot;
+      if (!roi_valid || roi_valid[r]) {
+        const float4 bx = ((const float4*)rois)[r];
+        if (roi_level(bx, LV) == li) {
+          const PoolBox pb = pool_box(bx, sc, a.PH, a.PW);
+          int ylo, yhi, xlo, xhi, t;
+          pool_window(0, pb.bh, pb.y1, H, ylo, t);
+          pool_window(a.PH - 1, pb.bh, pb.y1, H, t, yhi);
+          pool_window(0, pb.bw, pb.x1, W, xlo, t);
+          pool_window(a.PW - 1, pb.bw, pb.x1, W, t, xhi);
+          hit = ylo < ty0 + RB_T && yhi > ty0 && xlo < tx0 + RB_T && xhi > tx0;
+        }
+      }
+    }
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) wcount[wid] = __popcll(m);
+    __syncthreads();
+    int off = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w < wid) off += wcount[w];
+      total += wcount[w];
+    }
+    if (hit) list[off + __popcll(m & ((1ull << lane) - 1ull))] = slot;
+    __syncthreads();
+    if (cok) {
+      for (int k = 0; k < total; ++k) {
+        const int r = n * a.P + list[k];
+        const PoolBox pb = pool_box(((const float4*)rois)[r], sc, a.PH, a.PW);
+        const TI* g0 = dy + (size_t)r * a.PH * a.PW * a.C;
+        const int* a0 = argmax + (size_t)r * a.PH * a.PW * a.C;
+        for (int ph = 0; ph < a.PH; ++ph) {
+          int hs, he;
+          pool_window(ph, pb.bh, pb.y1, H, hs, he);
+          if (he <= r0 || hs > r0 + 1) continue;                // wave-uniform
+          for (int pw = 0; pw < a.PW; ++pw) {
+            int ws, we;
+            pool_window(pw, pb.bw, pb.x1, W, ws, we);
+            if (we <= tx0 || ws >= tx0 + RB_T) continue;        // uniform
+            const f32x4 g = ld4(g0 + (size_t)(ph * a.PW + pw) * a.C, lane);
+            const int4 am = ((const int4*)(a0 + (size_t)(ph * a.PW + pw) * a.C))[lane];
+            const int idx[4] = {am.x, am.y, am.z, am.w};
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+              for (int x = 0; x < RB_T; ++x) {
+                // columns past W are never stored (their index would name a pixel of the next row)
+                const int pix = tx0 + x < W ? (r0 + rr) * W + tx0 + x : -2;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[rr][x][e] += idx[e] == pix ? g[e] : 0.f;
+              }
+          }
+        }
+      }
+    }
+    __syncthreads();   // list is rewritten by the next round
+  }
+  if (cok) {
+    TO* out = (TO*)a.dfeat[li] + (size_t)n * H * W * a.C;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int y = r0 + r;
       if (y >= H) continue;
 #pragma unroll
       for (int x = 0; x < RB_T; ++x) {
@@ -1253,17 +1515,35 @@ static int fill_levels(RoiLevels& L, int num_levels, int min_level, const void* 
 
 // feats_host: host array of num_levels device pointers (NHWC level features of element type `dtype`, same C).
 // rois [R][4] xyxy in image coordinates, roi_batch [R] image index, roi_valid [R] (optional).
-// out [R][PH][PW][C] of element type `dtype`.
-int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_host, const int* H_host, const int* W_host,
-                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
-                       int R, int C, int PH, int PW, void* out, int dtype, hipStream_t stream) {
+// out [R][PH][PW][C] of element type `dtype`; argmax (UTV2_POOLER_MAX only) [R][PH][PW][C] int32.
+static bool pooler_ok(int pooler, int sampling_ratio) {
+  return (pooler == UTV2_POOLER_ALIGN_V2 || pooler == UTV2_POOLER_ALIGN || pooler == UTV2_POOLER_MAX) && sampling_ratio >= 0;
+}
+
+int utv2_roi_pooler_fwd(int pooler, int sampling_ratio, int num_levels, int min_level, const void* const* feats_host, const int* H_host,
+                        const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
+                        const unsigned char* roi_valid, int R, int C, int PH, int PW, void* out, int* argmax, int dtype,
+                        hipStream_t stream) {
   RoiLevels L;
   if (fill_levels(L, num_levels, min_level, feats_host, nullptr, H_host, W_host, scales_host) != UTV2_OK || (C & 3) || !rois ||
-      !roi_batch || !out || (dtype != UTV2_F32 && dtype != UTV2_BF16))
+      !roi_batch || !out || (dtype != UTV2_F32 && dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || PH < 1 || PW < 1)
     return UTV2_EARG;
+  L.aligned = pooler == UTV2_POOLER_ALIGN_V2;
+  L.ratio = sampling_ratio;
+  const int V = dtype == UTV2_BF16 ? 8 : 4;
+  if (pooler == UTV2_POOLER_MAX) {
+    if (!argmax || C % V) return UTV2_EARG;
+    for (int l = 0; l < num_levels; ++l)
+      if ((long long)H_host[l] * W_host[l] > 2147483647ll) return UTV2_EARG;   // argmax is a 32-bit pixel index
+    if (R == 0) return UTV2_OK;
+    if (dtype == UTV2_BF16)
+      hipLaunchKernelGGL((roi_pool_fwd_kernel<h16_t>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)out, argmax);
+    else
+      hipLaunchKernelGGL((roi_pool_fwd_kernel<float>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (float*)out, argmax);
+    return utv2_launch_status();
+  }
   if (R == 0) return UTV2_OK;
   static const bool per_roi = env_on("UTV2_ROI_FWD_PER_ROI");   // A/B: 0 = one wave per (roi, bin)
-  const int V = dtype == UTV2_BF16 ? 8 : 4;
   if (per_roi && PH <= 7 && PW <= 7 && C % V == 0) {
     if (dtype == UTV2_BF16)
       hipLaunchKernelGGL((roi_align_fwd_roi_kernel<h16_t>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)out);
@@ -1280,32 +1560,45 @@ int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_h
   return utv2_launch_status();
 }
 
-// dfeats (fp32, += : caller zero-fills) receive the scatter of dy (element type `dtype`) through the same sampling pattern.
-int utv2_roi_align_bwd(int num_levels, int min_level, float* const* dfeats_host, const int* H_host, const int* W_host,
-                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
-                       int R, int C, int PH, int PW, const void* dy, int dtype, hipStream_t stream) {
+// dfeats (fp32, += : caller zero-fills) receive the scatter of dy (element type `dtype`) through the same sampling pattern
+// (UTV2_POOLER_MAX: through the forward's argmax).
+int utv2_roi_pooler_bwd(int pooler, int sampling_ratio, int num_levels, int min_level, float* const* dfeats_host, const int* H_host,
+                        const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
+                        const unsigned char* roi_valid, int R, int C, int PH, int PW, const void* dy, const int* argmax, int dtype,
+                        hipStream_t stream) {
   RoiLevels L;
   if (fill_levels(L, num_levels, min_level, nullptr, dfeats_host, H_host, W_host, scales_host) != UTV2_OK || (C & 3) || !rois ||
-      !roi_batch || !dy || (dtype != UTV2_F32 && dtype != UTV2_BF16))
+      !roi_batch || !dy || (dtype != UTV2_F32 && dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || PH < 1 || PW < 1 ||
+      (pooler == UTV2_POOLER_MAX && !argmax))
     return UTV2_EARG;
+  L.aligned = pooler == UTV2_POOLER_ALIGN_V2;
+  L.ratio = sampling_ratio;
   if (R == 0) return UTV2_OK;
+  const dim3 g(R * PH * PW), b(64);
+  if (pooler == UTV2_POOLER_MAX) {
+    if (dtype == UTV2_BF16)
+      hipLaunchKernelGGL((roi_pool_bwd_kernel<h16_t>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (const h16_t*)dy, argmax);
+    else
+      hipLaunchKernelGGL((roi_pool_bwd_kernel<float>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (const float*)dy, argmax);
+    return utv2_launch_status();
+  }
   if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<true, h16_t>), dim3(R * PH * PW), dim3(64), 0, stream, L, rois, roi_batch, roi_valid, C, PH,
-                       PW, (h16_t*)dy);
+    hipLaunchKernelGGL((roi_align_kernel<true, h16_t>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)dy);
   else
-    hipLaunchKernelGGL((roi_align_kernel<true, float>), dim3(R * PH * PW), dim3(64), 0, stream, L, rois, roi_batch, roi_valid, C, PH,
-                       PW, (float*)dy);
+    hipLaunchKernelGGL((roi_align_kernel<true, float>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (float*)dy);
   return utv2_launch_status();
 }
 
-/* Deterministic gather form (see roi_align_bwd_tiled): the ROIs of image n are rois[n*rois_per_image .. (n+1)*rois_per_image), C <= 256,
- * PH, PW <= 7; every element of every dfeats[l] ([N][H_l][W_l][C], element type out_dtype) is WRITTEN (no zero-fill needed). */
-int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_host, const int* H_host, const int* W_host,
-                             const float* scales_host, const float* rois, const unsigned char* roi_valid, int N, int rois_per_image,
-                             int C, int PH, int PW, const void* dy, int dy_dtype, int out_dtype, hipStream_t stream) {
+/* Deterministic gather form (see roi_align_bwd_tiled / roi_pool_bwd_tiled): the ROIs of image n are
+ * rois[n*rois_per_image .. (n+1)*rois_per_image), C <= 256, PH, PW <= 7; every element of every dfeats[l] ([N][H_l][W_l][C], element
+ * type out_dtype) is WRITTEN (no zero-fill needed). */
+int utv2_roi_pooler_bwd_tiled(int pooler, int sampling_ratio, int num_levels, int min_level, void* const* dfeats_host, const int* H_host,
+                              const int* W_host, const float* scales_host, const float* rois, const unsigned char* roi_valid, int N,
+                              int rois_per_image, int C, int PH, int PW, const void* dy, const int* argmax, int dy_dtype, int out_dtype,
+                              hipStream_t stream) {
   if (num_levels < 1 || num_levels > 4 || !dfeats_host || !H_host || !W_host || !scales_host || !rois || !dy || (C & 3) || C > 256 ||
       PH < 1 || PH > 7 || PW < 1 || PW > 7 || N < 1 || rois_per_image < 1 || (dy_dtype != UTV2_F32 && dy_dtype != UTV2_BF16) ||
-      (out_dtype != UTV2_F32 && out_dtype != UTV2_BF16))
+      (out_dtype != UTV2_F32 && out_dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || (pooler == UTV2_POOLER_MAX && !argmax))
     return UTV2_EARG;
   RoiBwdArgs a;
   int blocks = 0;
@@ -1321,7 +1614,18 @@ int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_
   }
   a.tile_start[4] = blocks;
   a.num_levels = num_levels; a.min_level = min_level; a.N = N; a.P = rois_per_image; a.C = C; a.PH = PH; a.PW = PW;
+  a.aligned = pooler == UTV2_POOLER_ALIGN_V2; a.ratio = sampling_ratio;
   const dim3 g(blocks), b(256);
+  if (pooler == UTV2_POOLER_MAX) {
+    if (dy_dtype == UTV2_BF16) {
+      if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_pool_bwd_tiled<h16_t, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy, argmax);
+      else hipLaunchKernelGGL((roi_pool_bwd_tiled<h16_t, float>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy, argmax);
+    } else {
+      if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_pool_bwd_tiled<float, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy, argmax);
+      else hipLaunchKernelGGL((roi_pool_bwd_tiled<float, float>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy, argmax);
+    }
+    return utv2_launch_status();
+  }
   if (dy_dtype == UTV2_BF16) {
     if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_align_bwd_tiled<h16_t, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy);
     else hipLaunchKernelGGL((roi_align_bwd_tiled<h16_t, float>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy);
@@ -1330,6 +1634,28 @@ int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_
     else hipLaunchKernelGGL((roi_align_bwd_tiled<float, float>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy);
   }
   return utv2_launch_status();
+}
+
+// the shipped configs' pooler: RoIAlign, aligned, adaptive sampling grid
+int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_host, const int* H_host, const int* W_host,
+                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
+                       int R, int C, int PH, int PW, void* out, int dtype, hipStream_t stream) {
+  return utv2_roi_pooler_fwd(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, feats_host, H_host, W_host, scales_host, rois, roi_batch,
+                             roi_valid, R, C, PH, PW, out, nullptr, dtype, stream);
+}
+
+int utv2_roi_align_bwd(int num_levels, int min_level, float* const* dfeats_host, const int* H_host, const int* W_host,
+                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
+                       int R, int C, int PH, int PW, const void* dy, int dtype, hipStream_t stream) {
+  return utv2_roi_pooler_bwd(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, dfeats_host, H_host, W_host, scales_host, rois, roi_batch,
+                             roi_valid, R, C, PH, PW, dy, nullptr, dtype, stream);
+}
+
+int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_host, const int* H_host, const int* W_host,
+                             const float* scales_host, const float* rois, const unsigned char* roi_valid, int N, int rois_per_image,
+                             int C, int PH, int PW, const void* dy, int dy_dtype, int out_dtype, hipStream_t stream) {
+  return utv2_roi_pooler_bwd_tiled(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, dfeats_host, H_host, W_host, scales_host, rois,
+                                   roi_valid, N, rois_per_image, C, PH, PW, dy, nullptr, dy_dtype, out_dtype, stream);
 }
 
 // The scalar tail of the Faster-RCNN UTv2 losses in ONE launch (the FCOS counterpart is utv2_fcos_loss_combine): raw kernel sums of the

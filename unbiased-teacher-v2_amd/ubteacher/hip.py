@@ -753,29 +753,49 @@ def _ptr_array(tensors):
     return arr
 
 
-def roi_align_fwd(feats, scales, min_level, rois, roi_batch, roi_valid, out_size):
-    """feats: list of NHWC level tensors; rois [R,4]; roi_batch [R] int32 -> [R, PH, PW, C]."""
+POOLERS = {"ROIAlignV2": 0, "ROIAlign": 1, "ROIPool": 2}   # MODEL.ROI_BOX_HEAD.POOLER_TYPE -> UTV2_POOLER_* (include/utv2.h)
+
+
+def _pooler(pooler, sampling_ratio):
+    if pooler not in POOLERS:
+        raise NotImplementedError("ROI pooler %r: one of %s" % (pooler, sorted(POOLERS)))
+    if int(sampling_ratio) != sampling_ratio or sampling_ratio < 0:
+        raise ValueError("ROI pooler sampling ratio must be an integer >= 0, got %r" % (sampling_ratio,))
+    return POOLERS[pooler], int(sampling_ratio)
+
+
+def roi_align_fwd(feats, scales, min_level, rois, roi_batch, roi_valid, out_size, pooler="ROIAlignV2", sampling_ratio=0):
+    """feats: list of NHWC level tensors; rois [R,4]; roi_batch [R] int32 -> [R, PH, PW, C]; pooler "ROIPool": -> (output, argmax
+    [R, PH, PW, C] int32, the backward's input)."""
+    mode, ratio = _pooler(pooler, sampling_ratio)
     R = rois.shape[0]
     C = feats[0].shape[-1]
     out = torch.empty((R, out_size, out_size, C), dtype=feats[0].dtype, device=rois.device)
+    argmax = torch.empty((R, out_size, out_size, C), dtype=torch.int32, device=rois.device) if mode == 2 else None
     fp = _ptr_array(feats)
     H = _iarr([f.shape[1] for f in feats]); W = _iarr([f.shape[2] for f in feats]); S = _farr(scales)
-    call("utv2_roi_align_fwd", len(feats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p), ctypes.cast(W, c_p),
-         ctypes.cast(S, c_p), _p(rois), _p(roi_batch), _p(roi_valid), R, C, out_size, out_size, _p(out), _same_dt(*feats), _stream())
-    return out
+    call("utv2_roi_pooler_fwd", mode, ratio, len(feats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p), ctypes.cast(W, c_p),
+         ctypes.cast(S, c_p), _p(rois), _p(roi_batch), _p(roi_valid), R, C, out_size, out_size, _p(out), _p(argmax), _same_dt(*feats),
+         _stream())
+    return out if argmax is None else (out, argmax)
 
 
-def roi_align_bwd(dfeats, scales, min_level, rois, roi_batch, roi_valid, dy):
+def roi_align_bwd(dfeats, scales, min_level, rois, roi_batch, roi_valid, dy, pooler="ROIAlignV2", sampling_ratio=0, argmax=None):
+    mode, ratio = _pooler(pooler, sampling_ratio)
+    assert (argmax is not None and argmax.shape == dy.shape and argmax.dtype == torch.int32) if mode == 2 else argmax is None
     R, PH, PW, C = dy.shape
     fp = _ptr_array(dfeats)
     H = _iarr([f.shape[1] for f in dfeats]); W = _iarr([f.shape[2] for f in dfeats]); S = _farr(scales)
-    call("utv2_roi_align_bwd", len(dfeats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p), ctypes.cast(W, c_p),
-         ctypes.cast(S, c_p), _p(rois), _p(roi_batch), _p(roi_valid), R, C, PH, PW, _p(dy), _dt(dy), _stream())
+    call("utv2_roi_pooler_bwd", mode, ratio, len(dfeats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p), ctypes.cast(W, c_p),
+         ctypes.cast(S, c_p), _p(rois), _p(roi_batch), _p(roi_valid), R, C, PH, PW, _p(dy), _p(argmax), _dt(dy), _stream())
 
 
-def roi_align_bwd_tiled(shapes, out_dtype, scales, min_level, rois, roi_valid, dy, rois_per_image, outs=None):
+def roi_align_bwd_tiled(shapes, out_dtype, scales, min_level, rois, roi_valid, dy, rois_per_image, outs=None, pooler="ROIAlignV2",
+                        sampling_ratio=0, argmax=None):
     """deterministic gather form: returns the per-level gradient maps (every element written by the kernel); outs: preallocated
     contiguous destinations of these shapes / dtype (e.g. the levels' row ranges of one level-first buffer)"""
+    mode, ratio = _pooler(pooler, sampling_ratio)
+    assert (argmax is not None and argmax.shape == dy.shape and argmax.dtype == torch.int32) if mode == 2 else argmax is None
     R, PH, PW, C = dy.shape
     N = shapes[0][0]
     assert R == N * rois_per_image
@@ -786,8 +806,9 @@ def roi_align_bwd_tiled(shapes, out_dtype, scales, min_level, rois, roi_valid, d
         assert all(tuple(d.shape) == tuple(s) and d.dtype == out_dtype and d.is_contiguous() for d, s in zip(dfeats, shapes))
     fp = _ptr_array(dfeats)
     H = _iarr([s[1] for s in shapes]); W = _iarr([s[2] for s in shapes]); S = _farr(scales)
-    call("utv2_roi_align_bwd_tiled", len(dfeats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p), ctypes.cast(W, c_p),
-         ctypes.cast(S, c_p), _p(rois), _p(roi_valid), N, rois_per_image, C, PH, PW, _p(dy), _dt(dy), _dt(dfeats[0]), _stream())
+    call("utv2_roi_pooler_bwd_tiled", mode, ratio, len(dfeats), min_level, ctypes.cast(fp, c_p), ctypes.cast(H, c_p),
+         ctypes.cast(W, c_p), ctypes.cast(S, c_p), _p(rois), _p(roi_valid), N, rois_per_image, C, PH, PW, _p(dy), _p(argmax), _dt(dy),
+         _dt(dfeats[0]), _stream())
     return dfeats
 
 

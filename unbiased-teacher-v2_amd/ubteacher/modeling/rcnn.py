@@ -717,7 +717,15 @@ class StandardROIHeadsPseudoLab:
         self.scales = [1.0 / (2 ** int(f[1:])) for f in self.in_features]
         self.min_level = int(self.in_features[0][1:])
         self.res = bh.POOLER_RESOLUTION
-        assert bh.POOLER_TYPE == "ROIAlignV2" and bh.POOLER_SAMPLING_RATIO == 0 and bh.NUM_CONV == 0
+        # D2 ROIPooler's types minus the rotated one; only the two RoIAlign types read the sampling ratio (0 = adaptive grid)
+        if bh.POOLER_TYPE not in hip.POOLERS:
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.POOLER_TYPE %r is not built: one of %s" % (bh.POOLER_TYPE, sorted(hip.POOLERS)))
+        if not isinstance(bh.POOLER_SAMPLING_RATIO, int) or bh.POOLER_SAMPLING_RATIO < 0:
+            raise ValueError("MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO must be an integer >= 0, got %r" % (bh.POOLER_SAMPLING_RATIO,))
+        if bh.NUM_CONV != 0:
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.NUM_CONV %r: the conv layers of FastRCNNConvFCHead are not built, only NUM_CONV 0 "
+                                      "(fully connected layers on the pooled features)" % (bh.NUM_CONV,))
+        self.pooler_type, self.sampling_ratio = bh.POOLER_TYPE, bh.POOLER_SAMPLING_RATIO
         self.num_classes = rh.NUM_CLASSES
         self.batch_size_per_image = rh.BATCH_SIZE_PER_IMAGE
         self.positive_fraction = rh.POSITIVE_FRACTION
@@ -805,7 +813,7 @@ class StandardROIHeadsPseudoLab:
         rois = boxes.reshape(-1, 4).contiguous()
         batch = torch.arange(N, device=rois.device, dtype=torch.int32)[:, None].expand(N, P).reshape(-1).contiguous()
         x = ops.roi_align(feats, self.scales, self.min_level, rois, batch, valid.reshape(-1).contiguous(), self.res, rois_per_image=P,
-                          fanin=fanin)
+                          fanin=fanin, pooler=self.pooler_type, sampling_ratio=self.sampling_ratio)
         x = x.view(x.shape[0], 1, 1, -1)
         for fc in self.fcs:
             x = fc(x)

@@ -1377,18 +1377,25 @@ def assemble(big, rows, levels):
 class _RoIAlignFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rois, roi_batch, roi_valid, cfg, *feats):
-        scales, min_level, out_size, per_image, fanin = cfg
+        scales, min_level, out_size, per_image, fanin, pooler, ratio = cfg
         ctx.cfg = cfg[:3]
+        ctx.mode = dict(pooler=pooler, sampling_ratio=ratio)
         ctx.per_image = per_image
         ctx.fanin = fanin
         ctx.shapes = [tuple(f.shape) for f in feats]
         ctx.fdtype = feats[0].dtype
-        ctx.save_for_backward(rois, roi_batch, roi_valid)
-        return hip.roi_align_fwd([f.detach() for f in feats], scales, min_level, rois, roi_batch, roi_valid, out_size)
+        y = hip.roi_align_fwd([f.detach() for f in feats], scales, min_level, rois, roi_batch, roi_valid, out_size, **ctx.mode)
+        if pooler == "ROIPool":      # the gradient of each output element goes to the pixel its argmax names
+            y, argmax = y
+            ctx.save_for_backward(rois, roi_batch, roi_valid, argmax)
+        else:
+            ctx.save_for_backward(rois, roi_batch, roi_valid)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
-        rois, roi_batch, roi_valid = ctx.saved_tensors
+        rois, roi_batch, roi_valid = ctx.saved_tensors[:3]
+        mode = dict(ctx.mode, argmax=ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None)
         scales, min_level, out_size = ctx.cfg
         N, C = ctx.shapes[0][0], ctx.shapes[0][3]
         R = rois.shape[0]
@@ -1397,25 +1404,31 @@ class _RoIAlignFn(torch.autograd.Function):
             st = ctx.fanin.store(C, ctx.fdtype, dy.device) if (ctx.fanin is not None and ctx.fdtype == hip.h16_dtype()) else None
             if st is not None and [tuple(o.shape) for o in st[1]] == [tuple(x) for x in ctx.shapes]:
                 # the RPN conv's dgrad adds these level gradients in its epilogue (FanIn): no gradient reported from here
-                hip.roi_align_bwd_tiled(ctx.shapes, ctx.fdtype, scales, min_level, rois, roi_valid, dy.contiguous(), ctx.per_image, outs=st[1])
+                hip.roi_align_bwd_tiled(ctx.shapes, ctx.fdtype, scales, min_level, rois, roi_valid, dy.contiguous(), ctx.per_image, outs=st[1],
+                                        **mode)
                 return (None, None, None, None) + (None,) * len(ctx.shapes)
             if st is not None:
                 ctx.fanin.take(); ctx.fanin.closed = False
-            dfeats = hip.roi_align_bwd_tiled(ctx.shapes, ctx.fdtype, scales, min_level, rois, roi_valid, dy.contiguous(), ctx.per_image)
+            dfeats = hip.roi_align_bwd_tiled(ctx.shapes, ctx.fdtype, scales, min_level, rois, roi_valid, dy.contiguous(), ctx.per_image, **mode)
             return (None, None, None, None) + tuple(dfeats)
         dfeats = [torch.zeros(s, dtype=torch.float32, device=dy.device) for s in ctx.shapes]   # fp32: atomics
-        hip.roi_align_bwd(dfeats, scales, min_level, rois, roi_batch, roi_valid, dy.contiguous())
+        hip.roi_align_bwd(dfeats, scales, min_level, rois, roi_batch, roi_valid, dy.contiguous(), **mode)
         if ctx.fdtype != torch.float32:
             dfeats = [d.to(ctx.fdtype) for d in dfeats]
         return (None, None, None, None) + tuple(dfeats)
 
 
-def roi_align(feats, scales, min_level, rois, roi_batch, roi_valid, out_size, rois_per_image=0, fanin=None):
-    """rois_per_image > 0: the caller guarantees roi_batch == repeat_interleave(arange(N), rois_per_image) (the backward then runs as
+def roi_align(feats, scales, min_level, rois, roi_batch, roi_valid, out_size, rois_per_image=0, fanin=None, pooler="ROIAlignV2",
+              sampling_ratio=0):
+    """The ROI pooler.  pooler: MODEL.ROI_BOX_HEAD.POOLER_TYPE - "ROIAlignV2" (RoIAlign, aligned), "ROIAlign" (not aligned) or "ROIPool"
+    (maximum per bin); sampling_ratio: RoIAlign's samples per bin and axis, 0 = adaptive (ROIPool does not read it).
+    rois_per_image > 0: the caller guarantees roi_batch == repeat_interleave(arange(N), rois_per_image) (the backward then runs as
     the deterministic tiled gather instead of the atomic scatter); fanin: see FanIn"""
     if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
-        return _RoIAlignFn.apply(rois, roi_batch, roi_valid, (tuple(scales), min_level, out_size, int(rois_per_image), fanin), *feats)
-    return hip.roi_align_fwd(list(feats), scales, min_level, rois, roi_batch, roi_valid, out_size)
+        return _RoIAlignFn.apply(rois, roi_batch, roi_valid,
+                                 (tuple(scales), min_level, out_size, int(rois_per_image), fanin, pooler, int(sampling_ratio)), *feats)
+    y = hip.roi_align_fwd(list(feats), scales, min_level, rois, roi_batch, roi_valid, out_size, pooler=pooler, sampling_ratio=sampling_ratio)
+    return y[0] if pooler == "ROIPool" else y
 
 
 class _SoftmaxFocalFn(torch.autograd.Function):
