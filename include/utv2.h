@@ -422,22 +422,6 @@ int utv2_roi_pooler_bwd_tiled(int pooler, int sampling_ratio, int num_levels, in
                               const int* H_host, const int* W_host, const float* scales_host, const float* rois,
                               const unsigned char* roi_valid, int N, int rois_per_image, int C, int PH, int PW, const void* dy,
                               const int* argmax, int dy_dtype, int out_dtype, utv2_stream_t stream);
-/* the same three entry points at (UTV2_POOLER_ALIGN_V2, 0), the shipped configs' pooler:
- * torchvision roi_align(aligned=True, sampling_ratio=0) */
-int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_host, const int* H_host,
-                       const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
-                       const unsigned char* roi_valid, int R, int C, int PH, int PW, void* out, int dtype,
-                       utv2_stream_t stream);
-/* features / out / dy are `dtype` (UTV2_F32 / UTV2_BF16); the gradient buffers dfeats stay fp32 (atomics) */
-int utv2_roi_align_bwd(int num_levels, int min_level, float* const* dfeats_host, const int* H_host, const int* W_host,
-                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
-                       int R, int C, int PH, int PW, const void* dy, int dtype, utv2_stream_t stream);
-/* the same gradient as a deterministic gather over 8 x 8 pixel tiles (no atomics; the backward of the ROIPooler call at
- * roi_heads/roi_heads.py:118): the ROIs of image n are rois[n*rois_per_image .. (n+1)*rois_per_image), C <= 256, PH, PW <= 7;
- * every element of every dfeats[l] ([N][H_l][W_l][C], element type out_dtype) is written - no zero-fill, no fp32 staging */
-int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_host, const int* H_host, const int* W_host,
-                             const float* scales_host, const float* rois, const unsigned char* roi_valid, int N, int rois_per_image,
-                             int C, int PH, int PW, const void* dy, int dy_dtype, int out_dtype, utv2_stream_t stream);
 /* RPN proposal decoding, the part of detectron2's RPN.predict_proposals / find_top_rpn_proposals in front of the NMS that
  * proposal_generator/rpn.py:60-76 inherits.  head: level-first RPN head output, rows (level, image, pixel) x ch floats = A objectness
  * logits then 4A anchor-major deltas; hw_host[l] = pixels of level l.

@@ -323,11 +323,13 @@ def test_roi_align_bf16_io():
 
 
 def test_roi_align_fwd_per_roi_kernel_matches_per_bin_kernel(tmp_path):
-    """utv2_roi_align_fwd runs one workgroup per ROI (tap tables built once per ROI in LDS, 16-byte loads); UTV2_ROI_FWD_PER_ROI=0 keeps
-    the one-wave-per-(roi, bin) kernel: the same formula tap for tap - the compiler contracts the sample coordinate `start + k * bin`
-    into an FMA in one and not in the other, so the outputs agree to the last bits, not always bit for bit: <= 1e-6 of the tensor's scale in
-    fp32, <= one 16-bit rounding step in 16-bit, on ROIs of every level incl. clipped / out-of-image / degenerate / invalid ones (the
-    switch is read once per process: subprocess).  Both are checked against the oracle by test_roi_align_fwd_bwd_vs_oracle."""
+    """utv2_roi_pooler_fwd runs one workgroup per ROI (tap tables built once per ROI in LDS, 16-byte loads); UTV2_ROI_FWD_PER_ROI=0 keeps
+    the one-wave-per-(roi, bin) kernel: the same formula tap for tap (the library is built without FMA contraction), but a ROI with one
+    bin too wide for the tap tables goes sample by sample as a whole in the first and bin by bin in the second, and the tables add in
+    another order than the samples do - these boxes reach 1100 pixels - so the outputs agree to the last bits, not always bit for bit
+    (measured on an MI355X: 3.0e-7 in fp32): <= 1e-6 of the tensor's scale in fp32, <= one 16-bit rounding step in 16-bit, on ROIs of
+    every level incl. clipped / out-of-image / degenerate / invalid ones (the switch is read once per process: subprocess).  Both are
+    checked against the oracle by test_roi_align_fwd_bwd_vs_oracle."""
     import os
     import subprocess
     import sys
@@ -460,7 +462,7 @@ def test_rpn_fused_decode_equals_elementwise_chain():
 
 
 def test_roi_align_bwd_tiled_gather_equals_scatter_and_is_deterministic():
-    """utv2_roi_align_bwd_tiled (the deterministic gather over 8 x 8 pixel tiles the ROI heads' backward runs) against the atomic
+    """utv2_roi_pooler_bwd_tiled (the deterministic gather over 8 x 8 pixel tiles the ROI heads' backward runs) against the atomic
     scatter kernel and, through autograd, against the oracle: ROIs image by image (P slots each, some invalid), boxes that stick out of
     the image, elongated boxes with many samples per bin, all four levels; bit-identical between runs; bf16 in / out forms."""
     from ubteacher import hip, ops

@@ -260,6 +260,110 @@ def test_tiled_gather_equals_scatter_and_is_deterministic(mode, C, P):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# bins wider than the tap table: the sample-by-sample path of the forward kernels and of the atomic scatter
+ROI_MAXT = 18                                           # csrc/rcnn.hip: taps per axis the table path keeps
+LONG_SLOTS = 6
+LONG_MODES = [("ROIAlignV2", 0), ("ROIAlign", 0), ("ROIAlignV2", 2)]
+LONG_C = 16
+
+
+@functools.lru_cache(maxsize=None)
+def make_long_case():
+    """features NCHW fp32 on the CPU, long thin boxes of the finest level (and one ordinary box, one invalid slot) image by image,
+    image index, valid flags, a dy for resolution 7"""
+    g = torch.Generator().manual_seed(177)
+    feats = [torch.randn(N, LONG_C, h, w, generator=g) for h, w in SHAPES]
+    boxes = [
+        [40.0, 0.0, 46.0, 520.0],         # bins of 18.6 rows at resolution 7
+        [40.0, 0.0, 46.0, 600.0],         # of 18.75 rows at resolution 8
+        [0.0, 40.0, 1000.0, 46.0],        # at sampling ratio 2 the two samples of a bin lie about 18 columns apart
+        [0.0, 40.0, 1100.0, 46.0],        # about 20 (resolution 7) and 17 (resolution 8) columns apart
+        [20.0, 10.0, 90.0, 70.0],         # an ordinary box: the table path next to the others
+        [10.0, 0.0, 16.0, 560.0],         # the invalid slot
+    ]
+    rois = torch.cat([torch.tensor(boxes), torch.tensor(boxes) + torch.tensor([3.25, 1.5, 3.25, 1.5])])
+    valid = torch.ones(N * LONG_SLOTS, dtype=torch.uint8)
+    valid[LONG_SLOTS - 1] = valid[2 * LONG_SLOTS - 1] = 0
+    batch = torch.arange(N, dtype=torch.int32).repeat_interleave(LONG_SLOTS)
+    dy = torch.randn(N * LONG_SLOTS, LONG_C, 7, 7, generator=g)
+    return feats, rois, batch, valid, dy
+
+
+@functools.lru_cache(maxsize=None)
+def long_reference(mode, P):
+    """the fp64 restatement's output of the long-box case and, at resolution 7, its level gradients; computed once"""
+    feats, rois, batch, valid, dy = make_long_case()
+    fr = [f.double().clone().requires_grad_(P == 7) for f in feats]
+    y = R64.roi_pooler(fr, rois, batch, P, mode[0], mode[1], SCALES, 2, valid)
+    if P != 7:
+        return y.detach(), None
+    y.backward(dy.double())
+    return y.detach(), [f.grad if f.grad is not None else torch.zeros_like(f) for f in fr]
+
+
+def widest_bin_span(rois, valid, mode, P):
+    """per ROI the largest number of pixel rows or columns of its level that the counted samples of one of its bins put weight on
+    (0: none, or an invalid slot) - the restatement's geometry and tap rule in fp64"""
+    lv = R64.assign_levels(rois)
+    off = 0.5 if mode[0] == "ROIAlignV2" else 0.0
+    spans = []
+    for r in range(rois.shape[0]):
+        best = 0
+        if bool(valid[r]):
+            (h, w), sc = SHAPES[int(lv[r])], SCALES[int(lv[r])]
+            b = rois[r].double() * sc - off
+            for lo, hi, size in ((b[1], b[3], h), (b[0], b[2], w)):
+                side = float(hi - lo) if off else max(float(hi - lo), 1.0)
+                g = mode[1] if mode[1] > 0 else int(np.ceil(side / P))
+                for p in range(P if g > 0 else 0):
+                    v = lo + p * side / P + (torch.arange(g, dtype=torch.float64) + 0.5) * (side / P) / g
+                    ok, lo_px, hi_px, _ = R64._axis(v, size)
+                    if bool(ok.any()):
+                        best = max(best, int(hi_px[ok].max() - lo_px[ok].min()) + 1)
+        spans.append(best)
+    return spans
+
+
+@pytest.mark.parametrize("P", [7, 8])
+@pytest.mark.parametrize("mode", LONG_MODES, ids=mode_id)
+def test_long_case_has_bins_wider_than_the_tap_table(mode, P):
+    """no GPU needed: in every mode and at both resolutions a valid ROI of the long-box case has a bin whose samples touch more than
+    ROI_MAXT pixels of an axis (the kernels then leave the table path), and the ordinary box has none"""
+    _, rois, _, valid, _ = make_long_case()
+    spans = widest_bin_span(rois, valid, mode, P)
+    print("widest bin per ROI, %s at resolution %d: %s" % (mode_id(mode), P, spans))
+    assert max(spans) > ROI_MAXT
+    assert 0 < spans[4] <= ROI_MAXT and spans[LONG_SLOTS - 1] == 0
+    assert set(R64.assign_levels(rois[:4]).tolist()) == {0}
+
+
+@pytest.mark.parametrize("mode", LONG_MODES, ids=mode_id)
+def test_bins_wider_than_the_tap_table_vs_fp64_restatement(mode):
+    """Bins of more than ROI_MAXT pixels take the sample-by-sample path: the per-ROI forward's fall-back at resolution 7, the
+    per-(roi, bin) forward at resolution 8 (the per-ROI kernel stops at 7), the atomic scatter at 7; the tiled gather sums sample by
+    sample at any bin size.  Bounds of test_fwd_bwd_vs_fp64_restatement: output rtol 1e-4 / atol 1e-5, gradients rtol 1e-3 / atol 1e-5."""
+    from ubteacher import hip
+    feats, rois, batch, valid, dy = make_long_case()
+    for P in (7, 8):
+        assert max(widest_bin_span(rois, valid, mode, P)) > ROI_MAXT
+    kw = dict(pooler=mode[0], sampling_ratio=mode[1])
+    r, b, v = rois.to(DEV), batch.to(DEV), valid.to(DEV)
+    for P in (7, 8):
+        y = hip.roi_align_fwd(nhwc(feats), SCALES, 2, r, b, v, P, **kw)
+        close(y.permute(0, 3, 1, 2), long_reference(mode, P)[0], rtol=1e-4, atol=1e-5)
+        assert float(y[LONG_SLOTS - 1].abs().max()) == 0 and float(y[0].abs().max()) > 0
+    ref_g = long_reference(mode, 7)[1]
+    shapes = [(N, h, w, LONG_C) for h, w in SHAPES]
+    dyh = dy.permute(0, 2, 3, 1).contiguous().to(DEV)
+    scat = [torch.zeros(s, device=DEV) for s in shapes]
+    hip.roi_align_bwd(scat, SCALES, 2, r, b, v, dyh, **kw)
+    for got in (hip.roi_align_bwd_tiled(shapes, torch.float32, SCALES, 2, r, v, dyh, LONG_SLOTS, **kw), scat):
+        for a, g in zip(got, ref_g):
+            close(a.permute(0, 3, 1, 2), g, rtol=1e-3, atol=1e-5)
+    assert float(ref_g[0].abs().max()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # whole steps
 H, W = 96, 128
 STEP_MODES = [("ROIAlign", 2), ("ROIPool", 0)]

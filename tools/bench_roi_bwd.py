@@ -1,4 +1,4 @@
-"""RoIAlign backward (utv2_roi_align_bwd_tiled) at the Faster-RCNN step's size: N images x 512 sampled ROIs, 256 channels, 7 x 7 bins, p2-p5 of
+"""RoIAlign backward (utv2_roi_pooler_bwd_tiled) at the Faster-RCNN step's size: N images x 512 sampled ROIs, 256 channels, 7 x 7 bins, p2-p5 of
 an 800 x 1344 canvas, 16-bit gradients.  Prints the time per launch and a checksum of the maps (two builds / two runs must agree exactly).
 usage: python tools/bench_roi_bwd.py [N=12]"""
 import os, sys, hashlib

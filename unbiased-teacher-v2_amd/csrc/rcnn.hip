@@ -140,11 +140,30 @@ __device__ __forceinline__ RoiGeom roi_geom(const float4& b, float sc, int PH, i
   return g;
 }
 
-__device__ __forceinline__ int roi_level(const float4& b, const RoiLevels& L) {
+__device__ __forceinline__ int roi_level(const float4& b, int min_level, int num_levels) {
   const float area = (b.z - b.x) * (b.w - b.y);
   int lvl = (int)floorf(4.f + log2f(sqrtf(area) / 224.f + 1e-8f));
-  lvl = min(max(lvl, L.min_level), L.min_level + L.num_levels - 1);
-  return lvl - L.min_level;
+  lvl = min(max(lvl, min_level), min_level + num_levels - 1);
+  return lvl - min_level;
+}
+
+// The bilinear sample rule of one axis (torchvision's): a sample outside [-1, size] does not count; a counted one is clamped at 0, and
+// from pixel size - 1 on both its taps are that pixel with fraction 0.  Weight 1 - fr on pixel l, fr on pixel h.
+struct AxisSample {
+  bool ok;
+  int l, h;
+  float fr;
+};
+
+__device__ __forceinline__ AxisSample axis_sample(float v, int size) {
+  AxisSample s = {false, 0, 0, 0.f};
+  if (v < -1.f || v > (float)size) return s;
+  s.ok = true;
+  if (v <= 0.f) v = 0.f;
+  s.l = (int)v;
+  if (s.l >= size - 1) { s.h = s.l = size - 1; v = (float)s.l; } else s.h = s.l + 1;
+  s.fr = v - (float)s.l;
+  return s;
 }
 
 // The gh x gw bilinear samples of a bin are SEPARABLE: sample (iy, ix) puts weight wy(iy, Y) * wx(ix, X) on pixel (Y, X) and is
@@ -166,14 +185,10 @@ __device__ __forceinline__ bool axis_taps(float start, float bin, int g, int siz
   // accumulate the weights of the g samples of one axis onto pixel indices; returns false if they do not fit
   int lo = 1 << 30, hi = -1;
   for (int i = 0; i < g; ++i) {
-    float v = start + ((float)i + 0.5f) * bin / (float)g;
-    if (v < -1.f || v > (float)size) continue;
-    if (v <= 0.f) v = 0.f;
-    int l = (int)v;
-    if (l >= size - 1) l = size - 1;
-    const int h = l >= size - 1 ? l : l + 1;
-    lo = min(lo, l);
-    hi = max(hi, h);
+    const AxisSample s = axis_sample(start + ((float)i + 0.5f) * bin / (float)g, size);
+    if (!s.ok) continue;
+    lo = min(lo, s.l);
+    hi = max(hi, s.h);
   }
   t.lo = lo;
   t.n = hi >= lo ? hi - lo + 1 : 0;
@@ -181,19 +196,58 @@ __device__ __forceinline__ bool axis_taps(float start, float bin, int g, int siz
 #pragma unroll
   for (int k = 0; k < ROI_MAXT; ++k) t.w[k] = 0.f;
   for (int i = 0; i < g; ++i) {
-    float v = start + ((float)i + 0.5f) * bin / (float)g;
-    if (v < -1.f || v > (float)size) continue;
-    if (v <= 0.f) v = 0.f;
-    int l = (int)v, h;
-    if (l >= size - 1) { h = l = size - 1; v = (float)l; } else h = l + 1;
-    const float fr = v - (float)l;
+    const AxisSample s = axis_sample(start + ((float)i + 0.5f) * bin / (float)g, size);
+    if (!s.ok) continue;
 #pragma unroll
     for (int k = 0; k < ROI_MAXT; ++k) {   // register array: no dynamic indexing
-      if (k == l - lo) t.w[k] += 1.f - fr;
-      if (k == h - lo) t.w[k] += fr;
+      if (k == s.l - lo) t.w[k] += 1.f - s.fr;
+      if (k == s.h - lo) t.w[k] += s.fr;
     }
   }
   return true;
+}
+
+// A bin whose samples do not fit the tap tables: every sample of bin (ph, pw), four taps each, for channels 4c .. 4c + 3.
+// o: the bin's row of the output (forward: written) or of dy (BWD: read, and scattered into df with fp32 atomics).
+template <bool BWD, typename T>
+__device__ __forceinline__ void roi_bin_by_sample(const RoiGeom& q, int ph, int pw, int H, int W, int C4, int c, const T* f, float* df,
+                                                  T* o) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+  if (BWD) {
+    g = ld4((const T*)o, c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] /= q.cnt;
+  }
+  for (int iy = 0; iy < q.gh; ++iy) {
+    const AxisSample sy = axis_sample(q.y1 + ph * q.bh + ((float)iy + 0.5f) * q.bh / (float)q.gh, H);
+    for (int ix = 0; ix < q.gw; ++ix) {
+      const AxisSample sx = axis_sample(q.x1 + pw * q.bw + ((float)ix + 0.5f) * q.bw / (float)q.gw, W);
+      if (!sy.ok || !sx.ok) continue;
+      const float ly = sy.fr, lx = sx.fr, hy = 1.f - ly, hx = 1.f - lx;
+      const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+      const size_t o1 = ((size_t)sy.l * W + sx.l) * C4 + c, o2 = ((size_t)sy.l * W + sx.h) * C4 + c;
+      const size_t o3 = ((size_t)sy.h * W + sx.l) * C4 + c, o4 = ((size_t)sy.h * W + sx.h) * C4 + c;
+      if (!BWD) {
+        const f32x4 v1 = ld4(f, o1), v2 = ld4(f, o2), v3 = ld4(f, o3), v4 = ld4(f, o4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += w1 * v1[e] + w2 * v2[e] + w3 * v3[e] + w4 * v4[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          atomicAdd(df + o1 * 4 + e, g[e] * w1);
+          atomicAdd(df + o2 * 4 + e, g[e] * w2);
+          atomicAdd(df + o3 * 4 + e, g[e] * w3);
+          atomicAdd(df + o4 * 4 + e, g[e] * w4);
+        }
+      }
+    }
+  }
+  if (!BWD) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] /= q.cnt;
+    st4(o, c, acc);
+  }
 }
 
 template <bool BWD, typename T>
@@ -213,7 +267,7 @@ __global__ __launch_bounds__(64) void roi_align_kernel(RoiLevels L, const float*
     return;
   }
   const float4 b = ((const float4*)rois)[r];
-  const int li = roi_level(b, L);
+  const int li = roi_level(b, L.min_level, L.num_levels);
   const int H = L.H[li], W = L.W[li];
   const float sc = L.scale[li];
   const RoiGeom q = roi_geom(b, sc, PH, PW, L.aligned, L.ratio);
@@ -265,51 +319,7 @@ __global__ __launch_bounds__(64) void roi_align_kernel(RoiLevels L, const float*
     }
     return;
   }
-  // generic path: every sample, four taps each
-  for (int c = threadIdx.x; c < C4; c += 64) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    f32x4 g = {0.f, 0.f, 0.f, 0.f};
-    if (BWD) {
-      g = ld4((const T*)o, c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] /= cnt;
-    }
-    for (int iy = 0; iy < gh; ++iy) {
-      float y = y1 + ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        float x = x1 + pw * bw + ((float)ix + 0.5f) * bw / (float)gw;
-        float yy = y;
-        if (yy < -1.f || yy > (float)H || x < -1.f || x > (float)W) continue;
-        if (yy <= 0.f) yy = 0.f;
-        if (x <= 0.f) x = 0.f;
-        int yl = (int)yy, xl = (int)x, yh, xh;
-        if (yl >= H - 1) { yh = yl = H - 1; yy = (float)yl; } else yh = yl + 1;
-        if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else xh = xl + 1;
-        const float ly = yy - (float)yl, lx = x - (float)xl, hy = 1.f - ly, hx = 1.f - lx;
-        const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-        const size_t o1 = ((size_t)yl * W + xl) * C4 + c, o2 = ((size_t)yl * W + xh) * C4 + c;
-        const size_t o3 = ((size_t)yh * W + xl) * C4 + c, o4 = ((size_t)yh * W + xh) * C4 + c;
-        if (!BWD) {
-          const f32x4 v1 = ld4(f, o1), v2 = ld4(f, o2), v3 = ld4(f, o3), v4 = ld4(f, o4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[e] += w1 * v1[e] + w2 * v2[e] + w3 * v3[e] + w4 * v4[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            atomicAdd(df + o1 * 4 + e, g[e] * w1);
-            atomicAdd(df + o2 * 4 + e, g[e] * w2);
-            atomicAdd(df + o3 * 4 + e, g[e] * w3);
-            atomicAdd(df + o4 * 4 + e, g[e] * w4);
-          }
-        }
-      }
-    }
-    if (!BWD) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] /= cnt;
-      st4(o, c, acc);
-    }
-  }
+  for (int c = threadIdx.x; c < C4; c += 64) roi_bin_by_sample<BWD>(q, ph, pw, H, W, C4, c, f, df, o);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -317,8 +327,9 @@ __global__ __launch_bounds__(64) void roi_align_kernel(RoiLevels L, const float*
 // lane of it rebuilds both axes' tap tables in registers (18-entry arrays read through compare / select chains: the kernel was bound by
 // those, 470 us for 150 MB of output with nothing else in flight).  Here 14 threads build the 7 + 7 per-axis tables of the ROI ONCE into
 // LDS (same axis_taps), then each thread takes (bin, 16-byte channel group) items: <= 3 x 3 taps of one 16-byte load each for the ROI
-// sizes the level assignment produces.  Same per-channel arithmetic in the same order as roi_align_kernel (identical up to the FMA
-// contraction of the sample coordinates: tests/test_rcnn_kernels_gpu.py).
+// sizes the level assignment produces.  Same per-channel arithmetic in the same order as roi_align_kernel: the two agree bit for bit
+// (tests/test_roi_pooler_gpu.py), except on a ROI with a bin too wide for the tables, which goes sample by sample as a whole here and
+// bin by bin there (last-bit differences: the tables add in another order than the samples).
 template <typename T>
 __global__ __launch_bounds__(256) void roi_align_fwd_roi_kernel(RoiLevels L, const float* __restrict__ rois, const int* __restrict__ roi_batch,
                                                               const unsigned char* __restrict__ roi_valid, int C, int PH, int PW,
@@ -338,7 +349,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_roi_kernel(RoiLevels L, con
     return;
   }
   const float4 b = ((const float4*)rois)[r];
-  const int li = roi_level(b, L);
+  const int li = roi_level(b, L.min_level, L.num_levels);
   const int H = L.H[li], W = L.W[li];
   const float sc = L.scale[li];
   const RoiGeom q = roi_geom(b, sc, PH, PW, L.aligned, L.ratio);
@@ -401,34 +412,12 @@ __global__ __launch_bounds__(256) void roi_align_fwd_roi_kernel(RoiLevels L, con
     }
     return;
   }
-  // a bin wider than ROI_MAXT pixels (never with the D2 level assignment): every sample, four taps each - roi_align_kernel's generic path
+  // a bin wider than the tap table (never with the D2 level assignment)
   const int C4 = C >> 2;
   for (int it = tid; it < PH * PW * C4; it += 256) {
     const int bin = it / C4, c = it - bin * C4;
     const int ph = bin / PW, pw = bin - ph * PW;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int iy = 0; iy < gh; ++iy) {
-      const float y = y1 + ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        float x = x1 + pw * bw + ((float)ix + 0.5f) * bw / (float)gw;
-        float yy = y;
-        if (yy < -1.f || yy > (float)H || x < -1.f || x > (float)W) continue;
-        if (yy <= 0.f) yy = 0.f;
-        if (x <= 0.f) x = 0.f;
-        int yl = (int)yy, xl = (int)x, yh, xh;
-        if (yl >= H - 1) { yh = yl = H - 1; yy = (float)yl; } else yh = yl + 1;
-        if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else xh = xl + 1;
-        const float ly = yy - (float)yl, lx = x - (float)xl, hy = 1.f - ly, hx = 1.f - lx;
-        const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-        const f32x4 v1 = ld4(f, ((size_t)yl * W + xl) * C4 + c), v2 = ld4(f, ((size_t)yl * W + xh) * C4 + c);
-        const f32x4 v3 = ld4(f, ((size_t)yh * W + xl) * C4 + c), v4 = ld4(f, ((size_t)yh * W + xh) * C4 + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += w1 * v1[e] + w2 * v2[e] + w3 * v3[e] + w4 * v4[e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] /= cnt;
-    st4(o + (size_t)bin * C, c, acc);
+    roi_bin_by_sample<false>(q, ph, pw, H, W, C4, c, f, nullptr, o + (size_t)bin * C);
   }
 }
 
@@ -452,46 +441,94 @@ struct RoiBwdArgs {
   int aligned, ratio;   // RoIAlign mode (see RoiLevels)
 };
 
+// The tile walk both gathers (RoIAlign here, RoIPool further down) share.  All of it is inlined: acc stays in registers.
+struct RoiTile {
+  int li, n, H, W, ty0, tx0;   // level, image, map size, first row / column of the tile
+  float sc;
+};
+
+__device__ __forceinline__ RoiTile roi_tile(const RoiBwdArgs& a) {   // blockIdx.x -> (level, image, tile)
+  RoiTile t;
+  t.li = 0;
+#pragma unroll
+  for (int l = 1; l < 4; ++l)
+    if (l < a.num_levels && (int)blockIdx.x >= a.tile_start[l]) t.li = l;
+  t.H = a.H[t.li];
+  t.W = a.W[t.li];
+  const int tx_n = (t.W + RB_T - 1) / RB_T, ty_n = (t.H + RB_T - 1) / RB_T;
+  int b = blockIdx.x - a.tile_start[t.li];
+  t.n = b / (tx_n * ty_n);
+  b -= t.n * tx_n * ty_n;
+  t.ty0 = (b / tx_n) * RB_T;
+  t.tx0 = (b % tx_n) * RB_T;
+  t.sc = a.scale[t.li];
+  return t;
+}
+
+// thread `tid` holds ROI slot `slot` of a round of 256 and whether it touches the tile: list[0 .. total) receives the slots that do, in
+// ROI order (ballot per wave, prefix over the four waves); ends on a barrier, so list can be read at once.  The caller puts a barrier
+// between its last read of list and the next round.
+__device__ __forceinline__ int roi_tile_list(bool hit, int slot, int* list, int* wcount) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(hit);
+  if (lane == 0) wcount[wid] = __popcll(m);
+  __syncthreads();
+  int off = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (w < wid) off += wcount[w];
+    total += wcount[w];
+  }
+  if (hit) list[off + __popcll(m & ((1ull << lane) - 1ull))] = slot;
+  __syncthreads();
+  return total;
+}
+
+__device__ __forceinline__ void roi_tile_zero(f32x4 (&acc)[2][RB_T]) {
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int x = 0; x < RB_T; ++x) acc[r][x] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// the thread's 2 x 8 pixels x 4 channels (rows r0, r0 + 1) of the map `out`, rows / columns past the map left out
+template <typename TO>
+__device__ __forceinline__ void roi_tile_store(TO* out, int H, int W, int r0, int tx0, int C, const f32x4 (&acc)[2][RB_T]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int y = r0 + r;
+    if (y >= H) continue;
+#pragma unroll
+    for (int x = 0; x < RB_T; ++x) {
+      if (tx0 + x >= W) continue;
+      st4(out + ((size_t)y * W + tx0 + x) * C, lane, acc[r][x]);
+    }
+  }
+}
+
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const float* __restrict__ rois, const unsigned char* __restrict__ roi_valid,
                                                           const TI* __restrict__ dy) {
   __shared__ int list[256];
   __shared__ int wcount[4];
   __shared__ float wy[7 * RB_T], wx[7 * RB_T];   // PH, PW <= 7
-  __shared__ float geo[8];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int li = 0;
-#pragma unroll
-  for (int l = 1; l < 4; ++l)
-    if (l < a.num_levels && (int)blockIdx.x >= a.tile_start[l]) li = l;
-  const int H = a.H[li], W = a.W[li];
-  const int tx_n = (W + RB_T - 1) / RB_T, ty_n = (H + RB_T - 1) / RB_T;
-  int b = blockIdx.x - a.tile_start[li];
-  const int n = b / (tx_n * ty_n);
-  b -= n * tx_n * ty_n;
-  const int ty0 = (b / tx_n) * RB_T, tx0 = (b % tx_n) * RB_T;
-  const float sc = a.scale[li];
-  const int C4 = a.C >> 2;
-  const bool cok = lane < C4;
-
+  const RoiTile t = roi_tile(a);
+  const int li = t.li, n = t.n, H = t.H, W = t.W, ty0 = t.ty0, tx0 = t.tx0;
+  const float sc = t.sc;
+  const bool cok = lane < (a.C >> 2);
   f32x4 acc[2][RB_T];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int x = 0; x < RB_T; ++x) acc[r][x] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  RoiLevels LV;   // only for roi_level()
-  LV.num_levels = a.num_levels;
-  LV.min_level = a.min_level;
+  roi_tile_zero(acc);
   for (int base = 0; base < a.P; base += 256) {
-    // ---- which of these 256 ROIs touch the tile (kept in ROI order) ----
+    // ---- which of these 256 ROIs touch the tile ----
     const int slot = base + tid;
     bool hit = false;
     if (slot < a.P) {
       const int r = n * a.P + slot;
       if (!roi_valid || roi_valid[r]) {
         const float4 bx = ((const float4*)rois)[r];
-        if (roi_level(bx, LV) == li) {
+        if (roi_level(bx, a.min_level, a.num_levels) == li) {
           const float off = a.aligned ? 0.5f : 0.f;
           const float y1 = bx.y * sc - off, x1 = bx.x * sc - off;
           float y2 = bx.w * sc - off, x2 = bx.z * sc - off;
@@ -503,17 +540,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
         }
       }
     }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wcount[wid] = __popcll(m);
-    __syncthreads();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wid) off += wcount[w];
-      total += wcount[w];
-    }
-    if (hit) list[off + __popcll(m & ((1ull << lane) - 1ull))] = slot;
-    __syncthreads();
+    const int total = roi_tile_list(hit, slot, list, wcount);
     // ---- accumulate them one by one ----
     for (int k = 0; k < total; ++k) {
       const int r = n * a.P + list[k];
@@ -530,14 +557,10 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
           const float start = (axis ? x1 : y1) + pb * (axis ? bw : bh), bin = axis ? bw : bh;
           const int g = axis ? gw : gh, size = axis ? W : H, pix = (axis ? tx0 : ty0) + t;
           for (int i = 0; i < g; ++i) {
-            float v = start + ((float)i + 0.5f) * bin / (float)g;
-            if (v < -1.f || v > (float)size) continue;
-            if (v <= 0.f) v = 0.f;
-            int l = (int)v, h;
-            if (l >= size - 1) { h = l = size - 1; v = (float)l; } else h = l + 1;
-            const float fr = v - (float)l;
-            if (l == pix) wsum += 1.f - fr;
-            if (h == pix) wsum += fr;
+            const AxisSample s = axis_sample(start + ((float)i + 0.5f) * bin / (float)g, size);
+            if (!s.ok) continue;
+            if (s.l == pix) wsum += 1.f - s.fr;
+            if (s.h == pix) wsum += s.fr;
           }
         }
         (axis ? wx : wy)[pb * RB_T + t] = wsum;
@@ -573,19 +596,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled(RoiBwdArgs a, const f
       __syncthreads();
     }
   }
-  if (cok) {
-    TO* out = (TO*)a.dfeat[li] + (size_t)n * H * W * a.C;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int y = ty0 + 2 * wid + r;
-      if (y >= H) continue;
-#pragma unroll
-      for (int x = 0; x < RB_T; ++x) {
-        if (tx0 + x >= W) continue;
-        st4(out + ((size_t)y * W + tx0 + x) * a.C, lane, acc[r][x]);
-      }
-    }
-  }
+  if (cok) roi_tile_store((TO*)a.dfeat[li] + (size_t)n * H * W * a.C, H, W, ty0 + 2 * wid, tx0, a.C, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -629,7 +640,7 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(RoiLevels L, const fl
   int* am = argmax + (size_t)r * PH * PW * C;
   const bool ok = roi_valid ? roi_valid[r] != 0 : true;
   const float4 b = ((const float4*)rois)[r];
-  const int li = ok ? roi_level(b, L) : 0;
+  const int li = ok ? roi_level(b, L.min_level, L.num_levels) : 0;
   const int H = L.H[li], W = L.W[li];
   const PoolBox pb = pool_box(b, L.scale[li], PH, PW);
   const T* f = (const T*)L.feat[li] + (size_t)(ok ? roi_batch[r] : 0) * H * W * C;
@@ -688,7 +699,7 @@ __global__ __launch_bounds__(64) void roi_pool_bwd_kernel(RoiLevels L, const flo
   const int r = blockIdx.x / (PH * PW);
   if (roi_valid && roi_valid[r] == 0) return;
   const float4 b = ((const float4*)rois)[r];
-  const int li = roi_level(b, L);
+  const int li = roi_level(b, L.min_level, L.num_levels);
   const int HW = L.H[li] * L.W[li];
   float* df = L.dfeat[li] + (size_t)roi_batch[r] * HW * C;
   const int C4 = C >> 2;
@@ -714,30 +725,13 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const fl
   __shared__ int list[256];
   __shared__ int wcount[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int li = 0;
-#pragma unroll
-  for (int l = 1; l < 4; ++l)
-    if (l < a.num_levels && (int)blockIdx.x >= a.tile_start[l]) li = l;
-  const int H = a.H[li], W = a.W[li];
-  const int tx_n = (W + RB_T - 1) / RB_T, ty_n = (H + RB_T - 1) / RB_T;
-  int b = blockIdx.x - a.tile_start[li];
-  const int n = b / (tx_n * ty_n);
-  b -= n * tx_n * ty_n;
-  const int ty0 = (b / tx_n) * RB_T, tx0 = (b % tx_n) * RB_T;
-  const float sc = a.scale[li];
-  const int C4 = a.C >> 2;
-  const bool cok = lane < C4;
+  const RoiTile t = roi_tile(a);
+  const int li = t.li, n = t.n, H = t.H, W = t.W, ty0 = t.ty0, tx0 = t.tx0;
+  const float sc = t.sc;
+  const bool cok = lane < (a.C >> 2);
   const int r0 = ty0 + 2 * wid;      // this wave's two rows
-
   f32x4 acc[2][RB_T];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int x = 0; x < RB_T; ++x) acc[r][x] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  RoiLevels LV;   // only for roi_level()
-  LV.num_levels = a.num_levels;
-  LV.min_level = a.min_level;
+  roi_tile_zero(acc);
   for (int base = 0; base < a.P; base += 256) {
     const int slot = base + tid;
     bool hit = false;
@@ -745,7 +739,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const fl
       const int r = n * a.P + slot;
       if (!roi_valid || roi_valid[r]) {
         const float4 bx = ((const float4*)rois)[r];
-        if (roi_level(bx, LV) == li) {
+        if (roi_level(bx, a.min_level, a.num_levels) == li) {
           const PoolBox pb = pool_box(bx, sc, a.PH, a.PW);
           int ylo, yhi, xlo, xhi, t;
           pool_window(0, pb.bh, pb.y1, H, ylo, t);
@@ -756,17 +750,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const fl
         }
       }
     }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wcount[wid] = __popcll(m);
-    __syncthreads();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wid) off += wcount[w];
-      total += wcount[w];
-    }
-    if (hit) list[off + __popcll(m & ((1ull << lane) - 1ull))] = slot;
-    __syncthreads();
+    const int total = roi_tile_list(hit, slot, list, wcount);
     if (cok) {
       for (int k = 0; k < total; ++k) {
         const int r = n * a.P + list[k];
@@ -799,19 +783,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const fl
     }
     __syncthreads();   // list is rewritten by the next round
   }
-  if (cok) {
-    TO* out = (TO*)a.dfeat[li] + (size_t)n * H * W * a.C;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int y = r0 + r;
-      if (y >= H) continue;
-#pragma unroll
-      for (int x = 0; x < RB_T; ++x) {
-        if (tx0 + x >= W) continue;
-        st4(out + ((size_t)y * W + tx0 + x) * a.C, lane, acc[r][x]);
-      }
-    }
-  }
+  if (cok) roi_tile_store((TO*)a.dfeat[li] + (size_t)n * H * W * a.C, H, W, r0, tx0, a.C, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1497,11 +1469,21 @@ int utv2_match_lowq(const float* boxes, int64_t box_img_stride, int N, int P, co
   return utv2_launch_status();
 }
 
-static int fill_levels(RoiLevels& L, int num_levels, int min_level, const void* const* feats, float* const* dfeats,
-                       const int* H, const int* W, const float* scales) {
-  if (num_levels < 1 || num_levels > 4) return UTV2_EARG;
+// what the three pooler entry points ask of the arguments they share (maps_host: the level pointers, io: out / dy)
+static bool pooler_args_ok(int pooler, int sampling_ratio, int num_levels, const void* const* maps_host, const int* H_host,
+                           const int* W_host, const float* scales_host, const float* rois, const void* io, const int* argmax, int C,
+                           int PH, int PW, int dtype) {
+  return (pooler == UTV2_POOLER_ALIGN_V2 || pooler == UTV2_POOLER_ALIGN || pooler == UTV2_POOLER_MAX) && sampling_ratio >= 0 &&
+         num_levels >= 1 && num_levels <= 4 && maps_host && H_host && W_host && scales_host && rois && io &&
+         (pooler != UTV2_POOLER_MAX || argmax) && !(C & 3) && PH >= 1 && PW >= 1 && (dtype == UTV2_F32 || dtype == UTV2_BF16);
+}
+
+static void fill_levels(RoiLevels& L, int pooler, int sampling_ratio, int num_levels, int min_level, const void* const* feats,
+                        float* const* dfeats, const int* H, const int* W, const float* scales) {
   L.num_levels = num_levels;
   L.min_level = min_level;
+  L.aligned = pooler == UTV2_POOLER_ALIGN_V2;
+  L.ratio = sampling_ratio;
   for (int i = 0; i < 4; ++i) {
     const bool on = i < num_levels;
     L.feat[i] = on && feats ? feats[i] : nullptr;
@@ -1510,53 +1492,41 @@ static int fill_levels(RoiLevels& L, int num_levels, int min_level, const void* 
     L.W[i] = on ? W[i] : 0;
     L.scale[i] = on ? scales[i] : 0.f;
   }
-  return UTV2_OK;
 }
+
+// runs the statement with T = the element type a UTV2_F32 / UTV2_BF16 code names
+#define ROI_BY_DTYPE(code, T, ...) \
+  do { if ((code) == UTV2_BF16) { using T = h16_t; __VA_ARGS__; } else { using T = float; __VA_ARGS__; } } while (0)
 
 // feats_host: host array of num_levels device pointers (NHWC level features of element type `dtype`, same C).
 // rois [R][4] xyxy in image coordinates, roi_batch [R] image index, roi_valid [R] (optional).
 // out [R][PH][PW][C] of element type `dtype`; argmax (UTV2_POOLER_MAX only) [R][PH][PW][C] int32.
-static bool pooler_ok(int pooler, int sampling_ratio) {
-  return (pooler == UTV2_POOLER_ALIGN_V2 || pooler == UTV2_POOLER_ALIGN || pooler == UTV2_POOLER_MAX) && sampling_ratio >= 0;
-}
-
 int utv2_roi_pooler_fwd(int pooler, int sampling_ratio, int num_levels, int min_level, const void* const* feats_host, const int* H_host,
                         const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
                         const unsigned char* roi_valid, int R, int C, int PH, int PW, void* out, int* argmax, int dtype,
                         hipStream_t stream) {
-  RoiLevels L;
-  if (fill_levels(L, num_levels, min_level, feats_host, nullptr, H_host, W_host, scales_host) != UTV2_OK || (C & 3) || !rois ||
-      !roi_batch || !out || (dtype != UTV2_F32 && dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || PH < 1 || PW < 1)
+  if (!pooler_args_ok(pooler, sampling_ratio, num_levels, feats_host, H_host, W_host, scales_host, rois, out, argmax, C, PH, PW, dtype) ||
+      !roi_batch)
     return UTV2_EARG;
-  L.aligned = pooler == UTV2_POOLER_ALIGN_V2;
-  L.ratio = sampling_ratio;
+  RoiLevels L;
+  fill_levels(L, pooler, sampling_ratio, num_levels, min_level, feats_host, nullptr, H_host, W_host, scales_host);
   const int V = dtype == UTV2_BF16 ? 8 : 4;
   if (pooler == UTV2_POOLER_MAX) {
-    if (!argmax || C % V) return UTV2_EARG;
+    if (C % V) return UTV2_EARG;
     for (int l = 0; l < num_levels; ++l)
       if ((long long)H_host[l] * W_host[l] > 2147483647ll) return UTV2_EARG;   // argmax is a 32-bit pixel index
-    if (R == 0) return UTV2_OK;
-    if (dtype == UTV2_BF16)
-      hipLaunchKernelGGL((roi_pool_fwd_kernel<h16_t>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)out, argmax);
-    else
-      hipLaunchKernelGGL((roi_pool_fwd_kernel<float>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (float*)out, argmax);
-    return utv2_launch_status();
   }
   if (R == 0) return UTV2_OK;
   static const bool per_roi = env_on("UTV2_ROI_FWD_PER_ROI");   // A/B: 0 = one wave per (roi, bin)
-  if (per_roi && PH <= 7 && PW <= 7 && C % V == 0) {
-    if (dtype == UTV2_BF16)
-      hipLaunchKernelGGL((roi_align_fwd_roi_kernel<h16_t>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)out);
+  ROI_BY_DTYPE(dtype, T, {
+    if (pooler == UTV2_POOLER_MAX)
+      hipLaunchKernelGGL((roi_pool_fwd_kernel<T>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (T*)out, argmax);
+    else if (per_roi && PH <= 7 && PW <= 7 && C % V == 0)
+      hipLaunchKernelGGL((roi_align_fwd_roi_kernel<T>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (T*)out);
     else
-      hipLaunchKernelGGL((roi_align_fwd_roi_kernel<float>), dim3(R), dim3(256), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (float*)out);
-    return utv2_launch_status();
-  }
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<false, h16_t>), dim3(R * PH * PW), dim3(64), 0, stream, L, rois, roi_batch, roi_valid, C, PH,
-                       PW, (h16_t*)out);
-  else
-    hipLaunchKernelGGL((roi_align_kernel<false, float>), dim3(R * PH * PW), dim3(64), 0, stream, L, rois, roi_batch, roi_valid, C, PH,
-                       PW, (float*)out);
+      hipLaunchKernelGGL((roi_align_kernel<false, T>), dim3(R * PH * PW), dim3(64), 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW,
+                         (T*)out);
+  });
   return utv2_launch_status();
 }
 
@@ -1566,26 +1536,20 @@ int utv2_roi_pooler_bwd(int pooler, int sampling_ratio, int num_levels, int min_
                         const int* W_host, const float* scales_host, const float* rois, const int* roi_batch,
                         const unsigned char* roi_valid, int R, int C, int PH, int PW, const void* dy, const int* argmax, int dtype,
                         hipStream_t stream) {
-  RoiLevels L;
-  if (fill_levels(L, num_levels, min_level, nullptr, dfeats_host, H_host, W_host, scales_host) != UTV2_OK || (C & 3) || !rois ||
-      !roi_batch || !dy || (dtype != UTV2_F32 && dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || PH < 1 || PW < 1 ||
-      (pooler == UTV2_POOLER_MAX && !argmax))
+  if (!pooler_args_ok(pooler, sampling_ratio, num_levels, (const void* const*)dfeats_host, H_host, W_host, scales_host, rois, dy, argmax, C,
+                      PH, PW, dtype) ||
+      !roi_batch)
     return UTV2_EARG;
-  L.aligned = pooler == UTV2_POOLER_ALIGN_V2;
-  L.ratio = sampling_ratio;
+  RoiLevels L;
+  fill_levels(L, pooler, sampling_ratio, num_levels, min_level, nullptr, dfeats_host, H_host, W_host, scales_host);
   if (R == 0) return UTV2_OK;
   const dim3 g(R * PH * PW), b(64);
-  if (pooler == UTV2_POOLER_MAX) {
-    if (dtype == UTV2_BF16)
-      hipLaunchKernelGGL((roi_pool_bwd_kernel<h16_t>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (const h16_t*)dy, argmax);
+  ROI_BY_DTYPE(dtype, T, {
+    if (pooler == UTV2_POOLER_MAX)
+      hipLaunchKernelGGL((roi_pool_bwd_kernel<T>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (const T*)dy, argmax);
     else
-      hipLaunchKernelGGL((roi_pool_bwd_kernel<float>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (const float*)dy, argmax);
-    return utv2_launch_status();
-  }
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL((roi_align_kernel<true, h16_t>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (h16_t*)dy);
-  else
-    hipLaunchKernelGGL((roi_align_kernel<true, float>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (float*)dy);
+      hipLaunchKernelGGL((roi_align_kernel<true, T>), g, b, 0, stream, L, rois, roi_batch, roi_valid, C, PH, PW, (T*)dy);
+  });
   return utv2_launch_status();
 }
 
@@ -1596,9 +1560,9 @@ int utv2_roi_pooler_bwd_tiled(int pooler, int sampling_ratio, int num_levels, in
                               const int* W_host, const float* scales_host, const float* rois, const unsigned char* roi_valid, int N,
                               int rois_per_image, int C, int PH, int PW, const void* dy, const int* argmax, int dy_dtype, int out_dtype,
                               hipStream_t stream) {
-  if (num_levels < 1 || num_levels > 4 || !dfeats_host || !H_host || !W_host || !scales_host || !rois || !dy || (C & 3) || C > 256 ||
-      PH < 1 || PH > 7 || PW < 1 || PW > 7 || N < 1 || rois_per_image < 1 || (dy_dtype != UTV2_F32 && dy_dtype != UTV2_BF16) ||
-      (out_dtype != UTV2_F32 && out_dtype != UTV2_BF16) || !pooler_ok(pooler, sampling_ratio) || (pooler == UTV2_POOLER_MAX && !argmax))
+  if (!pooler_args_ok(pooler, sampling_ratio, num_levels, (const void* const*)dfeats_host, H_host, W_host, scales_host, rois, dy, argmax, C,
+                      PH, PW, dy_dtype) ||
+      C > 256 || PH > 7 || PW > 7 || N < 1 || rois_per_image < 1 || (out_dtype != UTV2_F32 && out_dtype != UTV2_BF16))
     return UTV2_EARG;
   RoiBwdArgs a;
   int blocks = 0;
@@ -1616,47 +1580,15 @@ int utv2_roi_pooler_bwd_tiled(int pooler, int sampling_ratio, int num_levels, in
   a.num_levels = num_levels; a.min_level = min_level; a.N = N; a.P = rois_per_image; a.C = C; a.PH = PH; a.PW = PW;
   a.aligned = pooler == UTV2_POOLER_ALIGN_V2; a.ratio = sampling_ratio;
   const dim3 g(blocks), b(256);
-  if (pooler == UTV2_POOLER_MAX) {
-    if (dy_dtype == UTV2_BF16) {
-      if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_pool_bwd_tiled<h16_t, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy, argmax);
-      else hipLaunchKernelGGL((roi_pool_bwd_tiled<h16_t, float>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy, argmax);
-    } else {
-      if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_pool_bwd_tiled<float, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy, argmax);
-      else hipLaunchKernelGGL((roi_pool_bwd_tiled<float, float>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy, argmax);
-    }
-    return utv2_launch_status();
-  }
-  if (dy_dtype == UTV2_BF16) {
-    if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_align_bwd_tiled<h16_t, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy);
-    else hipLaunchKernelGGL((roi_align_bwd_tiled<h16_t, float>), g, b, 0, stream, a, rois, roi_valid, (const h16_t*)dy);
-  } else {
-    if (out_dtype == UTV2_BF16) hipLaunchKernelGGL((roi_align_bwd_tiled<float, h16_t>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy);
-    else hipLaunchKernelGGL((roi_align_bwd_tiled<float, float>), g, b, 0, stream, a, rois, roi_valid, (const float*)dy);
-  }
+  ROI_BY_DTYPE(dy_dtype, TI, ROI_BY_DTYPE(out_dtype, TO, {
+    if (pooler == UTV2_POOLER_MAX)
+      hipLaunchKernelGGL((roi_pool_bwd_tiled<TI, TO>), g, b, 0, stream, a, rois, roi_valid, (const TI*)dy, argmax);
+    else
+      hipLaunchKernelGGL((roi_align_bwd_tiled<TI, TO>), g, b, 0, stream, a, rois, roi_valid, (const TI*)dy);
+  }));
   return utv2_launch_status();
 }
-
-// the shipped configs' pooler: RoIAlign, aligned, adaptive sampling grid
-int utv2_roi_align_fwd(int num_levels, int min_level, const void* const* feats_host, const int* H_host, const int* W_host,
-                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
-                       int R, int C, int PH, int PW, void* out, int dtype, hipStream_t stream) {
-  return utv2_roi_pooler_fwd(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, feats_host, H_host, W_host, scales_host, rois, roi_batch,
-                             roi_valid, R, C, PH, PW, out, nullptr, dtype, stream);
-}
-
-int utv2_roi_align_bwd(int num_levels, int min_level, float* const* dfeats_host, const int* H_host, const int* W_host,
-                       const float* scales_host, const float* rois, const int* roi_batch, const unsigned char* roi_valid,
-                       int R, int C, int PH, int PW, const void* dy, int dtype, hipStream_t stream) {
-  return utv2_roi_pooler_bwd(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, dfeats_host, H_host, W_host, scales_host, rois, roi_batch,
-                             roi_valid, R, C, PH, PW, dy, nullptr, dtype, stream);
-}
-
-int utv2_roi_align_bwd_tiled(int num_levels, int min_level, void* const* dfeats_host, const int* H_host, const int* W_host,
-                             const float* scales_host, const float* rois, const unsigned char* roi_valid, int N, int rois_per_image,
-                             int C, int PH, int PW, const void* dy, int dy_dtype, int out_dtype, hipStream_t stream) {
-  return utv2_roi_pooler_bwd_tiled(UTV2_POOLER_ALIGN_V2, 0, num_levels, min_level, dfeats_host, H_host, W_host, scales_host, rois,
-                                   roi_valid, N, rois_per_image, C, PH, PW, dy, nullptr, dy_dtype, out_dtype, stream);
-}
+#undef ROI_BY_DTYPE
 
 // The scalar tail of the Faster-RCNN UTv2 losses in ONE launch (the FCOS counterpart is utv2_fcos_loss_combine): raw kernel sums of the
 // two loss branches -> the eight losses of the trainer's record_dict, their weighted total and d total / d raw sums.
