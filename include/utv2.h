@@ -103,7 +103,7 @@ int utv2_conv2d_ml_fwd_bf16_g(const void* x, int x_dtype, int x_pitch, const voi
                               float* gn_part, const int* rowinfo, utv2_stream_t stream);
 /* The dgrad that produces the gradient of a GroupNorm + ReLU OUTPUT (the FCOS towers' conv -> GN -> ReLU chain, fcos/fcos.py:252-304,
  * in backward): a 16-bit level-first conv as ..._g with dense y (pitch K) whose epilogue applies the ReLU mask - mask_bits: [P * K / 8]
- * bytes, the plane utv2_groupnorm_relu_seg_fwd_p32b wrote - and leaves GroupNorm backward's first reduction, taken while the rows are in
+ * bytes, the plane utv2_groupnorm_relu_seg_fwd_p32 wrote - and leaves GroupNorm backward's first reduction, taken while the rows are in
  * registers: gnb_part fp32 [ceil(P / 64)][K][2] = {sum y, sum y * gnb_x} per 64-row block and channel over the rows as stored
  * (gnb_x: [P][K], the GroupNorm's input, 16-bit).  utv2_groupnorm_seg_bwd_p64 finishes the backward from them.
  * C % 64 == 0, KH * KW * C >= 1024, (K / groups) % 128 == 0. */
@@ -158,11 +158,14 @@ int utv2_weight_flip_transpose_bf16_batched(const float* arena, const float* sca
                                             utv2_stream_t stream);
 
 /* ---- teacher EMA: engine/trainer.py:468-486 (FCOS), :950-968 (RCNN) --------------------------
- * teacher = student*(1-keep) + teacher*keep, evaluated with the reference's three roundings. */
-int utv2_ema_axpby(float* teacher, const float* student, int64_t n, double keep_rate, utv2_stream_t stream);
+ * teacher = student*(1-keep) + teacher*keep, evaluated with the reference's three roundings.
+ * mirror16 (optional; here 8-byte aligned, and in the two SGD updates below): the 16-bit mirror of the arena range that is updated -
+ * mirror16[i] = the library's 16-bit rounding of the new value, the copy the mixed-precision convs read: the weights are not re-read by a
+ * conversion pass before the next forward */
+int utv2_ema_axpby(float* teacher, const float* student, void* mirror16, int64_t n, double keep_rate, utv2_stream_t stream);
 /* ---- SGD+momentum+weight-decay on a flat arena: torch.optim.SGD via D2 build_optimizer
  * (engine/trainer.py:50,625; optimizer.step at :425-429,:912). */
-int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, int64_t n, float lr, float momentum, float weight_decay,
+int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum, float weight_decay,
                       float grad_scale, int zero_grad, utv2_stream_t stream);
 /* Dynamic loss scaling of the fp16 AMP mode with torch.cuda.amp.GradScaler's semantics (reference engine/trainer.py:207,424-426),
  * on the device: state = fp32 {loss scale, found_inf flag, growth tracker}.  utv2_amp_found_inf sets the flag when the (scaled)
@@ -170,16 +173,9 @@ int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, int64_t n, floa
  * all when the flag is set; utv2_amp_update_scale: flag ? scale *= backoff : (every growth_interval clean steps scale *= growth),
  * then clears the flag. */
 int utv2_amp_found_inf(const float* grad, int64_t n, float* state, utv2_stream_t stream);
-int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, int64_t n, float lr, float momentum, float weight_decay,
-                          float grad_scale, const float* state, utv2_stream_t stream);
+int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum,
+                          float weight_decay, float grad_scale, const float* state, utv2_stream_t stream);
 int utv2_amp_update_scale(float* state, float growth_factor, float backoff_factor, int growth_interval, utv2_stream_t stream);
-/* the three updates above that ALSO write the 16-bit mirror of the arena range they update (mirror16[i] = the library's 16-bit rounding of
- * the new value; the copy the mixed-precision convs read): the weights are not re-read by a conversion pass before the next forward */
-int utv2_ema_axpby_m16(float* teacher, const float* student, void* mirror16, int64_t n, double keep_rate, utv2_stream_t stream);
-int utv2_sgd_momentum_m16(float* param, float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum, float weight_decay,
-                          float grad_scale, int zero_grad, utv2_stream_t stream);
-int utv2_sgd_momentum_amp_m16(float* param, const float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum,
-                              float weight_decay, float grad_scale, const float* state, utv2_stream_t stream);
 
 /* ---- elementwise pieces of ResNet / FPN ([D2-recall]) ------------------ */
 int utv2_relu_bwd_scale(const void* dy, const void* y, const float* scale, void* out, int64_t M, int C, int dtype,
@@ -217,47 +213,36 @@ int utv2_preprocess_images_bf16pad(const void* const* src_host, int is_u8, void*
 /* D2 FrozenBatchNorm2d.forward: scale = w*rsqrt(var+eps), shift = b - mean*scale, all layers at once */
 int utv2_frozenbn_fold(const float* w, const float* b, const float* mean, const float* var, float* scale, float* shift,
                        int n, float eps, utv2_stream_t stream);
-/* GroupNorm(32)+ReLU of the FCOS towers: fcos/fcos.py:263-264,283.  The _seg forms normalise every
- * (image, FPN level) segment of a level-first [rows][C] buffer in one launch (seg_rows_host: host int[nseg]). */
+/* GroupNorm(32)+ReLU of the FCOS towers: fcos/fcos.py:263-264,283.  Every entry normalises all the (image, FPN level) segments of a
+ * level-first [rows][C] buffer in one launch chain (seg_rows_host: host int[nseg], 1 <= nseg <= 160, rows of each segment >= 0; a dense
+ * [N][HW][C] tensor is N segments of HW rows).  ws: utv2_groupnorm_seg_workspace_floats() floats, for the forward and both backwards. */
 int64_t utv2_groupnorm_seg_workspace_floats(int nseg, const int* seg_rows_host, int C);
 int utv2_groupnorm_relu_seg_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                 float* ws, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu, int dtype,
                                 utv2_stream_t stream);
 /* the same for bf16 x with 8 channels per group when the conv that produced x left the statistics partials in part32
- * (utv2_conv2d_ml_fwd_bf16_g gn_part: fp32 [ceil(rows / 32)][G][2]): one tensor pass less */
+ * (utv2_conv2d_ml_fwd_bf16_g gn_part: fp32 [ceil(rows / 32)][G][2]): one tensor pass less.
+ * relu_bits (optional; C % 32 == 0): also writes the ReLU mask as a bit plane, [rows * C / 8] bytes, bit (row * C + c) = y > 0 in fp32,
+ * before the 16-bit rounding (the reference's ReLU follows an fp32 GroupNorm under autocast): the mask ..._seg_bwd recomputes from x */
 int utv2_groupnorm_relu_seg_fwd_p32(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                     const float* part32, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu,
-                                    utv2_stream_t stream);
-/* ... that also writes the ReLU mask as a bit plane: relu_bits (optional; C % 32 == 0) [rows * C / 8] bytes, bit (row * C + c) = y > 0 in
- * fp32, before the 16-bit rounding (the reference's ReLU follows an fp32 GroupNorm under autocast): the mask ..._seg_bwd recomputes from x */
-int utv2_groupnorm_relu_seg_fwd_p32b(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                     const float* part32, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu,
-                                     void* relu_bits, utv2_stream_t stream);
-/* beta (optional): the ReLU mask is recomputed from x with the forward expression instead of read from y (y may be null) */
-int utv2_groupnorm_relu_seg_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
-                                int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, utv2_stream_t stream);
-/* the same with colsum_part (optional, fp32 [utv2_groupnorm_seg_chunks(...)][C]) = per-chunk column sums of dx as stored: summed over
- * the chunks (utv2_colsum) they are the bias gradient of the convolution in front of the GroupNorm (fcos.py:263: conv -> GN -> ReLU), whose
+                                    void* relu_bits, utv2_stream_t stream);
+/* beta (optional): the ReLU mask is recomputed from x with the forward expression instead of read from y (y may be null).
+ * colsum_part (optional, fp32 [utv2_groupnorm_seg_chunks(...)][C]) = per-chunk column sums of dx as stored: summed over the chunks
+ * (utv2_colsum_partials) they are the bias gradient of the convolution in front of the GroupNorm (fcos.py:263: conv -> GN -> ReLU), whose
  * dY is this dx - no separate pass over dY */
 int64_t utv2_groupnorm_seg_chunks(int nseg, const int* seg_rows_host);
-int utv2_groupnorm_relu_seg_bwd_colsum(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                       const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
-                                       int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, float* colsum_part,
-                                       utv2_stream_t stream);
+int utv2_groupnorm_relu_seg_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
+                                const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
+                                int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, float* colsum_part,
+                                utv2_stream_t stream);
 /* GroupNorm (+ ReLU) backward from the partial sums of utv2_conv2d_ml_fwd_bf16_gnb: g = the incoming gradient with the ReLU mask already
- * applied (16-bit [rows][C]), part64 = that conv's gnb_part.  dx / dgamma / dbeta / colsum_part / ws as ..._seg_bwd_colsum. */
+ * applied (16-bit [rows][C]), part64 = that conv's gnb_part.  dx / dgamma / dbeta / colsum_part / ws as utv2_groupnorm_relu_seg_bwd. */
 int utv2_groupnorm_seg_bwd_p64(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,
                                float* dgamma, float* dbeta, float* ws, int nseg, const int* seg_rows_host, int C, int G,
                                const float* part64, float* colsum_part, utv2_stream_t stream);
 /* db[c] (+)= sum_b partial[b][c], partial fp32 [nb][K] (the colsum_part above; fixed summation order) */
 int utv2_colsum_partials(const float* partial, float* db, int nb, int K, int accumulate, utv2_stream_t stream);
-int64_t utv2_groupnorm_workspace_floats(int N, int HW, int C);
-int utv2_groupnorm_relu_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
-                            float* ws, int N, int HW, int C, int G, float eps, int relu, utv2_stream_t stream);
-int utv2_groupnorm_relu_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd,
-                            const float* gamma, float* dx, float* dgamma, float* dbeta, float* ws, int N, int HW, int C,
-                            int G, int relu, utv2_stream_t stream);
 
 /* ---- FCOS targets / losses / decode: modeling/fcos/fcos_outputs.py --------------------------- */
 /* :649-698,:772-906; center_radius > 0 = CENTER_SAMPLE with POS_RADIUS (get_sample_region :700-770), 0 = plain in-box test.

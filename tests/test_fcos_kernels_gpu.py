@@ -289,7 +289,7 @@ def test_groupnorm_relu_fwd_bwd():
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_groupnorm_bwd_column_sums_of_dx(dtype):
-    """utv2_groupnorm_relu_seg_bwd_colsum: the per-chunk column sums written next to dx add up to the column sums of dx AS STORED (the
+    """utv2_groupnorm_relu_seg_bwd with colsum_part: the per-chunk column sums written next to dx add up to the column sums of dx AS STORED (the
     bias gradient of the conv in front of the GroupNorm: what the separate colsum pass over its dY computed), dx / dgamma / dbeta are those
     of the plain entry; ragged (image, level) segments, chunks that end mid-way."""
     from ubteacher import hip

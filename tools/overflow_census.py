@@ -19,8 +19,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-FWD = ["conv2d_fwd", "conv2d_stem_fwd", "conv2d_ml_fwd", "groupnorm_relu_seg_fwd", "groupnorm_relu_fwd", "upsample2x_add", "maxpool3x3s2"]
-BWD = ["conv2d_dgrad", "conv2d_ml_dgrad", "groupnorm_relu_seg_bwd", "groupnorm_relu_bwd", "relu_bwd_scale", "downsample2x_sum",
+FWD = ["conv2d_fwd", "conv2d_stem_fwd", "conv2d_ml_fwd", "groupnorm_relu_seg_fwd", "upsample2x_add", "maxpool3x3s2"]
+BWD = ["conv2d_dgrad", "conv2d_ml_dgrad", "groupnorm_relu_seg_bwd", "relu_bwd_scale", "downsample2x_sum",
        "zero_interleave2x", "add"]
 F16_MAX, F16_MIN_NORMAL, F16_MIN_SUB = 65504.0, 6.1035e-5, 5.96e-8
 SCALE = 65536.0

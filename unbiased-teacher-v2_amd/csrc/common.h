@@ -62,6 +62,20 @@ __device__ __forceinline__ float __attribute__((ext_vector_type(16))) mfma_32x32
 #define UTV2_F32 0
 #define UTV2_BF16 1
 
+// Element-type dispatch: f(TypeTag<T>{}) with T = the type `dtype` names (h16_t / float) - the one place a launch site chooses between
+// the 16-bit and the fp32 instantiation of a kernel; with_types: the same for a kernel templated on two tensor types.
+template <typename T> struct TypeTag { using type = T; };
+#define TAG_T(tag) typename decltype(tag)::type
+template <typename F>
+static void with_type(int dtype, F&& f) {
+  if (dtype == UTV2_BF16) f(TypeTag<h16_t>{});
+  else f(TypeTag<float>{});
+}
+template <typename F>
+static void with_types(int dtype_a, int dtype_b, F&& f) {
+  with_type(dtype_a, [&](auto ta) { with_type(dtype_b, [&](auto tb) { f(ta, tb); }); });
+}
+
 // quad (4 consecutive elements) load / store of an activation tensor, arithmetic always in fp32
 __device__ __forceinline__ f32x4 ld4(const float* p, size_t i4) { return ((const f32x4*)p)[i4]; }
 __device__ __forceinline__ f32x4 ld4(const h16_t* p, size_t i4) {

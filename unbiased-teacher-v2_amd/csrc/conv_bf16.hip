@@ -1384,20 +1384,6 @@ static const int g_epi_general = env_int("UTV2_EPI_PLAIN", 1) ? 0 : 2;   // OR-e
 static const int g_use_pp = env_int("UTV2_PP", 2) == 1 ? 1 : 2;  // 256 x 256 forward tile, ping-pong schedule: 2 = persistent grid of 256 workgroups,
                                                                  // 1 = one tile per workgroup
 
-// Element-type dispatch: f(TypeTag<T>{}) with T = the type `dtype` names (h16_t / float) - the one place a launch site chooses between
-// the 16-bit and the fp32 instantiation of a kernel; with_types: the same for a kernel templated on two tensor types.
-template <typename T> struct TypeTag { using type = T; };
-#define TAG_T(tag) typename decltype(tag)::type
-template <typename F>
-static void with_type(int dtype, F&& f) {
-  if (dtype == UTV2_BF16) f(TypeTag<h16_t>{});
-  else f(TypeTag<float>{});
-}
-template <typename F>
-static void with_types(int dtype_a, int dtype_b, F&& f) {
-  with_type(dtype_a, [&](auto ta) { with_type(dtype_b, [&](auto tb) { f(ta, tb); }); });
-}
-
 template <int BN, bool ML>
 static void launch_igemm16(const ConvArgs16& a, int tiles, int x_dtype, int y_dtype, hipStream_t stream) {
   const dim3 g(tiles), b(256);
@@ -1591,7 +1577,7 @@ int utv2_conv2d_ml_fwd_bf16_g(const void* x, int x_dtype, int x_pitch, const voi
 
 // The dgrad that produces the gradient of a GroupNorm + ReLU output (FCOS towers, fcos/fcos.py:252-304 in backward): a 16-bit level-first
 // conv as utv2_conv2d_ml_fwd_bf16_g (dense y: pitch K) whose epilogue applies the ReLU mask - mask_bits: [P * K / 8] bytes, the plane
-// utv2_groupnorm_relu_seg_fwd_p32b wrote - and leaves GroupNorm backward's first reduction: gnb_part fp32 [ceil(P / 64)][K][2] =
+// utv2_groupnorm_relu_seg_fwd_p32 wrote - and leaves GroupNorm backward's first reduction: gnb_part fp32 [ceil(P / 64)][K][2] =
 // {sum y, sum y * gnb_x} per 64-row block and channel over the rows as stored (gnb_x: [P][K], the GroupNorm's input, y's element type).
 // utv2_groupnorm_seg_bwd_p64 finishes the backward from them.  C % 64 == 0, KH * KW * C >= 1024, K % 128 == 0 per group.
 int utv2_conv2d_ml_fwd_bf16_gnb(const void* x, int x_pitch, const void* w16, void* y, int nlev, const int* H_host, const int* W_host, int N,
@@ -2432,7 +2418,7 @@ static bool wgrad16_w8_shape_ok(int M, int C, int K, int KH, int KW, int xs, int
 int utv2_conv2d_wgrad_bf16_splits(int M, int K, int Kred) { return wgrad16_small_splits(M, K, Kred); }
 
 // large enough for either kernel (which one runs also depends on the element types)
-// db[c] (+)= sum_b partial[b][c] for a [nb][K] matrix of per-block column sums (e.g. utv2_groupnorm_relu_seg_bwd_colsum's): 32 channels x
+// db[c] (+)= sum_b partial[b][c] for a [nb][K] matrix of per-block column sums (e.g. utv2_groupnorm_relu_seg_bwd's colsum_part): 32 channels x
 // 8 row parts per workgroup, fixed combine order
 int utv2_colsum_partials(const float* partial, float* db, int nb, int K, int accumulate, hipStream_t stream) {
   if (!partial || !db || nb < 1 || K < 1) return UTV2_EARG;

@@ -498,6 +498,68 @@ __device__ __forceinline__ void gn_locate(const GnSegs& sg, int chunk, int& seg,
   if (r1 > sg.row0[s + 1]) r1 = sg.row0[s + 1];
 }
 
+// The row walk of every per-chunk pass: row lane rl of RL takes rows r0 + rl, r0 + rl + RL, ... < r1 in ascending order (the sums are
+// fixed-order fp32 reductions).  Four rows are loaded before the four are consumed, then a rolled tail: with one dependent load per
+// iteration the passes were latency-bound (the statistics at 2.5 TB/s), and inside the step they share the chip with the weight-gradient
+// stream and get a fraction of the CUs, so the bandwidth one CU sustains decides their time (gn_bwd_apply: 324 us per launch in the step
+// against ~100 alone).  load(row) -> the row's operands, use(operands, row).
+template <typename Load, typename Use>
+__device__ __forceinline__ void gn_walk_rows(int r0, int r1, int rl, int RL, Load load, Use use) {
+  int row = r0 + rl;
+  for (; row + 3 * RL < r1; row += 4 * RL) {
+    decltype(load(row)) v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = load(row + u * RL);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) use(v[u], row + u * RL);
+  }
+  for (; row < r1; row += RL) use(load(row), row);
+}
+
+struct GnGX { f32x4 g, x; };   // one row's operands of the backward passes: the gradient and the GroupNorm's input
+
+// The forward's value before the ReLU.  Its sign is the ReLU mask the backward recomputes from x, so the forward and the mask share this
+// one expression (the library is built with -ffp-contract=off: the same roundings wherever it is inlined).
+__device__ __forceinline__ float gn_affine(float x, float m, float r, float ga, float be) { return (x - m) * r * ga + be; }
+
+// gg where the forward's ReLU passed, 0 elsewhere.  remask (beta given): the sign of gn_affine recomputed from x - one tensor read less
+// in each backward pass; otherwise the sign of the stored y at quad o.
+template <typename T>
+__device__ __forceinline__ f32x4 gn_relu_mask(f32x4 gg, const f32x4 xx, float m, float r, const f32x4 ga, const f32x4 be, bool remask,
+                                              int relu, const T* __restrict__ y, size_t o) {
+  if (remask) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gg[e] = gn_affine(xx[e], m, r, ga[e], be[e]) > 0.f ? gg[e] : 0.f;
+  } else if (relu) {
+    const f32x4 yy = ld4(y, o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
+  }
+  return gg;
+}
+
+// mean / rstd of cnt values with sum s and sum of squares q, in double (var clamped at 0)
+__device__ __forceinline__ void gn_mean_rstd(double s, double q, double cnt, float eps, float* mean, float* rstd) {
+  const double m = s / cnt;
+  double var = q / cnt - m * m;
+  if (var < 0.0) var = 0.0;
+  *mean = (float)m;
+  *rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// Rows [r0, r1) of a segment against a grid of (1 << shift)-row blocks: the whole blocks [b0, b1) and the edge rows in front of the
+// first, [r0, h1), and behind the last, [t0, r1).  A segment inside one block has no whole block and only "head" rows.
+struct GnSplit { int b0, b1, h1, t0; };
+__device__ __forceinline__ GnSplit gn_split(int r0, int r1, int shift) {
+  GnSplit s;
+  s.b0 = (r0 + (1 << shift) - 1) >> shift;
+  s.b1 = r1 >> shift;
+  if (s.b1 < s.b0) s.b1 = s.b0;
+  s.h1 = (s.b0 << shift) < r1 ? (s.b0 << shift) : r1;
+  s.t0 = (s.b1 << shift) > s.h1 ? (s.b1 << shift) : s.h1;
+  return s;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_partial(GnSegs sg, const T* __restrict__ x, float* __restrict__ part, int C, int G) {
   // thread t owns channel quad c4 = t % C4 and row lane t / C4 (deterministic reduction order)
@@ -508,24 +570,11 @@ __global__ __launch_bounds__(256) void gn_stats_partial(GnSegs sg, const T* __re
   const int cpg4 = (C / G) >> 2;  // channel quads per group
   const int c4 = threadIdx.x % C4, rl = threadIdx.x / C4, RL = blockDim.x / C4;
   float s = 0.f, q = 0.f;
-  int row = r0 + rl;
-  // four independent loads in flight per thread, accumulated in row order (same arithmetic as the rolled loop: the reduction was
-  // latency-bound at 2.5 TB/s with one dependent 8-byte load per iteration)
-  for (; row + 3 * RL < r1; row += 4 * RL) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = ld4(x, (size_t)(row + u * RL) * C4 + c4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      s += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
-      q += (v[u][0] * v[u][0] + v[u][1] * v[u][1]) + (v[u][2] * v[u][2] + v[u][3] * v[u][3]);
-    }
-  }
-  for (; row < r1; row += RL) {
-    const f32x4 v = ld4(x, (size_t)row * C4 + c4);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
-    q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  }
+  gn_walk_rows(r0, r1, rl, RL, [&](int row) { return ld4(x, (size_t)row * C4 + c4); },
+               [&](const f32x4 v, int) {
+                 s += (v[0] + v[1]) + (v[2] + v[3]);
+                 q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+               });
   red[0][threadIdx.x] = s;
   red[1][threadIdx.x] = q;
   __syncthreads();
@@ -559,12 +608,7 @@ __global__ __launch_bounds__(256) void gn_stats_final(GnSegs sg, const float* __
   __syncthreads();
   if (ln == 0) {
     for (int k = 1; k < L; ++k) { s += red[0][k * G + g]; q += red[1][k * G + g]; }
-    const double cnt = (double)(sg.row0[seg + 1] - sg.row0[seg]) * cpg;
-    const double m = s / cnt;
-    double var = q / cnt - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[seg * G + g] = (float)m;
-    rstd[seg * G + g] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd(s, q, (double)(sg.row0[seg + 1] - sg.row0[seg]) * cpg, eps, &mean[seg * G + g], &rstd[seg * G + g]);
   }
 }
 
@@ -580,20 +624,16 @@ __global__ __launch_bounds__(256) void gn_stats_final_p32(GnSegs sg, const float
   const int gl = threadIdx.x & 7, ln = threadIdx.x >> 3, L = 32;
   const int g = blockIdx.y * 8 + gl;
   const int r0 = sg.row0[seg], r1 = sg.row0[seg + 1];
-  int b0 = (r0 + 31) >> 5, b1 = r1 >> 5;      // whole blocks [b0, b1)
-  if (b1 < b0) b1 = b0;                        // the segment lies inside one block
+  const GnSplit sp = gn_split(r0, r1, 5);
   double s = 0.0, q = 0.0;
   if (g < G) {
-    for (int b = b0 + ln; b < b1; b += L) {
+    for (int b = sp.b0 + ln; b < sp.b1; b += L) {
       const float2 p = *(const float2*)(part32 + ((size_t)b * G + g) * 2);
       s += (double)p.x;
       q += (double)p.y;
     }
-    // edge rows: [r0, min(b0 * 32, r1)) and [max(b1 * 32, head end), r1)
-    const int h1 = (b0 << 5) < r1 ? (b0 << 5) : r1;
-    const int t0 = (b1 << 5) > h1 ? (b1 << 5) : h1;
     for (int pass = 0; pass < 2; ++pass) {
-      const int e0 = pass == 0 ? r0 : t0, e1 = pass == 0 ? h1 : r1;
+      const int e0 = pass == 0 ? r0 : sp.t0, e1 = pass == 0 ? sp.h1 : r1;
       for (int r = e0 + ln; r < e1; r += L) {
         const bf16x8_t v = *(const bf16x8_t*)(x + (size_t)r * C + g * 8);
         float fs = 0.f, fq = 0.f;
@@ -609,12 +649,7 @@ __global__ __launch_bounds__(256) void gn_stats_final_p32(GnSegs sg, const float
   __syncthreads();
   if (ln == 0 && g < G) {
     for (int k = 1; k < L; ++k) { s += red[0][k * 8 + gl]; q += red[1][k * 8 + gl]; }
-    const double cnt = (double)(r1 - r0) * 8.0;
-    const double m = s / cnt;
-    double var = q / cnt - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[seg * G + g] = (float)m;
-    rstd[seg * G + g] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd(s, q, (double)(r1 - r0) * 8.0, eps, &mean[seg * G + g], &rstd[seg * G + g]);
   }
 }
 
@@ -638,11 +673,12 @@ __global__ __launch_bounds__(256) void gn_apply_relu(GnSegs sg, const T* __restr
   const int g = (c4 * 4) / cpg;
   const float m = mean[seg * G + g], r = rstd[seg * G + g];
   const f32x4 ga = ((const f32x4*)gamma)[c4], be = ((const f32x4*)beta)[c4];
-  auto apply = [&](const f32x4 v, size_t i) {
+  auto apply = [&](const f32x4 v, int row) {
+    const size_t i = (size_t)row * C4 + c4;
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float t = (v[e] - m) * r * ga[e] + be[e];
+      const float t = gn_affine(v[e], m, r, ga[e], be[e]);
       o[e] = relu ? fmaxf(t, 0.f) : t;
     }
     st4(y, i, o);
@@ -657,15 +693,16 @@ __global__ __launch_bounds__(256) void gn_apply_relu(GnSegs sg, const T* __restr
       if ((threadIdx.x & 7) == 0) bits[i >> 3] = b;
     }
   };
+  // gn_walk_rows written out: through the helper the fp32 instantiation of this kernel takes 52 VGPRs instead of 50
   int row = r0 + rl;
-  for (; row + 3 * RL < r1; row += 4 * RL) {  // four independent row loads in flight per thread
+  for (; row + 3 * RL < r1; row += 4 * RL) {
     f32x4 v[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = ld4(x, (size_t)(row + u * RL) * C4 + c4);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) apply(v[u], (size_t)(row + u * RL) * C4 + c4);
+    for (int u = 0; u < 4; ++u) apply(v[u], row + u * RL);
   }
-  for (; row < r1; row += RL) apply(ld4(x, (size_t)row * C4 + c4), (size_t)row * C4 + c4);
+  for (; row < r1; row += RL) apply(ld4(x, (size_t)row * C4 + c4), row);
 }
 
 // backward stage 1: per (chunk, c): A = sum g*xhat, B = sum g   with g = dy * (y > 0)
@@ -683,42 +720,22 @@ __global__ __launch_bounds__(256) void gn_bwd_partial(GnSegs sg, const T* __rest
   const int g = (c4 * 4) / cpg;
   const float m = mean[seg * G + g], r = rstd[seg * G + g];
   f32x4 A = {0.f, 0.f, 0.f, 0.f}, B = {0.f, 0.f, 0.f, 0.f};
-  // ReLU mask: with beta given it is RECOMPUTED from x with the forward's exact expression (same sign as the stored y)
-  // instead of re-reading y - one tensor read less in each backward pass
-  const bool remask = relu && beta != nullptr;
+  const bool remask = relu && beta != nullptr;   // see gn_relu_mask
   f32x4 ga = {0.f, 0.f, 0.f, 0.f}, be = {0.f, 0.f, 0.f, 0.f};
   if (remask) { ga = ((const f32x4*)gamma)[c4]; be = ((const f32x4*)beta)[c4]; }
-  auto accumulate = [&](f32x4 gg, const f32x4 xx, size_t o) {
-    if (remask) {
+  gn_walk_rows(r0, r1, rl, RL,
+               [&](int row) {
+                 const size_t o = (size_t)row * C4 + c4;
+                 return GnGX{ld4(dy, o), ld4(x, o)};
+               },
+               [&](const GnGX v, int row) {
+                 const f32x4 gg = gn_relu_mask(v.g, v.x, m, r, ga, be, remask, relu, y, (size_t)row * C4 + c4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) gg[e] = ((xx[e] - m) * r * ga[e] + be[e]) > 0.f ? gg[e] : 0.f;
-    } else if (relu) {
-      const f32x4 yy = ld4(y, o);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      A[e] += gg[e] * ((xx[e] - m) * r);
-      B[e] += gg[e];
-    }
-  };
-  int row = r0 + rl;
-  for (; row + 3 * RL < r1; row += 4 * RL) {  // 8 independent loads in flight per thread, accumulated in row order
-    f32x4 gv[4], xv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t o = (size_t)(row + u * RL) * C4 + c4;
-      gv[u] = ld4(dy, o);
-      xv[u] = ld4(x, o);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) accumulate(gv[u], xv[u], (size_t)(row + u * RL) * C4 + c4);
-  }
-  for (; row < r1; row += RL) {
-    const size_t o = (size_t)row * C4 + c4;
-    accumulate(ld4(dy, o), ld4(x, o), o);
-  }
+                 for (int e = 0; e < 4; ++e) {
+                   A[e] += gg[e] * ((v.x[e] - m) * r);
+                   B[e] += gg[e];
+                 }
+               });
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     red[0][threadIdx.x * 4 + e] = A[e];
@@ -745,30 +762,12 @@ __global__ __launch_bounds__(256) void gn_bwd_partial(GnSegs sg, const T* __rest
 // Grid (segments, C / 64): a workgroup owns 64 channels (whole groups: cpg divides 64) of one segment, thread (channel, lane) walks
 // every 4th chunk with four loads in flight and the four lanes are combined in a fixed order - one block per segment with one walk per
 // channel was pure load latency (78 us per launch on the backward's critical path for 0.3 MB of partials).
-__global__ __launch_bounds__(256) void gn_bwd_reduce(GnSegs sg, const float* __restrict__ part, const float* __restrict__ gamma,
+// (the tail both stage-2 kernels end on: thread `lead` of channel c = blockIdx.y * 64 + cl holds that channel's segment sums sa = A, sb = B)
+__device__ __forceinline__ void gn_bwd_reduce_tail(bool lead, float sa, float sb, int seg, int c, int cl, const float* __restrict__ gamma,
                                                    float* __restrict__ AB, float* __restrict__ s12, int C, int G) {
-  __shared__ float ra[256], rb[256], sh[64][2];
-  const int seg = blockIdx.x, cl = threadIdx.x & 63, ln = threadIdx.x >> 6;
-  const int c = blockIdx.y * 64 + cl, cpg = C / G;
-  const int k0 = sg.chunk0[seg], k1 = sg.chunk0[seg + 1];
-  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    for (int k = k0 + ln; k < k1; k += 16) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (k + 4 * q < k1) {
-          const float2 v = *(const float2*)(part + ((size_t)(k + 4 * q) * C + c) * 2);
-          a[q] += v.x;
-          b[q] += v.y;
-        }
-    }
-  }
-  ra[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
-  rb[threadIdx.x] = (b[0] + b[1]) + (b[2] + b[3]);
-  __syncthreads();
-  if (ln == 0 && c < C) {
-    const float sa = (ra[cl] + ra[cl + 64]) + (ra[cl + 128] + ra[cl + 192]);
-    const float sb = (rb[cl] + rb[cl + 64]) + (rb[cl + 128] + rb[cl + 192]);
+  __shared__ float sh[64][2];
+  const int cpg = C / G;
+  if (lead) {
     AB[((size_t)seg * C + c) * 2] = sa;
     AB[((size_t)seg * C + c) * 2 + 1] = sb;
     sh[cl][0] = sa * gamma[c];
@@ -788,6 +787,36 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce(GnSegs sg, const float* __r
   }
 }
 
+__global__ __launch_bounds__(256) void gn_bwd_reduce(GnSegs sg, const float* __restrict__ part, const float* __restrict__ gamma,
+                                                   float* __restrict__ AB, float* __restrict__ s12, int C, int G) {
+  __shared__ float ra[256], rb[256];
+  const int seg = blockIdx.x, cl = threadIdx.x & 63, ln = threadIdx.x >> 6;
+  const int c = blockIdx.y * 64 + cl;
+  const int k0 = sg.chunk0[seg], k1 = sg.chunk0[seg + 1];
+  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < C) {
+    for (int k = k0 + ln; k < k1; k += 16) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (k + 4 * q < k1) {
+          const float2 v = *(const float2*)(part + ((size_t)(k + 4 * q) * C + c) * 2);
+          a[q] += v.x;
+          b[q] += v.y;
+        }
+    }
+  }
+  ra[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
+  rb[threadIdx.x] = (b[0] + b[1]) + (b[2] + b[3]);
+  __syncthreads();
+  const bool lead = ln == 0 && c < C;
+  float sa = 0.f, sb = 0.f;
+  if (lead) {
+    sa = (ra[cl] + ra[cl + 64]) + (ra[cl + 128] + ra[cl + 192]);
+    sb = (rb[cl] + rb[cl + 64]) + (rb[cl + 128] + rb[cl + 192]);
+  }
+  gn_bwd_reduce_tail(lead, sa, sb, seg, c, cl, gamma, AB, s12, C, G);
+}
+
 // The same from the dgrad epilogue's partials (common.h EpiBits::gnb_part: fp32 [ceil(rows / 64)][C][2] = {sum g, sum g * x} per 64-row
 // block and channel, g = dy * mask as stored in `g`): A = sum g * xhat = rstd * (sum g x - mean * sum g), B = sum g.  The 64-row blocks
 // that lie inside the segment come from part64; the rows in front of the first and behind the last whole block - segments start at
@@ -797,31 +826,27 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_p64(GnSegs sg, const float*
                                                        const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                        float* __restrict__ AB, float* __restrict__ s12, int C, int G) {
   __shared__ double r0s[256], r1s[256];
-  __shared__ float sh[64][2];
   const int seg = blockIdx.x, cl = threadIdx.x & 63, ln = threadIdx.x >> 6;
   const int c = blockIdx.y * 64 + cl, cpg = C / G;
   const int r0 = sg.row0[seg], r1 = sg.row0[seg + 1];
-  int b0 = (r0 + 63) >> 6, b1 = r1 >> 6;      // whole blocks [b0, b1)
-  if (b1 < b0) b1 = b0;                        // the segment lies inside one block
+  const GnSplit sp = gn_split(r0, r1, 6);
   double t0 = 0.0, t1 = 0.0;
   if (c < C) {
-    int k = b0 + ln;
-    for (; k + 12 < b1; k += 16) {   // four loads in flight per thread
+    int k = sp.b0 + ln;
+    for (; k + 12 < sp.b1; k += 16) {   // four loads in flight per thread
       float2 v[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = *(const float2*)(part64 + ((size_t)(k + 4 * q) * C + c) * 2);
 #pragma unroll
       for (int q = 0; q < 4; ++q) { t0 += (double)v[q].x; t1 += (double)v[q].y; }
     }
-    for (; k < b1; k += 4) {
+    for (; k < sp.b1; k += 4) {
       const float2 v = *(const float2*)(part64 + ((size_t)k * C + c) * 2);
       t0 += (double)v.x;
       t1 += (double)v.y;
     }
-    const int h1 = (b0 << 6) < r1 ? (b0 << 6) : r1;
-    const int e2 = (b1 << 6) > h1 ? (b1 << 6) : h1;
     for (int pass = 0; pass < 2; ++pass) {
-      const int e0 = pass == 0 ? r0 : e2, e1 = pass == 0 ? h1 : r1;
+      const int e0 = pass == 0 ? r0 : sp.t0, e1 = pass == 0 ? sp.h1 : r1;
       for (int r = e0 + ln; r < e1; r += 4) {
         const float gv = (float)gy[(size_t)r * C + c], xv = (float)x[(size_t)r * C + c];
         t0 += (double)gv;
@@ -832,29 +857,16 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_p64(GnSegs sg, const float*
   r0s[threadIdx.x] = t0;
   r1s[threadIdx.x] = t1;
   __syncthreads();
-  if (ln == 0 && c < C) {
+  const bool lead = ln == 0 && c < C;
+  float sa = 0.f, sb = 0.f;
+  if (lead) {
     const double S0 = (r0s[cl] + r0s[cl + 64]) + (r0s[cl + 128] + r0s[cl + 192]);
     const double S1 = (r1s[cl] + r1s[cl + 64]) + (r1s[cl + 128] + r1s[cl + 192]);
     const int g = c / cpg;
-    const float sa = (float)((double)rstd[seg * G + g] * (S1 - (double)mean[seg * G + g] * S0));
-    const float sb = (float)S0;
-    AB[((size_t)seg * C + c) * 2] = sa;
-    AB[((size_t)seg * C + c) * 2 + 1] = sb;
-    sh[cl][0] = sa * gamma[c];
-    sh[cl][1] = sb * gamma[c];
+    sa = (float)((double)rstd[seg * G + g] * (S1 - (double)mean[seg * G + g] * S0));
+    sb = (float)S0;
   }
-  __syncthreads();
-  const int gpb = 64 / cpg;   // groups per block
-  if ((int)threadIdx.x < gpb && blockIdx.y * 64 + threadIdx.x * cpg < C) {
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < cpg; ++k) {
-      s1 += sh[threadIdx.x * cpg + k][0];
-      s2 += sh[threadIdx.x * cpg + k][1];
-    }
-    const int g = blockIdx.y * gpb + threadIdx.x;
-    s12[(seg * G + g) * 2] = s1;
-    s12[(seg * G + g) * 2 + 1] = s2;
-  }
+  gn_bwd_reduce_tail(lead, sa, sb, seg, c, cl, gamma, AB, s12, C, G);
 }
 
 // dgamma / dbeta += sums of AB over the segments.  Runs as the prologue of the first cdiv(C, 64) workgroups of gn_bwd_apply: a launch of
@@ -905,19 +917,13 @@ __global__ __launch_bounds__(256) void gn_bwd_apply(GnSegs sg, const T* __restri
   f32x4 be = {0.f, 0.f, 0.f, 0.f};
   if (remask) be = ((const f32x4*)beta)[c4];
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};   // colpart: column sums of the rows this thread writes
-  auto apply = [&](f32x4 gg, const f32x4 xx, size_t i) {
-    if (remask) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) gg[e] = ((xx[e] - m) * r * ga[e] + be[e]) > 0.f ? gg[e] : 0.f;
-    } else if (relu) {
-      const f32x4 yy = ld4(y, i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-    }
+  auto apply = [&](const GnGX v, int row) {
+    const size_t i = (size_t)row * C4 + c4;
+    const f32x4 gg = gn_relu_mask(v.g, v.x, m, r, ga, be, remask, relu, y, i);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float xh = (xx[e] - m) * r;
+      const float xh = (v.x[e] - m) * r;
       o[e] = r * (gg[e] * ga[e] - (s2 + xh * s1) * inv_cnt);
     }
     st4(dx, i, o);
@@ -926,24 +932,12 @@ __global__ __launch_bounds__(256) void gn_bwd_apply(GnSegs sg, const T* __restri
       for (int e = 0; e < 4; ++e) csum[e] += (float)(T)o[e];   // the value as stored (rounded to T)
     }
   };
-  // 8 independent loads in flight per thread: inside the step this kernel shares the chip with the weight-gradient stream and gets a
-  // fraction of the CUs, so the bandwidth one CU sustains decides its time (324 us per launch in the step against ~100 alone)
-  int row = r0 + rl;
-  for (; row + 3 * RL < r1; row += 4 * RL) {
-    f32x4 gv[4], xv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t i = (size_t)(row + u * RL) * C4 + c4;
-      gv[u] = ld4(dy, i);
-      xv[u] = ld4(x, i);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) apply(gv[u], xv[u], (size_t)(row + u * RL) * C4 + c4);
-  }
-  for (; row < r1; row += RL) {
-    const size_t i = (size_t)row * C4 + c4;
-    apply(ld4(dy, i), ld4(x, i), i);
-  }
+  gn_walk_rows(r0, r1, rl, RL,
+               [&](int row) {
+                 const size_t i = (size_t)row * C4 + c4;
+                 return GnGX{ld4(dy, i), ld4(x, i)};
+               },
+               apply);
   if (colpart) {   // colpart[chunk][c] = column sums of this chunk of dx, row lanes combined in a fixed order
     __shared__ float cred[256 * 4];
 #pragma unroll
@@ -960,6 +954,13 @@ __global__ __launch_bounds__(256) void gn_bwd_apply(GnSegs sg, const T* __restri
 
 static const bool g_gn_reverse = [] { const char* v = getenv("UTV2_GN_REVERSE"); return !(v && v[0] == '0'); }();   // A/B switch, read once
 
+// chunks of nseg consecutive segments (a chunk never straddles a segment)
+static int64_t gn_chunks(int nseg, const int* seg_rows) {
+  int64_t c = 0;
+  for (int s = 0; s < nseg; ++s) c += (seg_rows[s] + GN_ROWS - 1) / GN_ROWS;
+  return c;
+}
+
 static int gn_fill(GnSegs& sg, int nseg, const int* seg_rows) {
   sg.nseg = nseg;
   sg.rev = g_gn_reverse ? 1 : 0;
@@ -968,10 +969,36 @@ static int gn_fill(GnSegs& sg, int nseg, const int* seg_rows) {
     sg.row0[s] = r;
     sg.chunk0[s] = c;
     r += seg_rows[s];
-    c += (seg_rows[s] + GN_ROWS - 1) / GN_ROWS;
+    c += (int)gn_chunks(1, seg_rows + s);
   }
   for (int s = nseg; s <= GN_MAX_SEG; ++s) { sg.row0[s] = r; sg.chunk0[s] = c; }
   return c;
+}
+
+static int gn_check(int nseg, int C, int G) {
+  return !(nseg < 1 || nseg > GN_MAX_SEG || G < 1 || C < 4 || (C & 3) || ((C / G) & 3) || C / 4 > 256 || (256 % (C / 4)) || (256 % G) || (C % G) || (64 % (C / G)));
+}
+
+// What every GroupNorm entry does with its segment arguments: checks them (gn_check; seg_rows_host given, no negative row count) and
+// fills sg.  -> the chunk count, or -1 for an argument error.
+static int gn_prepare(int nseg, const int* seg_rows_host, int C, int G, GnSegs& sg) {
+  if (!seg_rows_host || !gn_check(nseg, C, G)) return -1;
+  for (int s = 0; s < nseg; ++s)
+    if (seg_rows_host[s] < 0) return -1;
+  return gn_fill(sg, nseg, seg_rows_host);
+}
+
+// The backward's workspace, as offsets in floats: part [chunks][C][2] (gn_bwd_partial's sums), AB [nseg][C][2], s12 [nseg][G][2] (C
+// floats per segment are set aside for it).  utv2_groupnorm_seg_workspace_floats returns `floats`; the forward's part [chunks][G][2]
+// fits in it.
+struct GnBwdWs { int64_t part, AB, s12, floats; };
+static GnBwdWs gn_bwd_ws(int64_t chunks, int nseg, int C) {
+  GnBwdWs w;
+  w.part = 0;
+  w.AB = w.part + chunks * C * 2;
+  w.s12 = w.AB + (int64_t)nseg * C * 2;
+  w.floats = w.s12 + (int64_t)nseg * C;
+  return w;
 }
 
 static inline int grid_for(size_t n, int block = 256, int cap = 256 * 16) {
@@ -981,45 +1008,23 @@ static inline int grid_for(size_t n, int block = 256, int cap = 256 * 16) {
   return (int)b;
 }
 
-template <typename T>
-static void gn_fwd_launch(const GnSegs& sg, int chunks, int nseg, const void* x, const float* gamma, const float* beta, void* y,
-                          float* mean, float* rstd, float* ws, int C, int G, float eps, int relu, hipStream_t stream) {
-  hipLaunchKernelGGL(gn_stats_partial<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)x, ws, C, G);
-  hipLaunchKernelGGL(gn_stats_final, dim3(nseg), dim3(256), 0, stream, sg, (const float*)ws, mean, rstd, G, C / G, eps);
-  hipLaunchKernelGGL(gn_apply_relu<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)x, (const float*)mean, (const float*)rstd,
-                     gamma, beta, (T*)y, C, G, relu);
-}
+static inline bool is_act_dtype(int dtype) { return dtype == UTV2_F32 || dtype == UTV2_BF16; }
 
+// stage 3 of both backward entries: dx, and dgamma / dbeta in the first cdiv(C, 64) workgroups (a workgroup past the last chunk finds no rows)
 template <typename T>
-static void gn_bwd_launch(const GnSegs& sg, int chunks, int nseg, const void* dy, const void* y, const void* x, const float* mean,
-                          const float* rstd, const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta,
-                          float* ws, int C, int G, int relu, float* colpart, hipStream_t stream) {
-  float* part = ws;
-  float* AB = ws + (size_t)chunks * C * 2;
-  float* s12 = AB + (size_t)nseg * C * 2;
-  hipLaunchKernelGGL(gn_bwd_partial<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)dy, (const T*)y, (const T*)x, mean, rstd,
-                     gamma, beta, part, C, G, relu);
-  hipLaunchKernelGGL(gn_bwd_reduce, dim3(nseg, cdiv(C, 64)), dim3(256), 0, stream, sg, (const float*)part, gamma, AB, s12, C, G);
-  const int pb = cdiv(C, 64);   // workgroups that also run gn_bwd_param (a workgroup past the last chunk finds no rows)
+static void gn_bwd_apply_launch(const GnSegs& sg, int chunks, const void* dy, const void* y, const void* x, const float* mean,
+                                const float* rstd, const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta,
+                                const float* AB, const float* s12, int C, int G, int relu, float* colpart, hipStream_t stream) {
+  const int pb = cdiv(C, 64);
   hipLaunchKernelGGL(gn_bwd_apply<T>, dim3(chunks > pb ? chunks : pb), dim3(256), 0, stream, sg, (const T*)dy, (const T*)y, (const T*)x, mean,
-                     rstd, gamma, beta, (const float*)s12, (T*)dx, C, G, relu, (const float*)AB, dgamma, dbeta, pb, colpart);
+                     rstd, gamma, beta, s12, (T*)dx, C, G, relu, AB, dgamma, dbeta, pb, colpart);
 }
 
 extern "C" {
 
-int utv2_ema_axpby(float* teacher, const float* student, int64_t n, double keep_rate, hipStream_t stream) {
+// mirror16 (optional, 8-byte aligned): mirror16[i] = the library's 16-bit rounding of the new teacher[i]
+int utv2_ema_axpby(float* teacher, const float* student, void* mirror16, int64_t n, double keep_rate, hipStream_t stream) {
   if (!teacher || !student || n < 0) return UTV2_EARG;
-  if (n == 0) return UTV2_OK;
-  if (((uintptr_t)teacher | (uintptr_t)student) & 15) return UTV2_EARG;
-  const float a = (float)(1.0 - keep_rate), b = (float)keep_rate;
-  hipLaunchKernelGGL(ema_axpby_f32, dim3(grid_for((size_t)n / 4)), dim3(256), 0, stream, teacher, student, (size_t)n / 4,
-                     (size_t)n, a, b, (h16_t*)nullptr);
-  return utv2_launch_status();
-}
-
-// the same + mirror16[i] = the library's 16-bit rounding of the new teacher[i] (8-byte aligned)
-int utv2_ema_axpby_m16(float* teacher, const float* student, void* mirror16, int64_t n, double keep_rate, hipStream_t stream) {
-  if (!teacher || !student || !mirror16 || n < 0) return UTV2_EARG;
   if (n == 0) return UTV2_OK;
   if ((((uintptr_t)teacher | (uintptr_t)student) & 15) || ((uintptr_t)mirror16 & 7)) return UTV2_EARG;
   const float a = (float)(1.0 - keep_rate), b = (float)keep_rate;
@@ -1028,31 +1033,13 @@ int utv2_ema_axpby_m16(float* teacher, const float* student, void* mirror16, int
   return utv2_launch_status();
 }
 
-int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, int64_t n, float lr, float momentum, float weight_decay,
+// mirror16 (optional; here and in utv2_sgd_momentum_amp): mirror16[i] = the library's 16-bit rounding of the new param[i]
+int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum, float weight_decay,
                       float grad_scale, int zero_grad, hipStream_t stream) {
   if (!param || !grad || !mom_buf || n < 0) return UTV2_EARG;
   if (n == 0) return UTV2_OK;
   hipLaunchKernelGGL(sgd_momentum_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr,
-                     momentum, weight_decay, grad_scale, zero_grad, (h16_t*)nullptr);
-  return utv2_launch_status();
-}
-
-// utv2_sgd_momentum / utv2_sgd_momentum_amp that also write mirror16[i] = the library's 16-bit rounding of the new param[i]
-int utv2_sgd_momentum_m16(float* param, float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum, float weight_decay,
-                          float grad_scale, int zero_grad, hipStream_t stream) {
-  if (!param || !grad || !mom_buf || !mirror16 || n < 0) return UTV2_EARG;
-  if (n == 0) return UTV2_OK;
-  hipLaunchKernelGGL(sgd_momentum_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr,
                      momentum, weight_decay, grad_scale, zero_grad, (h16_t*)mirror16);
-  return utv2_launch_status();
-}
-
-int utv2_sgd_momentum_amp_m16(float* param, const float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum,
-                              float weight_decay, float grad_scale, const float* state, hipStream_t stream) {
-  if (!param || !grad || !mom_buf || !mirror16 || !state || n < 0) return UTV2_EARG;
-  if (n == 0) return UTV2_OK;
-  hipLaunchKernelGGL(sgd_momentum_amp_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr, momentum,
-                     weight_decay, grad_scale, state, (h16_t*)mirror16);
   return utv2_launch_status();
 }
 
@@ -1064,12 +1051,12 @@ int utv2_amp_found_inf(const float* grad, int64_t n, float* state, hipStream_t s
   return utv2_launch_status();
 }
 
-int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, int64_t n, float lr, float momentum, float weight_decay,
-                          float grad_scale, const float* state, hipStream_t stream) {
+int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum,
+                          float weight_decay, float grad_scale, const float* state, hipStream_t stream) {
   if (!param || !grad || !mom_buf || !state || n < 0) return UTV2_EARG;
   if (n == 0) return UTV2_OK;
   hipLaunchKernelGGL(sgd_momentum_amp_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr, momentum,
-                     weight_decay, grad_scale, state, (h16_t*)nullptr);
+                     weight_decay, grad_scale, state, (h16_t*)mirror16);
   return utv2_launch_status();
 }
 
@@ -1082,15 +1069,13 @@ int utv2_amp_update_scale(float* state, float growth_factor, float backoff_facto
 // out[M][C] = (y? relu-mask by y : 1) * dy * (scale? scale[c] : 1).  C % 4 == 0.  dy / y / out are `dtype`.
 int utv2_relu_bwd_scale(const void* dy, const void* y, const float* scale, void* out, int64_t M, int C, int dtype,
                         hipStream_t stream) {
-  if (!dy || !out || (C & 3) || (dtype != UTV2_F32 && dtype != UTV2_BF16)) return UTV2_EARG;
+  if (!dy || !out || (C & 3) || !is_act_dtype(dtype)) return UTV2_EARG;
   const size_t n4 = (size_t)M * C / 4;
   if (n4 == 0) return UTV2_OK;
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL(relu_bwd_scale_k<h16_t>, dim3(grid_for(n4)), dim3(256), 0, stream, (const h16_t*)dy, (const h16_t*)y,
-                       scale, (h16_t*)out, n4, C / 4);
-  else
-    hipLaunchKernelGGL(relu_bwd_scale_k<float>, dim3(grid_for(n4)), dim3(256), 0, stream, (const float*)dy, (const float*)y,
-                       scale, (float*)out, n4, C / 4);
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(relu_bwd_scale_k<T>, dim3(grid_for(n4)), dim3(256), 0, stream, (const T*)dy, (const T*)y, scale, (T*)out, n4, C / 4);
+  });
   return utv2_launch_status();
 }
 
@@ -1106,78 +1091,68 @@ int utv2_add(const float* a, const float* b, float* out, int64_t n, hipStream_t 
 // (x_dtype), dpool / dx: g_dtype.
 int utv2_maxpool3x3s2_bwd_nhwc(const void* x, int x_dtype, const void* dpool, void* dx, int g_dtype, int N, int H, int W, int C, int OH,
                                int OW, int relu, hipStream_t stream) {
-  if (!x || !dpool || !dx || (C & 3)) return UTV2_EARG;
+  if (!x || !dpool || !dx || (C & 3) || !is_act_dtype(x_dtype) || !is_act_dtype(g_dtype)) return UTV2_EARG;
+  if (x_dtype == UTV2_F32 && g_dtype == UTV2_BF16) return UTV2_EARG;   // no 16-bit gradient of an fp32 pool
   const dim3 g(grid_for((size_t)N * H * W * C / 4, 256, 1 << 16)), b(256);
-  if (x_dtype == UTV2_F32 && g_dtype == UTV2_F32)
-    hipLaunchKernelGGL((maxpool3x3s2_bwd_nhwc_k<float, float>), g, b, 0, stream, (const float*)x, (const float*)dpool, (float*)dx, N, H, W, C / 4, OH, OW, relu);
-  else if (x_dtype == UTV2_BF16 && g_dtype == UTV2_BF16)
-    hipLaunchKernelGGL((maxpool3x3s2_bwd_nhwc_k<h16_t, h16_t>), g, b, 0, stream, (const h16_t*)x, (const h16_t*)dpool, (h16_t*)dx, N, H, W, C / 4, OH, OW, relu);
-  else if (x_dtype == UTV2_BF16 && g_dtype == UTV2_F32)
-    hipLaunchKernelGGL((maxpool3x3s2_bwd_nhwc_k<h16_t, float>), g, b, 0, stream, (const h16_t*)x, (const float*)dpool, (float*)dx, N, H, W, C / 4, OH, OW, relu);
-  else
-    return UTV2_EARG;
+  with_types(x_dtype, g_dtype, [&](auto tx, auto tg) {
+    using TX = TAG_T(tx);
+    using TG = TAG_T(tg);
+    if constexpr (sizeof(TX) <= sizeof(TG))   // (the pair refused above is not instantiated)
+      hipLaunchKernelGGL((maxpool3x3s2_bwd_nhwc_k<TX, TG>), g, b, 0, stream, (const TX*)x, (const TG*)dpool, (TG*)dx, N, H, W, C / 4, OH, OW, relu);
+  });
   return utv2_launch_status();
 }
 
 int utv2_maxpool3x3s2_nhwc(const void* x, int x_dtype, void* y, int y_dtype, int N, int H, int W, int C, int OH, int OW,
                            hipStream_t stream) {
-  if (!x || !y || (C & 3)) return UTV2_EARG;
+  if (!x || !y || (C & 3) || !is_act_dtype(x_dtype) || !is_act_dtype(y_dtype)) return UTV2_EARG;
+  if (x_dtype == UTV2_BF16 && y_dtype == UTV2_F32) return UTV2_EARG;   // no fp32 pool of a 16-bit tensor
   const dim3 g(grid_for((size_t)N * OH * OW * C / 4, 256, 1 << 16)), b(256);
-  if (x_dtype == UTV2_F32 && y_dtype == UTV2_F32)
-    hipLaunchKernelGGL((maxpool3x3s2_nhwc_k<float, float>), g, b, 0, stream, (const float*)x, (float*)y, N, H, W, C / 4, OH, OW);
-  else if (x_dtype == UTV2_F32 && y_dtype == UTV2_BF16)
-    hipLaunchKernelGGL((maxpool3x3s2_nhwc_k<float, h16_t>), g, b, 0, stream, (const float*)x, (h16_t*)y, N, H, W, C / 4, OH, OW);
-  else if (x_dtype == UTV2_BF16 && y_dtype == UTV2_BF16 && (C & 7) == 0 && (size_t)N * OH * OW * C / 8 < (1ull << 31) &&
-           (size_t)N * H * W < (1ull << 31))
+  if (x_dtype == UTV2_BF16 && y_dtype == UTV2_BF16 && (C & 7) == 0 && (size_t)N * OH * OW * C / 8 < (1ull << 31) &&
+      (size_t)N * H * W < (1ull << 31))
     hipLaunchKernelGGL(maxpool3x3s2_nhwc_bf16x8_k, dim3(grid_for((size_t)N * OH * OW * C / 8, 256, 1 << 16)), b, 0, stream,
                        (const h16_t*)x, (h16_t*)y, N, H, W, C / 8, OH, OW);
-  else if (x_dtype == UTV2_BF16 && y_dtype == UTV2_BF16)
-    hipLaunchKernelGGL((maxpool3x3s2_nhwc_k<h16_t, h16_t>), g, b, 0, stream, (const h16_t*)x, (h16_t*)y, N, H, W, C / 4, OH, OW);
   else
-    return UTV2_EARG;
+    with_types(x_dtype, y_dtype, [&](auto ti, auto to) {
+      using TI = TAG_T(ti);
+      using TO = TAG_T(to);
+      if constexpr (sizeof(TI) >= sizeof(TO))   // (the pair refused above is not instantiated)
+        hipLaunchKernelGGL((maxpool3x3s2_nhwc_k<TI, TO>), g, b, 0, stream, (const TI*)x, (TO*)y, N, H, W, C / 4, OH, OW);
+    });
   return utv2_launch_status();
 }
 
 int utv2_upsample2x_add_nhwc(const void* lateral, const void* top, void* out, int N, int H, int W, int C, int dtype,
                              hipStream_t stream) {
-  if (!lateral || !top || !out || (C & 3) || (H & 1) || (W & 1)) return UTV2_EARG;
+  if (!lateral || !top || !out || (C & 3) || (H & 1) || (W & 1) || !is_act_dtype(dtype)) return UTV2_EARG;
   const dim3 g(grid_for((size_t)N * H * W * C / 4, 256, 1 << 16)), b(256);
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL(upsample2x_add_nhwc_k<h16_t>, g, b, 0, stream, (const h16_t*)lateral, (const h16_t*)top, (h16_t*)out, N,
-                       H, W, C / 4);
-  else if (dtype == UTV2_F32)
-    hipLaunchKernelGGL(upsample2x_add_nhwc_k<float>, g, b, 0, stream, (const float*)lateral, (const float*)top, (float*)out, N, H,
-                       W, C / 4);
-  else
-    return UTV2_EARG;
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(upsample2x_add_nhwc_k<T>, g, b, 0, stream, (const T*)lateral, (const T*)top, (T*)out, N, H, W, C / 4);
+  });
   return utv2_launch_status();
 }
 
 int utv2_downsample2x_sum_nhwc(const void* g, void* dtop, int N, int TH, int TW, int C, int accumulate, int dtype,
                                hipStream_t stream) {
-  if (!g || !dtop || (C & 3)) return UTV2_EARG;
+  if (!g || !dtop || (C & 3) || !is_act_dtype(dtype)) return UTV2_EARG;
   const dim3 gr(grid_for((size_t)N * TH * TW * C / 4, 256, 1 << 16)), b(256);
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL(downsample2x_sum_nhwc_k<h16_t>, gr, b, 0, stream, (const h16_t*)g, (h16_t*)dtop, N, TH, TW, C / 4,
-                       accumulate);
-  else if (dtype == UTV2_F32)
-    hipLaunchKernelGGL(downsample2x_sum_nhwc_k<float>, gr, b, 0, stream, (const float*)g, (float*)dtop, N, TH, TW, C / 4, accumulate);
-  else
-    return UTV2_EARG;
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(downsample2x_sum_nhwc_k<T>, gr, b, 0, stream, (const T*)g, (T*)dtop, N, TH, TW, C / 4, accumulate);
+  });
   return utv2_launch_status();
 }
 
 // dst[n,2i,2j,:] = src[n,i,j,:], zero elsewhere.  TH = (H+1)/2, TW = (W+1)/2.
 int utv2_zero_interleave2x_nhwc(const void* src, const void* mask, void* dst, int N, int H, int W, int C, int dtype, hipStream_t stream) {
-  if (!src || !dst || (C & 3)) return UTV2_EARG;
+  if (!src || !dst || (C & 3) || !is_act_dtype(dtype)) return UTV2_EARG;
   const int TH = (H + 1) / 2, TW = (W + 1) / 2;
   const dim3 g(grid_for((size_t)N * H * W * C / 4, 256, 1 << 16)), b(256);
-  if (dtype == UTV2_BF16)
-    hipLaunchKernelGGL(zero_interleave2x_nhwc_k<h16_t>, g, b, 0, stream, (const h16_t*)src, (const h16_t*)mask, (h16_t*)dst, N, H, W, TH, TW, C / 4);
-  else if (dtype == UTV2_F32)
-    hipLaunchKernelGGL(zero_interleave2x_nhwc_k<float>, g, b, 0, stream, (const float*)src, (const float*)mask, (float*)dst, N, H, W, TH, TW, C / 4);
-  else
-    return UTV2_EARG;
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(zero_interleave2x_nhwc_k<T>, g, b, 0, stream, (const T*)src, (const T*)mask, (T*)dst, N, H, W, TH, TW, C / 4);
+  });
   return utv2_launch_status();
 }
 
@@ -1257,24 +1232,25 @@ int utv2_frozenbn_fold(const float* w, const float* b, const float* mean, const 
 
 // Segmented API: seg_rows_host = host int[nseg] (rows of each (image, level) segment, consecutive in memory).
 int64_t utv2_groupnorm_seg_workspace_floats(int nseg, const int* seg_rows_host, int C) {
-  int64_t chunks = 0;
-  for (int s = 0; s < nseg; ++s) chunks += (seg_rows_host[s] + GN_ROWS - 1) / GN_ROWS;
-  return chunks * C * 2 + (int64_t)nseg * C * 2 + (int64_t)nseg * C;
+  return gn_bwd_ws(gn_chunks(nseg, seg_rows_host), nseg, C).floats;
 }
 
-static int gn_check(int nseg, int C, int G) {
-  return !(nseg < 1 || nseg > GN_MAX_SEG || (C & 3) || ((C / G) & 3) || C / 4 > 256 || (256 % (C / 4)) || (256 % G) || (C % G) || (64 % (C / G)));
-}
+int64_t utv2_groupnorm_seg_chunks(int nseg, const int* seg_rows_host) { return gn_chunks(nseg, seg_rows_host); }
 
 // x,y: [rows][C] of `dtype`; mean,rstd: fp32 [nseg][G] (saved for backward).  Statistics and arithmetic are fp32.
 int utv2_groupnorm_relu_seg_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                 float* ws, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu, int dtype,
                                 hipStream_t stream) {
-  if (!x || !y || !mean || !rstd || !ws || !gn_check(nseg, C, G) || (dtype != UTV2_F32 && dtype != UTV2_BF16)) return UTV2_EARG;
   GnSegs sg;
-  const int chunks = gn_fill(sg, nseg, seg_rows_host);
-  if (dtype == UTV2_BF16) gn_fwd_launch<h16_t>(sg, chunks, nseg, x, gamma, beta, y, mean, rstd, ws, C, G, eps, relu, stream);
-  else gn_fwd_launch<float>(sg, chunks, nseg, x, gamma, beta, y, mean, rstd, ws, C, G, eps, relu, stream);
+  const int chunks = gn_prepare(nseg, seg_rows_host, C, G, sg);
+  if (!x || !y || !mean || !rstd || !ws || chunks < 0 || !is_act_dtype(dtype)) return UTV2_EARG;
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(gn_stats_partial<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)x, ws, C, G);
+    hipLaunchKernelGGL(gn_stats_final, dim3(nseg), dim3(256), 0, stream, sg, (const float*)ws, mean, rstd, G, C / G, eps);
+    hipLaunchKernelGGL(gn_apply_relu<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)x, (const float*)mean, (const float*)rstd,
+                       gamma, beta, (T*)y, C, G, relu);
+  });
   return utv2_launch_status();
 }
 
@@ -1283,98 +1259,57 @@ int utv2_groupnorm_relu_seg_fwd(const void* x, const float* gamma, const float* 
 // pass less than utv2_groupnorm_relu_seg_fwd.
 // relu_bits (optional; C % 32 == 0): [rows * C / 8] bytes, bit (row * C + c) = y > 0 in fp32 (before the 16-bit rounding; the mask
 // utv2_groupnorm_relu_seg_bwd recomputes from x when it is given beta) - the plane utv2_conv2d_ml_fwd_bf16_gnb reads
-int utv2_groupnorm_relu_seg_fwd_p32b(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                     const float* part32, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu,
-                                     void* relu_bits, hipStream_t stream) {
-  if (!x || !y || !mean || !rstd || !part32 || !gn_check(nseg, C, G) || C != 8 * G || (relu_bits && (C & 31))) return UTV2_EARG;
+int utv2_groupnorm_relu_seg_fwd_p32(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                    const float* part32, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu,
+                                    void* relu_bits, hipStream_t stream) {
   GnSegs sg;
-  const int chunks = gn_fill(sg, nseg, seg_rows_host);
+  const int chunks = gn_prepare(nseg, seg_rows_host, C, G, sg);
+  if (!x || !y || !mean || !rstd || !part32 || chunks < 0 || C != 8 * G || (relu_bits && (C & 31))) return UTV2_EARG;
   hipLaunchKernelGGL(gn_stats_final_p32, dim3(nseg, cdiv(G, 8)), dim3(256), 0, stream, sg, part32, (const h16_t*)x, mean, rstd, G, C, eps);
   hipLaunchKernelGGL(gn_apply_relu<h16_t>, dim3(chunks), dim3(256), 0, stream, sg, (const h16_t*)x, (const float*)mean, (const float*)rstd,
                      gamma, beta, (h16_t*)y, C, G, relu, (unsigned*)relu_bits);
   return utv2_launch_status();
 }
 
-int utv2_groupnorm_relu_seg_fwd_p32(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                    const float* part32, int nseg, const int* seg_rows_host, int C, int G, float eps, int relu,
-                                    hipStream_t stream) {
-  return utv2_groupnorm_relu_seg_fwd_p32b(x, gamma, beta, y, mean, rstd, part32, nseg, seg_rows_host, C, G, eps, relu, nullptr, stream);
+// dx written (`dtype`, like dy / y / x); dgamma/dbeta (fp32) accumulated (+=).  The ReLU mask comes from y, or - when
+// beta is given - is recomputed from x (y may then be null).
+// colsum_part (optional, fp32 [utv2_groupnorm_seg_chunks()][C]): per-chunk column sums of dx as stored - the partial sums of the bias
+// gradient of the convolution that produced x (its dY is this dx), for free while dx is in registers.
+int utv2_groupnorm_relu_seg_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
+                                const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
+                                int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, float* colsum_part,
+                                hipStream_t stream) {
+  GnSegs sg;
+  const int chunks = gn_prepare(nseg, seg_rows_host, C, G, sg);
+  if (!dy || !x || !dx || !ws || chunks < 0 || !is_act_dtype(dtype) || (relu && !y && !beta)) return UTV2_EARG;
+  const GnBwdWs w = gn_bwd_ws(chunks, nseg, C);
+  with_type(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(gn_bwd_partial<T>, dim3(chunks), dim3(256), 0, stream, sg, (const T*)dy, (const T*)y, (const T*)x, mean, rstd,
+                       gamma, beta, ws + w.part, C, G, relu);
+    hipLaunchKernelGGL(gn_bwd_reduce, dim3(nseg, cdiv(C, 64)), dim3(256), 0, stream, sg, (const float*)(ws + w.part), gamma, ws + w.AB,
+                       ws + w.s12, C, G);
+    gn_bwd_apply_launch<T>(sg, chunks, dy, y, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, ws + w.AB, ws + w.s12, C, G, relu,
+                           colsum_part, stream);
+  });
+  return utv2_launch_status();
 }
 
 // GroupNorm (+ ReLU) backward whose first reduction the producing dgrad's epilogue already made (utv2_conv2d_ml_fwd_bf16_gnb): g = the
 // gradient with the ReLU mask applied (16-bit [rows][C]), part64 = that conv's gnb_part.  Two launches (segment sums; apply) instead of
-// three, and one pass over g and x instead of two.  Outputs as utv2_groupnorm_relu_seg_bwd_colsum; ws: utv2_groupnorm_seg_workspace_floats.
+// three, and one pass over g and x instead of two.  Outputs and ws as utv2_groupnorm_relu_seg_bwd (the `part` range of ws stays unused).
 int utv2_groupnorm_seg_bwd_p64(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,
                                float* dgamma, float* dbeta, float* ws, int nseg, const int* seg_rows_host, int C, int G,
                                const float* part64, float* colsum_part, hipStream_t stream) {
-  if (!g || !x || !dx || !ws || !part64 || !mean || !rstd || !gamma || !gn_check(nseg, C, G)) return UTV2_EARG;
   GnSegs sg;
-  const int chunks = gn_fill(sg, nseg, seg_rows_host);
-  float* AB = ws;
-  float* s12 = AB + (size_t)nseg * C * 2;
+  const int chunks = gn_prepare(nseg, seg_rows_host, C, G, sg);
+  if (!g || !x || !dx || !ws || !part64 || !mean || !rstd || !gamma || chunks < 0) return UTV2_EARG;
+  const GnBwdWs w = gn_bwd_ws(chunks, nseg, C);
   hipLaunchKernelGGL(gn_bwd_reduce_p64, dim3(nseg, cdiv(C, 64)), dim3(256), 0, stream, sg, part64, (const h16_t*)g, (const h16_t*)x, mean,
-                     rstd, gamma, AB, s12, C, G);
-  const int pb = cdiv(C, 64);
-  hipLaunchKernelGGL(gn_bwd_apply<h16_t>, dim3(chunks > pb ? chunks : pb), dim3(256), 0, stream, sg, (const h16_t*)g, (const h16_t*)nullptr,
-                     (const h16_t*)x, mean, rstd, gamma, (const float*)nullptr, (const float*)s12, (h16_t*)dx, C, G, 0, (const float*)AB, dgamma,
-                     dbeta, pb, colsum_part);
+                     rstd, gamma, ws + w.AB, ws + w.s12, C, G);
+  gn_bwd_apply_launch<h16_t>(sg, chunks, g, nullptr, x, mean, rstd, gamma, nullptr, dx, dgamma, dbeta, ws + w.AB, ws + w.s12, C, G, 0,
+                             colsum_part, stream);
   return utv2_launch_status();
-}
-
-// dx written (`dtype`, like dy / y / x); dgamma/dbeta (fp32) accumulated (+=).  The ReLU mask comes from y, or - when
-// beta is given - is recomputed from x (y may then be null).
-int64_t utv2_groupnorm_seg_chunks(int nseg, const int* seg_rows_host) {
-  int64_t chunks = 0;
-  for (int s = 0; s < nseg; ++s) chunks += (seg_rows_host[s] + GN_ROWS - 1) / GN_ROWS;
-  return chunks;
-}
-
-// colsum_part (optional, fp32 [utv2_groupnorm_seg_chunks()][C]): per-chunk column sums of dx as stored - the partial sums of the bias
-// gradient of the convolution that produced x (its dY is this dx), for free while dx is in registers.
-int utv2_groupnorm_relu_seg_bwd_colsum(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                       const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
-                                       int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, float* colsum_part,
-                                       hipStream_t stream) {
-  if (!dy || !x || !dx || !ws || !gn_check(nseg, C, G) || (dtype != UTV2_F32 && dtype != UTV2_BF16) || (relu && !y && !beta))
-    return UTV2_EARG;
-  GnSegs sg;
-  const int chunks = gn_fill(sg, nseg, seg_rows_host);
-  if (dtype == UTV2_BF16)
-    gn_bwd_launch<h16_t>(sg, chunks, nseg, dy, y, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, ws, C, G, relu, colsum_part, stream);
-  else gn_bwd_launch<float>(sg, chunks, nseg, dy, y, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, ws, C, G, relu, colsum_part, stream);
-  return utv2_launch_status();
-}
-
-int utv2_groupnorm_relu_seg_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws,
-                                int nseg, const int* seg_rows_host, int C, int G, int relu, int dtype, hipStream_t stream) {
-  return utv2_groupnorm_relu_seg_bwd_colsum(dy, y, x, mean, rstd, gamma, beta, dx, dgamma, dbeta, ws, nseg, seg_rows_host, C, G, relu, dtype,
-                                            nullptr, stream);
-}
-
-// Dense [N][HW][C] convenience forms (one segment per image).
-int64_t utv2_groupnorm_workspace_floats(int N, int HW, int C) {
-  int rows[GN_MAX_SEG];
-  if (N > GN_MAX_SEG) return -1;
-  for (int i = 0; i < N; ++i) rows[i] = HW;
-  return utv2_groupnorm_seg_workspace_floats(N, rows, C);
-}
-
-int utv2_groupnorm_relu_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
-                            float* ws, int N, int HW, int C, int G, float eps, int relu, hipStream_t stream) {
-  int rows[GN_MAX_SEG];
-  if (N > GN_MAX_SEG) return UTV2_EARG;
-  for (int i = 0; i < N; ++i) rows[i] = HW;
-  return utv2_groupnorm_relu_seg_fwd(x, gamma, beta, y, mean, rstd, ws, N, rows, C, G, eps, relu, UTV2_F32, stream);
-}
-
-int utv2_groupnorm_relu_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd,
-                            const float* gamma, float* dx, float* dgamma, float* dbeta, float* ws, int N, int HW, int C,
-                            int G, int relu, hipStream_t stream) {
-  int rows[GN_MAX_SEG];
-  if (N > GN_MAX_SEG) return UTV2_EARG;
-  for (int i = 0; i < N; ++i) rows[i] = HW;
-  return utv2_groupnorm_relu_seg_bwd(dy, y, x, mean, rstd, gamma, nullptr, dx, dgamma, dbeta, ws, N, rows, C, G, relu, UTV2_F32, stream);
 }
 
 }  // extern "C"

@@ -72,7 +72,7 @@ def _parse_header(path):
 
 
 _SIGS = _parse_header(HEADER_PATH)
-_PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats", "utv2_groupnorm_workspace_floats",
+_PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats",
           "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
           "utv2_coco_eval_workspace_bytes", "utv2_gconv3x3_supported", "utv2_gconv3x3_wgrad_splits",
           "utv2_gconv3x3_wgrad_workspace_floats"}  # return a value, not a status
@@ -268,20 +268,13 @@ def conv_clock_probe():
 def ema_axpby(teacher_flat, student_flat, keep_rate, mirror16=None):
     """mirror16 (optional, the library's 16-bit type, same length): also receives the 16-bit rounding of the new teacher values"""
     assert teacher_flat.numel() == student_flat.numel()
-    if mirror16 is not None:
-        assert mirror16.dtype == h16_dtype() and mirror16.numel() == teacher_flat.numel()
-        call("utv2_ema_axpby_m16", _p(teacher_flat), _p(student_flat), _p(mirror16), teacher_flat.numel(), float(keep_rate), _stream())
-        return
-    call("utv2_ema_axpby", _p(teacher_flat), _p(student_flat), teacher_flat.numel(), float(keep_rate), _stream())
+    assert mirror16 is None or (mirror16.dtype == h16_dtype() and mirror16.numel() == teacher_flat.numel())
+    call("utv2_ema_axpby", _p(teacher_flat), _p(student_flat), _p(mirror16), teacher_flat.numel(), float(keep_rate), _stream())
 
 
 def sgd_momentum(param, grad, mom, lr, momentum, weight_decay, grad_scale=1.0, zero_grad=True, mirror16=None):
-    if mirror16 is not None:
-        assert mirror16.dtype == h16_dtype() and mirror16.numel() == param.numel()
-        call("utv2_sgd_momentum_m16", _p(param), _p(grad), _p(mom), _p(mirror16), param.numel(), float(lr), float(momentum),
-             float(weight_decay), float(grad_scale), int(zero_grad), _stream())
-        return
-    call("utv2_sgd_momentum", _p(param), _p(grad), _p(mom), param.numel(), float(lr), float(momentum),
+    assert mirror16 is None or (mirror16.dtype == h16_dtype() and mirror16.numel() == param.numel())
+    call("utv2_sgd_momentum", _p(param), _p(grad), _p(mom), _p(mirror16), param.numel(), float(lr), float(momentum),
          float(weight_decay), float(grad_scale), int(zero_grad), _stream())
 
 
@@ -290,12 +283,8 @@ def amp_found_inf(grad, state):
 
 
 def sgd_momentum_amp(param, grad, mom, lr, momentum, weight_decay, grad_scale, state, mirror16=None):
-    if mirror16 is not None:
-        assert mirror16.dtype == h16_dtype() and mirror16.numel() == param.numel()
-        call("utv2_sgd_momentum_amp_m16", _p(param), _p(grad), _p(mom), _p(mirror16), param.numel(), float(lr), float(momentum),
-             float(weight_decay), float(grad_scale), _p(state), _stream())
-        return
-    call("utv2_sgd_momentum_amp", _p(param), _p(grad), _p(mom), param.numel(), float(lr), float(momentum), float(weight_decay),
+    assert mirror16 is None or (mirror16.dtype == h16_dtype() and mirror16.numel() == param.numel())
+    call("utv2_sgd_momentum_amp", _p(param), _p(grad), _p(mom), _p(mirror16), param.numel(), float(lr), float(momentum), float(weight_decay),
          float(grad_scale), _p(state), _stream())
 
 
@@ -458,26 +447,17 @@ def frozenbn_fold(w, b, mean, var, scale, shift, eps=1e-5):
     call("utv2_frozenbn_fold", _p(w), _p(b), _p(mean), _p(var), _p(scale), _p(shift), w.numel(), float(eps), _stream())
 
 
-def groupnorm_relu_fwd(x, gamma, beta, G=32, eps=1e-5, relu=True, out=None):
+def groupnorm_relu_fwd(x, gamma, beta, G=32, eps=1e-5, relu=True):
+    """dense [N,H,W,C]: one segment per image"""
     N, H, W, C = x.shape
-    HW = H * W
-    y = torch.empty_like(x) if out is None else out
-    mean = torch.empty((N, G), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((N, G), dtype=torch.float32, device=x.device)
-    ws = workspace(load().utv2_groupnorm_workspace_floats(N, HW, C), x.device, "gn")
-    call("utv2_groupnorm_relu_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(ws), N, HW, C, G,
-         float(eps), int(relu), _stream())
-    return y, mean, rstd
+    y, mean, rstd = groupnorm_relu_seg_fwd(x.view(N * H * W, C), [H * W] * N, gamma, beta, G, eps, relu)
+    return y.view(x.shape), mean, rstd
 
 
-def groupnorm_relu_bwd(dy, y, x, mean, rstd, gamma, dgamma, dbeta, G=32, relu=True, out=None):
+def groupnorm_relu_bwd(dy, y, x, mean, rstd, gamma, dgamma, dbeta, G=32, relu=True):
     N, H, W, C = x.shape
-    HW = H * W
-    dx = torch.empty_like(x) if out is None else out
-    ws = workspace(load().utv2_groupnorm_workspace_floats(N, HW, C), x.device, "gn")
-    call("utv2_groupnorm_relu_bwd", _p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(dgamma), _p(dbeta),
-         _p(ws), N, HW, C, G, int(relu), _stream())
-    return dx
+    dx = groupnorm_relu_seg_bwd(dy.view(-1, C), y.view(-1, C), x.view(-1, C), [H * W] * N, mean, rstd, gamma, dgamma, dbeta, G, relu)
+    return dx.view(x.shape)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1228,13 +1208,9 @@ def groupnorm_relu_seg_fwd_p32(x2d, seg_rows, gamma, beta, part32, G, eps=1e-5, 
     mean = torch.empty((S, G), dtype=torch.float32, device=x2d.device)
     rstd = torch.empty((S, G), dtype=torch.float32, device=x2d.device)
     sr = _iarr(seg_rows)
-    if relu_bits is not None:
-        assert relu_bits.dtype == torch.uint8 and relu_bits.numel() * 8 == rows * C and C % 32 == 0
-        call("utv2_groupnorm_relu_seg_fwd_p32b", _p(x2d), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(part32), S, ctypes.cast(sr, c_p),
-             C, G, float(eps), int(relu), _p(relu_bits), _stream())
-    else:
-        call("utv2_groupnorm_relu_seg_fwd_p32", _p(x2d), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(part32), S, ctypes.cast(sr, c_p),
-             C, G, float(eps), int(relu), _stream())
+    assert relu_bits is None or (relu_bits.dtype == torch.uint8 and relu_bits.numel() * 8 == rows * C and C % 32 == 0)
+    call("utv2_groupnorm_relu_seg_fwd_p32", _p(x2d), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(part32), S, ctypes.cast(sr, c_p),
+         C, G, float(eps), int(relu), _p(relu_bits), _stream())
     return y, mean, rstd
 
 
@@ -1424,7 +1400,7 @@ def groupnorm_relu_seg_bwd(dy, y, x2d, seg_rows, mean, rstd, gamma, dgamma, dbet
     part = None
     if want_colsum:
         part = torch.empty((load().utv2_groupnorm_seg_chunks(S, ctypes.cast(sr, c_p)), C), dtype=torch.float32, device=x2d.device)
-    call("utv2_groupnorm_relu_seg_bwd_colsum", _p(dy), _p(y), _p(x2d), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx), _p(dgamma), _p(dbeta),
+    call("utv2_groupnorm_relu_seg_bwd", _p(dy), _p(y), _p(x2d), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx), _p(dgamma), _p(dbeta),
          _p(ws), S, ctypes.cast(sr, c_p), C, G, int(relu), _same_dt(dy, y, x2d), _p(part), _stream())
     return (dx, part) if want_colsum else dx
 

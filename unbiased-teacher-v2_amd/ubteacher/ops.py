@@ -430,7 +430,7 @@ class Conv:
 
     def bias_grad_from_gn(self):
         """the bias gradient = column sums of this conv's dY, and dY is the dx the following GroupNorm's backward writes: its last pass
-        sums the columns while it has them in registers (utv2_groupnorm_relu_seg_bwd_colsum) instead of a separate pass over dY next
+        sums the columns while it has them in registers (utv2_groupnorm_relu_seg_bwd with colsum_part) instead of a separate pass over dY next
         to the weight-gradient kernel"""
         return self.bias_by_gn and self.bias is not None and self.trainable and self.use_bf16_wgrad() and self.use_bf16_dgrad() \
             and os.environ.get("UTV2_GN_BIAS_GRAD", "1") != "0"
