@@ -176,6 +176,25 @@ int utv2_amp_found_inf(const float* grad, int64_t n, float* state, utv2_stream_t
 int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, void* mirror16, int64_t n, float lr, float momentum,
                           float weight_decay, float grad_scale, const float* state, utv2_stream_t stream);
 int utv2_amp_update_scale(float* state, float growth_factor, float backoff_factor, int growth_interval, utv2_stream_t stream);
+/* Per-tensor gradient clipping and Nesterov momentum inside the SGD update (SOLVER.CLIP_GRADIENTS.*, SOLVER.NESTEROV; Detectron2's
+ * maybe_add_gradient_clipping: clip_grad_value_ / clip_grad_norm_ on every parameter tensor inside optimizer.step(), then
+ * torch.optim.SGD [D2-recall]).  The updated arena range [0, chunk_start[nchunks]) is described by a device work list the caller builds
+ * once: chunk c = elements [chunk_start[c], chunk_start[c+1]) (int64, increasing, chunk_start[0] = 0), chunk_seg[c] = the reference
+ * tensor ("segment", 0 <= s < nseg) it lies in or -1 for elements of no tensor (padding), chunk_wd[c] its weight decay; seg_chunks =
+ * nseg pairs {first chunk, chunk count}: the chunks of a segment are consecutive.  The entry points cannot read the list; the caller
+ * vouches for it.  grad / param / mom_buf are 16-byte aligned, mirror16 8-byte.
+ * utv2_grad_clip_coef: coef[s] = min(1, clip_value / (mult * ||grad[segment s]||_p + 1e-6)), p = 2 / 1 / inf for norm_kind 0 / 1 / 2,
+ *   mult = grad_scale (/ amp_state[0], the loss scale, when amp_state is given).  Sums in fp64, two stages, no atomics: the result is
+ *   bit-reproducible.  partial: nchunks doubles of scratch.
+ * utv2_sgd_segmented: g = grad * mult; clip_mode 1: g = clamp(g, -clip_value, clip_value), 2: g *= coef[segment] (1 outside every
+ *   segment), 0: nothing; g += wd*p; buf = momentum*buf + g; p -= lr * (nesterov ? g + momentum*buf : buf); mirror16 as above.  With
+ *   amp_state the step is skipped when its found_inf flag is set.  The clipped gradient is not written back. */
+int utv2_grad_clip_coef(const float* grad, const int64_t* chunk_start, const int32_t* chunk_seg, int nchunks, const int32_t* seg_chunks,
+                        int nseg, int norm_kind, double clip_value, float grad_scale, const float* amp_state, double* partial, float* coef,
+                        utv2_stream_t stream);
+int utv2_sgd_segmented(float* param, const float* grad, float* mom_buf, void* mirror16, const int64_t* chunk_start,
+                       const int32_t* chunk_seg, const float* chunk_wd, int nchunks, const float* coef, int clip_mode, float clip_value,
+                       float lr, float momentum, float grad_scale, int nesterov, const float* amp_state, utv2_stream_t stream);
 
 /* ---- elementwise pieces of ResNet / FPN ([D2-recall]) ------------------ */
 int utv2_relu_bwd_scale(const void* dy, const void* y, const float* scale, void* out, int64_t M, int C, int dtype,

@@ -122,6 +122,165 @@ __global__ void amp_update_scale_f32(float* __restrict__ state, float growth, fl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-tensor gradient clipping and Nesterov momentum inside the SGD update (SOLVER.CLIP_GRADIENTS.*, SOLVER.NESTEROV).
+// [D2-recall] maybe_add_gradient_clipping runs, inside optimizer.step(), one clipper PER PARAMETER TENSOR on the unscaled gradient:
+//   "value": clip_grad_value_ - g = clamp(g, -v, v);   "norm": clip_grad_norm_ - g *= min(1, v / (||g||_p + 1e-6)), p in {2, 1, inf};
+// then torch.optim.SGD: g += wd*p ; buf = mom*buf + g ; p -= lr*(nesterov ? g + mom*buf : buf).
+// The arena knows nothing of tensors, so the host hands over a WORK LIST that tiles the updated range: chunk c is the elements
+// [chunk_start[c], chunk_start[c+1]) with the weight decay chunk_wd[c], and belongs to reference tensor ("segment") chunk_seg[c], or to
+// none (-1: alignment padding and unexported rows - coefficient 1).  A chunk never crosses a segment
+// border; a long segment is many chunks, so no tensor is serialised onto one workgroup.  Workgroups walk the list grid-stride; inside a
+// chunk the head up to the first 16-byte boundary and the tail are done by single lanes, the body with 16-byte accesses.
+// The norm is two-stage and atomic-free (bit-reproducible): seg_norm_partial writes one fp64 partial per chunk (every product and sum in
+// fp64: a square of an fp32 value is exact there), seg_clip_coef adds a segment's partials in a fixed order with one wave and rounds
+// once, at the end: coef = (float)min(1, v / (mult * norm + 1e-6)), mult = grad_scale / loss scale - the multiplier the update applies
+// to the raw gradient (norms are homogeneous, so the norm of the scaled gradient is mult * the norm of the raw one).
+enum { SEG_NORM_L2 = 0, SEG_NORM_L1 = 1, SEG_NORM_INF = 2 };
+
+template <int KIND>
+__device__ __forceinline__ double seg_norm_term(float v) {
+  const double d = (double)v;
+  return KIND == SEG_NORM_L2 ? d * d : fabs(d);
+}
+
+// sum, or a maximum that keeps a NaN once it has seen one (torch's max does)
+template <int KIND>
+__device__ __forceinline__ double seg_norm_join(double a, double b) {
+  if (KIND != SEG_NORM_INF) return a + b;
+  return (b > a || b != b) ? b : a;
+}
+
+template <int KIND>
+__device__ __forceinline__ double seg_norm_wave(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = seg_norm_join<KIND>(v, __shfl_down(v, off, WAVE));
+  return v;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_norm_partial(const float* __restrict__ g, const int64_t* __restrict__ chunk_start,
+                                                      const int32_t* __restrict__ chunk_seg, int nchunks,
+                                                      double* __restrict__ partial) {
+  __shared__ double red[4];
+  const int t = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    if (chunk_seg[c] < 0) continue;                  // the same for the whole workgroup; nobody reads a gap's partial
+    const int64_t s = chunk_start[c], e = chunk_start[c + 1];
+    int64_t a = (s + 3) & ~(int64_t)3;               // first 16-byte boundary (the arena's base is 16-byte aligned)
+    if (a > e) a = e;
+    const int64_t n4 = (e - a) >> 2, tail = a + 4 * n4;
+    double acc = 0.0;
+    if (t < a - s) acc = seg_norm_term<KIND>(g[s + t]);                              // head: lanes 0..2
+    else if (t >= 4 && t - 4 < e - tail) acc = seg_norm_term<KIND>(g[tail + t - 4]);   // tail: lanes 4..6
+    for (int64_t j = t; j < n4; j += 4 * 256) {
+      f32x4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {                  // four independent 16-byte loads in flight per lane
+        const int64_t jj = j + 256 * u;
+        v[u] = jj < n4 ? *(const f32x4*)(g + a + 4 * jj) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc = seg_norm_join<KIND>(acc, seg_norm_term<KIND>(v[u][q]));
+    }
+    acc = seg_norm_wave<KIND>(acc);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0)
+      partial[c] = seg_norm_join<KIND>(seg_norm_join<KIND>(red[0], red[1]), seg_norm_join<KIND>(red[2], red[3]));
+    __syncthreads();                                 // red is written again in the next round
+  }
+}
+
+// one wave per segment; seg_chunks[s] = {first chunk, chunk count}; state (AMP): the loss scale is read here, on the device
+template <int KIND>
+__global__ __launch_bounds__(64) void seg_clip_coef(const double* __restrict__ partial, const int32_t* __restrict__ seg_chunks, int nseg,
+                                                  double clip_value, float gscale, const float* __restrict__ state,
+                                                  float* __restrict__ coef) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (s >= nseg) return;
+  const int first = seg_chunks[2 * s], cnt = seg_chunks[2 * s + 1];
+  double acc = 0.0;
+  for (int i = lane; i < cnt; i += 64) acc = seg_norm_join<KIND>(acc, partial[first + i]);
+  acc = seg_norm_wave<KIND>(acc);
+  if (lane == 0) {
+    const double mult = state ? (double)gscale / (double)state[0] : (double)gscale;
+    const double norm = (KIND == SEG_NORM_L2 ? sqrt(acc) : acc) * mult;
+    const double c = clip_value / (norm + 1e-6);
+    coef[s] = (float)(c > 1.0 ? 1.0 : c);            // a NaN norm gives a NaN coefficient, as clip_grad_norm_ does
+  }
+}
+
+enum { SEG_CLIP_NONE = 0, SEG_CLIP_VALUE = 1, SEG_CLIP_NORM = 2 };
+
+// one element of the update; the roundings are those of sgd_momentum_f32 / sgd_momentum_amp_f32, with the clip between the gradient
+// multiplier and the weight decay (cf == 1 and no Nesterov: the same bits as those kernels)
+template <bool AMP>
+__device__ __forceinline__ float sgd_seg_elem(float pv, float gr, float& mv, float inv, float gscale, int clip_mode, float cf, float cv,
+                                              float wd, float mom, float lr, int nesterov) {
+  float gv = AMP ? __fmul_rn(__fmul_rn(gr, inv), gscale) : __fmul_rn(gr, gscale);
+  if (clip_mode == SEG_CLIP_NORM) gv = __fmul_rn(gv, cf);
+  else if (clip_mode == SEG_CLIP_VALUE) gv = gv < -cv ? -cv : (gv > cv ? cv : gv);   // a NaN stays a NaN (clamp_)
+  gv = __fadd_rn(gv, __fmul_rn(wd, pv));
+  mv = __fadd_rn(__fmul_rn(mom, mv), gv);
+  const float step = nesterov ? __fadd_rn(gv, __fmul_rn(mom, mv)) : mv;
+  return __fsub_rn(pv, __fmul_rn(lr, step));
+}
+
+template <bool AMP>
+__global__ __launch_bounds__(256) void sgd_seg_f32(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 h16_t* __restrict__ mirror16, const int64_t* __restrict__ chunk_start,
+                                                 const int32_t* __restrict__ chunk_seg, const float* __restrict__ chunk_wd, int nchunks,
+                                                 const float* __restrict__ coef, int clip_mode, float cv, float lr, float mom,
+                                                 float gscale, int nesterov, const float* __restrict__ state) {
+  float inv = 1.f;
+  if (AMP) {
+    if (state[1] != 0.f) return;                     // non-finite gradients: the step is skipped (a fresh mirror16 stays fresh)
+    inv = 1.0f / state[0];                           // the scale is a power of two: exact
+  }
+  const int t = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t s = chunk_start[c], e = chunk_start[c + 1];
+    const int seg = chunk_seg[c];
+    const float cf = (clip_mode == SEG_CLIP_NORM && seg >= 0) ? coef[seg] : 1.f;
+    const float wd = chunk_wd[c];
+    int64_t a = (s + 3) & ~(int64_t)3;
+    if (a > e) a = e;
+    const int64_t n4 = (e - a) >> 2, tail = a + 4 * n4;
+    int64_t i = -1;                                  // the head / tail element of this lane, if it has one
+    if (t < a - s) i = s + t;
+    else if (t >= 4 && t - 4 < e - tail) i = tail + t - 4;
+    if (i >= 0) {
+      float mv = m[i];
+      const float pn = sgd_seg_elem<AMP>(p[i], g[i], mv, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
+      m[i] = mv;
+      p[i] = pn;
+      if (mirror16) mirror16[i] = (h16_t)pn;
+    }
+    for (int64_t j = t; j < n4; j += 256) {
+      const int64_t o = a + 4 * j;
+      const f32x4 pv = *(const f32x4*)(p + o), gv = *(const f32x4*)(g + o);
+      f32x4 mv = *(const f32x4*)(m + o), pn;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float mq = mv[q];
+        pn[q] = sgd_seg_elem<AMP>(pv[q], gv[q], mq, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
+        mv[q] = mq;
+      }
+      *(f32x4*)(m + o) = mv;
+      *(f32x4*)(p + o) = pn;
+      if (mirror16) {
+        bf16x4_t h;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) h[q] = (h16_t)pn[q];
+        *(bf16x4_t*)(mirror16 + o) = h;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // out = (mask_y ? (y > 0 ? dy : 0) : dy) * (scale ? scale[c] : 1)     on [M][C]
 template <typename T>
 __global__ __launch_bounds__(256) void relu_bwd_scale_k(const T* __restrict__ dy, const T* __restrict__ y,
@@ -1063,6 +1222,44 @@ int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, void*
 int utv2_amp_update_scale(float* state, float growth_factor, float backoff_factor, int growth_interval, hipStream_t stream) {
   if (!state || growth_interval < 1) return UTV2_EARG;
   hipLaunchKernelGGL(amp_update_scale_f32, dim3(1), dim3(64), 0, stream, state, growth_factor, backoff_factor, growth_interval);
+  return utv2_launch_status();
+}
+
+// the work list (see seg_norm_partial) is device memory the caller built and checked; here only what the host can see is checked
+int utv2_grad_clip_coef(const float* grad, const int64_t* chunk_start, const int32_t* chunk_seg, int nchunks, const int32_t* seg_chunks,
+                        int nseg, int norm_kind, double clip_value, float grad_scale, const float* amp_state, double* partial, float* coef,
+                        hipStream_t stream) {
+  if (!grad || !chunk_start || !chunk_seg || !seg_chunks || !partial || !coef || nchunks < 0 || nseg < 0) return UTV2_EARG;
+  if (norm_kind < SEG_NORM_L2 || norm_kind > SEG_NORM_INF || !(clip_value > 0.0) || ((uintptr_t)grad & 15)) return UTV2_EARG;
+  if (nseg == 0 || nchunks == 0) return UTV2_OK;
+  const int grid = nchunks < 2048 ? nchunks : 2048;
+#define SEG_NORM_LAUNCH(KIND)                                                                                                      \
+  hipLaunchKernelGGL(seg_norm_partial<KIND>, dim3(grid), dim3(256), 0, stream, grad, chunk_start, chunk_seg, nchunks, partial);    \
+  hipLaunchKernelGGL(seg_clip_coef<KIND>, dim3(nseg), dim3(64), 0, stream, partial, seg_chunks, nseg, clip_value, grad_scale,      \
+                     amp_state, coef)
+  if (norm_kind == SEG_NORM_L2) { SEG_NORM_LAUNCH(SEG_NORM_L2); }
+  else if (norm_kind == SEG_NORM_L1) { SEG_NORM_LAUNCH(SEG_NORM_L1); }
+  else { SEG_NORM_LAUNCH(SEG_NORM_INF); }
+#undef SEG_NORM_LAUNCH
+  return utv2_launch_status();
+}
+
+int utv2_sgd_segmented(float* param, const float* grad, float* mom_buf, void* mirror16, const int64_t* chunk_start,
+                       const int32_t* chunk_seg, const float* chunk_wd, int nchunks, const float* coef, int clip_mode, float clip_value,
+                       float lr, float momentum, float grad_scale, int nesterov, const float* amp_state, hipStream_t stream) {
+  if (!param || !grad || !mom_buf || !chunk_start || !chunk_seg || !chunk_wd || nchunks < 0) return UTV2_EARG;
+  if (clip_mode < SEG_CLIP_NONE || clip_mode > SEG_CLIP_NORM || (clip_mode == SEG_CLIP_NORM && !coef) ||
+      (clip_mode == SEG_CLIP_VALUE && !(clip_value > 0.f)))
+    return UTV2_EARG;
+  if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)mom_buf) & 15) || ((uintptr_t)mirror16 & 7)) return UTV2_EARG;
+  if (nchunks == 0) return UTV2_OK;
+  const int grid = nchunks < 2048 ? nchunks : 2048;
+  if (amp_state)
+    hipLaunchKernelGGL(sgd_seg_f32<true>, dim3(grid), dim3(256), 0, stream, param, grad, mom_buf, (h16_t*)mirror16, chunk_start, chunk_seg,
+                       chunk_wd, nchunks, coef, clip_mode, clip_value, lr, momentum, grad_scale, nesterov, amp_state);
+  else
+    hipLaunchKernelGGL(sgd_seg_f32<false>, dim3(grid), dim3(256), 0, stream, param, grad, mom_buf, (h16_t*)mirror16, chunk_start, chunk_seg,
+                       chunk_wd, nchunks, coef, clip_mode, clip_value, lr, momentum, grad_scale, nesterov, amp_state);
   return utv2_launch_status();
 }
 

@@ -32,9 +32,16 @@ from .step_gc import StepGC
 
 
 class ArenaSGD:
-    """torch.optim.SGD semantics (momentum, dampening 0, no nesterov; weight decay per group as D2's
+    """torch.optim.SGD semantics (momentum, dampening 0; weight decay per group as D2's
     get_default_optimizer_params: WEIGHT_DECAY on weights and biases, WEIGHT_DECAY_NORM on norm
-    params) as one fused launch per group over the flat arena."""
+    params) as one fused launch per group over the flat arena.
+
+    SOLVER.CLIP_GRADIENTS (Detectron2 maybe_add_gradient_clipping [D2-recall]: inside optimizer.step(), clip_grad_value_ or
+    clip_grad_norm_ on EACH parameter tensor - there is no global clipper - applied to the unscaled gradient, before weight decay) and
+    SOLVER.NESTEROV take the segmented path instead: a work list of the reference's tensors inside the arena (params.export_segments),
+    a per-tensor norm reduction, and ONE update launch that applies each element's coefficient on the fly.  No host read, nothing
+    uploaded per step, the clipped gradient is never written back; clipping carries no state, so checkpoints are unchanged.  With both
+    keys at their defaults the step is exactly the launches it was."""
 
     def __init__(self, cfg, model):
         s = cfg.SOLVER
@@ -44,11 +51,66 @@ class ArenaSGD:
         self.momentum = s.MOMENTUM
         self.wd = s.WEIGHT_DECAY
         self.wd_norm = s.WEIGHT_DECAY_NORM
+        # D2 get_default_optimizer_params [D2-recall]: per-bias learning rate / weight decay would need a third parameter group
+        if float(s.BIAS_LR_FACTOR) != 1.0:
+            raise NotImplementedError("SOLVER.BIAS_LR_FACTOR %r: a separate learning rate for biases is not built, only 1.0" % (s.BIAS_LR_FACTOR,))
+        if s.WEIGHT_DECAY_BIAS is not None and float(s.WEIGHT_DECAY_BIAS) != float(s.WEIGHT_DECAY):
+            raise NotImplementedError("SOLVER.WEIGHT_DECAY_BIAS %r: a separate weight decay for biases is not built, only None or "
+                                      "SOLVER.WEIGHT_DECAY (%r)" % (s.WEIGHT_DECAY_BIAS, s.WEIGHT_DECAY))
+        self.nesterov = bool(s.NESTEROV)
+        self.clip_type = self.clip_value = self.norm_type = None
+        cg = s.CLIP_GRADIENTS
+        if cg.ENABLED:
+            if cg.CLIP_TYPE not in ("value", "norm"):
+                raise NotImplementedError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE %r: only \"value\" and \"norm\" exist" % (cg.CLIP_TYPE,))
+            if not float(cg.CLIP_VALUE) > 0.0:
+                raise ValueError("SOLVER.CLIP_GRADIENTS.CLIP_VALUE %r: must be positive" % (cg.CLIP_VALUE,))
+            self.clip_type, self.clip_value = cg.CLIP_TYPE, float(cg.CLIP_VALUE)
+            if self.clip_type == "norm":
+                try:
+                    self.norm_type = float(cg.NORM_TYPE)
+                except (TypeError, ValueError):
+                    self.norm_type = None
+                if self.norm_type not in hip.NORM_KINDS:
+                    raise NotImplementedError("SOLVER.CLIP_GRADIENTS.NORM_TYPE %r: the norm reduction is built for 2.0, 1.0 and inf"
+                                              % (cg.NORM_TYPE,))
         self.store.mom = torch.zeros_like(self.store.grad)
         self.param_groups = [{"lr": self.lr}]  # scheduler surface
+        self._seg_table = None
+        if self.segmented:
+            self.segment_table()
+
+    @property
+    def segmented(self):
+        return self.clip_type is not None or self.nesterov
+
+    def _layout(self):
+        st = self.store
+        return (st.n_train, st.ranges["decay"], st.ranges["nodecay"], st.grad.data_ptr(), len(st.handles))
+
+    def segment_table(self):
+        """the device work list of the segmented step (params.SegmentTable): built and uploaded at construction, rebuilt only when the
+        store's layout is no longer the one it was built from"""
+        if self._seg_table is None or self._seg_table[0] != self._layout():
+            from ..params import SegmentTable, export_segments
+            st = self.store
+            segs = export_segments(st)
+            table = SegmentTable(st.n_train, [(a, b) for _, a, b, _ in segs],
+                                 [st.ranges["decay"] + (self.wd,), st.ranges["nodecay"] + (self.wd_norm,)], st.grad.device)
+            table.keys = [k for k, _, _, _ in segs]
+            self._seg_table = (self._layout(), table)
+        return self._seg_table[1]
 
     def zero_grad(self):
         self.store.grad.zero_()
+
+    def _step_segmented(self, lr, grad_scale, amp_state, m16):
+        st, tb = self.store, self.segment_table()
+        n = st.n_train
+        if self.clip_type == "norm":
+            hip.grad_clip_coef(st.grad, tb, self.norm_type, self.clip_value, grad_scale, amp_state)
+        hip.sgd_segmented(st.flat[:n], st.grad, st.mom, tb, lr, self.momentum, grad_scale, self.clip_type, self.clip_value or 1.0,
+                          self.nesterov, amp_state, mirror16=None if m16 is None else m16[:n])
 
     def step(self, grad_scale=1.0, amp_state=None):
         """amp_state (fp16 mode): device fp32 {loss scale, found_inf, growth tracker} - the step unscales the gradients and is skipped on
@@ -58,7 +120,11 @@ class ArenaSGD:
         if amp_state is not None:
             hip.amp_found_inf(st.grad, amp_state)
         m16 = st.mirror16(need_fresh=True)    # the 16-bit copy the convs read: written by the update itself (no conversion pass next step)
-        for kind, wd in (("decay", self.wd), ("nodecay", self.wd_norm)):
+        groups = (("decay", self.wd), ("nodecay", self.wd_norm))
+        if self.segmented:
+            self._step_segmented(lr, grad_scale, amp_state, m16)
+            groups = ()
+        for kind, wd in groups:
             s, e = st.ranges[kind]
             mk = None if m16 is None else m16[s:e]
             if e > s and amp_state is not None:

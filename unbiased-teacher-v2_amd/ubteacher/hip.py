@@ -292,6 +292,32 @@ def amp_update_scale(state, growth=2.0, backoff=0.5, interval=2000):
     call("utv2_amp_update_scale", _p(state), float(growth), float(backoff), int(interval), _stream())
 
 
+NORM_KINDS = {2.0: 0, 1.0: 1, float("inf"): 2}      # CLIP_GRADIENTS.NORM_TYPE -> norm_kind of utv2_grad_clip_coef
+CLIP_MODES = {None: 0, "value": 1, "norm": 2}       # CLIP_GRADIENTS.CLIP_TYPE -> clip_mode of utv2_sgd_segmented
+
+
+def grad_clip_coef(grad, table, norm_type, clip_value, grad_scale=1.0, state=None):
+    """table.coef[s] = min(1, clip_value / (||grad_scale (/ loss scale) * grad[segment s]||_p + 1e-6)) for every segment of `table`
+    (params.SegmentTable); state: the AMP state whose loss scale the kernel reads.  Returns table.coef."""
+    assert grad.dtype == torch.float32 and grad.numel() == table.n and table.chunk_start.device == grad.device
+    call("utv2_grad_clip_coef", _p(grad), _p(table.chunk_start), _p(table.chunk_seg), table.nchunks, _p(table.seg_chunks), table.nseg,
+         NORM_KINDS[float(norm_type)], float(clip_value), float(grad_scale), _p(state), _p(table.partial), _p(table.coef), _stream())
+    return table.coef
+
+
+def sgd_segmented(param, grad, mom, table, lr, momentum, grad_scale=1.0, clip_type=None, clip_value=1.0, nesterov=False, state=None,
+                  mirror16=None):
+    """the SGD update of param[0:table.n] with table's per-chunk weight decay; clip_type "norm" multiplies each segment's gradient by
+    table.coef (grad_clip_coef first), "value" clamps every gradient element, None leaves it; state: the AMP step (unscale, skip on
+    found_inf)"""
+    assert param.numel() == grad.numel() == mom.numel() == table.n and table.chunk_start.device == param.device
+    assert param.dtype == grad.dtype == mom.dtype == torch.float32
+    assert mirror16 is None or (mirror16.dtype == h16_dtype() and mirror16.numel() == param.numel())
+    call("utv2_sgd_segmented", _p(param), _p(grad), _p(mom), _p(mirror16), _p(table.chunk_start), _p(table.chunk_seg), _p(table.chunk_wd),
+         table.nchunks, _p(table.coef), CLIP_MODES[clip_type], float(clip_value), float(lr), float(momentum), float(grad_scale),
+         int(bool(nesterov)), _p(state), _stream())
+
+
 def relu_bwd_scale(dy, y=None, scale=None, out=None):
     C = dy.shape[-1]
     M = dy.numel() // C

@@ -49,6 +49,91 @@ class Handle:
         return self
 
 
+def export_segments(store):
+    """The reference's parameter tensors as element ranges of the trainable arena: [(state_dict key, start, end, kind)] sorted by start.
+    One handle may hold several reference tensors (the paired FCOS towers, the fused box head, the fused RPN / ROI prediction layers),
+    and what Detectron2 clips is the reference's tensor [D2-recall], so the ranges are DERIVED, not declared: an index tensor is pushed
+    through each export function and what comes out must be a contiguous range of exactly the exported tensor's numel.  An export that
+    is not (the 7x7 stem's strided view of its padded rows) raises: per-tensor operations on the arena cannot express it."""
+    segs = []
+    for h in store.handles:
+        if h.kind not in ("decay", "nodecay"):
+            continue
+        idx = torch.arange(h.numel, dtype=torch.int64).view(h.shape)
+        for key, fn in h.exports:
+            flat = (idx if fn is None else fn(idx)).reshape(-1)
+            n = flat.numel()
+            lo = int(flat.min()) if n else 0
+            seen = torch.zeros(n, dtype=torch.bool)
+            if n:
+                seen[(flat - lo).clamp_(0, n - 1)] = True
+            if n == 0 or int(flat.max()) - lo + 1 != n or not bool(seen.all()):
+                raise ValueError("%s is not a contiguous range of the parameter arena (its export view strides over other elements): "
+                                 "no per-tensor segment can be built for it" % key)
+            segs.append((key, h.offset + lo, h.offset + lo + n, h.kind))
+    segs.sort(key=lambda s: s[1])
+    for a, b in zip(segs, segs[1:]):
+        if b[1] < a[2]:
+            raise ValueError("%s and %s overlap in the parameter arena" % (a[0], b[0]))
+    return segs
+
+
+class SegmentTable:
+    """The device work list of the segmented optimizer kernels (include/utv2.h utv2_grad_clip_coef / utv2_sgd_segmented) over the arena
+    range [0, n): `segments` = sorted disjoint (start, end) element ranges, `wd_ranges` = (start, end, weight decay) tiling [0, n).
+    The range is cut into chunks of at most CHUNK elements that cross neither a segment border nor a weight-decay border; what lies in
+    no segment (alignment padding, unexported rows) becomes chunks of segment -1.  Built and uploaded once; `partial` and `coef` are the
+    kernels' scratch and output, allocated here so that a step allocates nothing."""
+    CHUNK = 4096
+
+    def __init__(self, n, segments, wd_ranges, device):
+        segments = [(int(s), int(e)) for s, e in segments]
+        pos = 0
+        for s, e in segments:
+            if not (pos <= s < e <= n):
+                raise ValueError("segments must be sorted, disjoint, non-empty and inside [0, %d): got (%d, %d) after %d" % (n, s, e, pos))
+            pos = e
+        pos = 0
+        for s, e, _ in wd_ranges:
+            if s != pos or e < s:
+                raise ValueError("weight-decay ranges must tile [0, %d)" % n)
+            pos = e
+        if pos != n:
+            raise ValueError("weight-decay ranges must tile [0, %d)" % n)
+        # pieces: (start, end, segment id or -1), then cut at the weight-decay borders and into chunks
+        pieces, pos = [], 0
+        for i, (s, e) in enumerate(segments):
+            if s > pos:
+                pieces.append((pos, s, -1))
+            pieces.append((s, e, i))
+            pos = e
+        if pos < n:
+            pieces.append((pos, n, -1))
+        starts, segs, wds = [], [], []
+        seg_chunks = [[0, 0] for _ in segments]
+        for s, e, i in pieces:
+            for ws, we, wd in wd_ranges:
+                a, b = max(s, ws), min(e, we)
+                for c0 in range(a, b, self.CHUNK):
+                    if i >= 0:
+                        if seg_chunks[i][1] == 0:
+                            seg_chunks[i][0] = len(starts)
+                        seg_chunks[i][1] += 1
+                    starts.append(c0)
+                    segs.append(i)
+                    wds.append(float(wd))
+        starts.append(n)
+        assert starts[0] == 0 and all(b > a for a, b in zip(starts, starts[1:]))
+        self.n, self.nseg, self.nchunks = int(n), len(segments), len(segs)
+        self.segments = segments
+        self.chunk_start = torch.tensor(starts, dtype=torch.int64).to(device)
+        self.chunk_seg = torch.tensor(segs, dtype=torch.int32).to(device)
+        self.chunk_wd = torch.tensor(wds, dtype=torch.float32).to(device)
+        self.seg_chunks = torch.tensor(seg_chunks, dtype=torch.int32).reshape(-1, 2).to(device)
+        self.partial = torch.zeros(max(self.nchunks, 1), dtype=torch.float64, device=device)
+        self.coef = torch.ones(max(self.nseg, 1), dtype=torch.float32, device=device)
+
+
 class ParamStore:
     def __init__(self):
         self.handles = []
