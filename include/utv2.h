@@ -325,15 +325,36 @@ int utv2_fcos_loss_combine(const float* focal_sup, const float* sums_sup, const 
                            const float* sums_reg, const float* norm, float world, int flags, float kl_weight, const float* wmul_host,
                            const float* wdiv_host, float* rec, float* coef, utv2_stream_t stream);
 /* :1146-1195 ranking score -> sortable int64 key (method 0 cls, 1 cls_n_ctr, 2 ctr, 3 cls_n_loc); image n's HW*C keys
- * start at keys + n*key_row_stride (>= HW*C: rows of a wider matrix shared by all FPN levels) */
+ * start at keys + n*key_row_stride (>= HW*C: rows of a wider matrix shared by all FPN levels).  = utv2_fcos_rank_keys_f with flags 0. */
 int utv2_fcos_rank_keys(const float* logits, const float* box, int box_stride, int reg_max, int N, int HW, int C,
                         float thr, int method, long long* keys, int64_t key_row_stride, utv2_stream_t stream);
+/* MODEL.FCOS.THRESH_WITH_CTR (fcos_outputs.py:148,1172-1195,1270-1275): the ranking / decode entry points with a further `flags`
+ * argument, 0 or UTV2_FCOS_THRESH_WITH_CTR; utv2_fcos_rank_keys, utv2_fcos_decode and utv2_fcos_decode_cont forward to them with
+ * flags 0 (one kernel per op, the flag is a uniform branch in it), every other argument and check as there.  With the flag,
+ * s = sigmoid(logit) * sigmoid(ctrness) (both sigmoids first, one fp32 product) is what the threshold tests, s is the ranking score
+ * the key carries for EVERY criterion (the cls / cls_n_ctr / ctr / cls_n_loc switch is skipped; ctrness is read at column
+ * 4 * (reg_max + 1) + 4: the discrete rows and, with reg_max = 0, the continuous ones) and the decode writes oconf = s; oscores
+ * still follows the criterion's name: sqrt(s) for cls_n_ctr / cls_n_loc, s for cls / ctr; octr (the plain sigmoid), ostd, boxes and
+ * locations do not depend on the flag.  The keys a decode is given must come from utv2_fcos_rank_keys_f with the same flags.
+ * UTV2_EARG, nothing launched: method outside 0..3, any flag bit other than UTV2_FCOS_THRESH_WITH_CTR. */
+#define UTV2_FCOS_THRESH_WITH_CTR 1
+int utv2_fcos_rank_keys_f(const float* logits, const float* box, int box_stride, int reg_max, int N, int HW, int C,
+                          float thr, int method, int flags, long long* keys, int64_t key_row_stride, utv2_stream_t stream);
+int utv2_fcos_decode_f(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int reg_max,
+                       int N, int HW, int Wl, int C, int stride, int level, int method, int flags, int MAXC, int slot0, float* oboxes,
+                       float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
+                       unsigned char* ovalid, utv2_stream_t stream);
+int utv2_fcos_decode_cont_f(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
+                            int C, int stride, int level, int method, int flags, int MAXC, int slot0, float* oboxes, float* oscores,
+                            int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid,
+                            utv2_stream_t stream);
 /* :1238-1241 `topk(pre_nms_top_n)` for every (image, level) row at once: exact MSD radix select over ragged rows
  * (row r = keys[row_off[r] .. row_off[r+1]), row_off device int64[rows+1]); out[rows][k] descending, -1 padded; k <= 8192 */
 int64_t utv2_topk_rows_workspace_bytes(int rows, int k);
 int utv2_topk_rows_i64(const long long* keys, const long long* row_off, int rows, int64_t max_width, int k, long long* out,
                        void* ws, utv2_stream_t stream);
-/* :1093-1104,:1258-1296 decode of the selected candidates of one level into padded slots */
+/* :1093-1104,:1258-1296 decode of the selected candidates of one level into padded slots (method 0..3, as utv2_fcos_rank_keys; this
+ * entry point does not check it: any other value writes what 0 writes, as it always did).  = utv2_fcos_decode_f with flags 0. */
 int utv2_fcos_decode(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int reg_max,
                      int N, int HW, int Wl, int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes,
                      float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
@@ -360,7 +381,7 @@ int utv2_fcos_loc_terms_cont_bwd_acc(const int* labels, const float* box, int bo
  * utv2_fcos_rank_keys with reg_max = 0 (it finds std / ctr at 4 * (reg_max + 1) = 4: this layout).
  * Checked: non-null pointers (outputs included), box_stride >= 9 and % 4 == 0, K >= 0, 1 <= N <= 65535, HW, Wl, C, stride >= 1,
  * Wl <= HW, HW * C < 2^32, method 0..3, slot0 >= 0, slot0 + K <= MAXC.  K == 0 writes nothing.  A key >= 0 whose index lies outside
- * HW * C (no utv2_fcos_rank_keys output) becomes an empty slot. */
+ * HW * C (no utv2_fcos_rank_keys output) becomes an empty slot.  = utv2_fcos_decode_cont_f with flags 0. */
 int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
                           int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
                           float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid,

@@ -563,7 +563,10 @@ __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict
 // Ranking keys for the pre-NMS top-k (fcos_outputs.py:1146-1195,1238-1241).
 // key = (float bits of ranking score) << 32 | (0xFFFFFFFF - flat index) for candidates
 // (sigmoid(logit) > thr), else -1: descending int64 order == (score desc, index asc).
-// method: 0 cls, 1 cls_n_ctr, 2 ctr, 3 cls_n_loc
+// method: 0 cls, 1 cls_n_ctr, 2 ctr, 3 cls_n_loc; | FCOS_THRESH_WITH_CTR (MODEL.FCOS.THRESH_WITH_CTR, :1172-1181; the entry points'
+// `flags & UTV2_FCOS_THRESH_WITH_CTR`, put on top of the criterion by fcos_kernel_method): the threshold tests
+// s = sigmoid(logit) * sigmoid(ctrness) and s is the ranking score of every criterion (the switch at :1181-1195 is skipped).
+#define FCOS_THRESH_WITH_CTR 4
 __global__ __launch_bounds__(256) void fcos_rank_keys_kernel(const float* __restrict__ logits, const float* __restrict__ box, int BS,
                                                            int R4, int HW, int C, float thr, int method,
                                                            long long* __restrict__ keys, size_t key_stride) {
@@ -577,7 +580,10 @@ __global__ __launch_bounds__(256) void fcos_rank_keys_kernel(const float* __rest
     const size_t row = (size_t)n * HW + hw;
     const float p = 1.f / (1.f + expf(-logits[row * C + (i - hw * C)]));
     long long key = -1;
-    if (p > thr) {
+    if (method & FCOS_THRESH_WITH_CTR) {
+      const float sc = p * (1.f / (1.f + expf(-box[row * BS + R4 + 4])));
+      if (sc > thr) key = ((long long)__float_as_uint(sc) << 32) | (long long)(0xFFFFFFFFu - (unsigned)i);
+    } else if (p > thr) {
       float r = p;
       const float* br = box + row * BS;
       if (method == 1) r = p * (1.f / (1.f + expf(-br[R4 + 4])));
@@ -634,11 +640,13 @@ __global__ __launch_bounds__(128) void fcos_decode_kernel(const long long* __res
   oboxes[s * 4 + 1] = ly - d[1] * fs;
   oboxes[s * 4 + 2] = lx + d[2] * fs;
   oboxes[s * 4 + 3] = ly + d[3] * fs;
-  oscores[s] = (method == 1 || method == 3) ? sqrtf(rank) : rank;
+  const int crit = method & 3;
+  oscores[s] = (crit == 1 || crit == 3) ? sqrtf(rank) : rank;
   ocls[s] = c;
   oloc[s * 2] = lx; oloc[s * 2 + 1] = ly;
   octr[s] = 1.f / (1.f + expf(-br[4 * R1 + 4]));
-  oconf[s] = 1.f / (1.f + expf(-logits[row * C + c]));
+  // THRESH_WITH_CTR: cls_confs is taken after the centerness product (:1175-1179) - the ranking score the key carries
+  oconf[s] = (method & FCOS_THRESH_WITH_CTR) ? rank : 1.f / (1.f + expf(-logits[row * C + c]));
 #pragma unroll
   for (int e = 0; e < 4; ++e) ostd[s * 4 + e] = br[4 * R1 + e];
   olevel[s] = level;
@@ -821,11 +829,13 @@ __global__ __launch_bounds__(128) void fcos_decode_cont_kernel(const long long* 
   oboxes[s * 4 + 1] = ly - fmaxf(br[1], 0.f) * fs;
   oboxes[s * 4 + 2] = lx + fmaxf(br[2], 0.f) * fs;
   oboxes[s * 4 + 3] = ly + fmaxf(br[3], 0.f) * fs;
-  oscores[s] = (method == 1 || method == 3) ? sqrtf(rank) : rank;
+  const int crit = method & 3;
+  oscores[s] = (crit == 1 || crit == 3) ? sqrtf(rank) : rank;
   ocls[s] = c;
   oloc[s * 2] = lx; oloc[s * 2 + 1] = ly;
   octr[s] = 1.f / (1.f + expf(-br[CT_CTR]));
-  oconf[s] = 1.f / (1.f + expf(-logits[row * C + c]));
+  // THRESH_WITH_CTR: cls_confs is taken after the centerness product (:1175-1179) - the ranking score the key carries
+  oconf[s] = (method & FCOS_THRESH_WITH_CTR) ? rank : 1.f / (1.f + expf(-logits[row * C + c]));
 #pragma unroll
   for (int e = 0; e < 4; ++e) ostd[s * 4 + e] = br[CT_STD + e];
   olevel[s] = level;
@@ -1139,9 +1149,16 @@ int utv2_fcos_loc_terms_bwd_acc(const int* labels, const float* box, int box_str
 }
 
 // one level: logits [N][HW][C], box [N][HW][BS] -> keys [N][HW*C]
-int utv2_fcos_rank_keys(const float* logits, const float* box, int box_stride, int reg_max, int N, int HW, int C, float thr,
-                        int method, long long* keys, int64_t key_row_stride, hipStream_t stream) {
-  if (!logits || !box || !keys || method < 0 || method > 3 || key_row_stride < (int64_t)HW * C) return UTV2_EARG;
+// criterion 0..3 and flags 0 | 1 (UTV2_FCOS_THRESH_WITH_CTR) -> what the kernels are told; -1: an unknown criterion or flag
+static int fcos_kernel_method(int method, int flags) {
+  if (method < 0 || method > 3 || (flags & ~1)) return -1;
+  return method | (flags ? FCOS_THRESH_WITH_CTR : 0);
+}
+
+int utv2_fcos_rank_keys_f(const float* logits, const float* box, int box_stride, int reg_max, int N, int HW, int C, float thr,
+                          int method, int flags, long long* keys, int64_t key_row_stride, hipStream_t stream) {
+  method = fcos_kernel_method(method, flags);
+  if (!logits || !box || !keys || method < 0 || key_row_stride < (int64_t)HW * C) return UTV2_EARG;
   int gx = cdiv((int64_t)HW * C, 256);
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(fcos_rank_keys_kernel, dim3(gx, N), dim3(256), 0, stream, logits, box, box_stride, 4 * (reg_max + 1), HW, C,
@@ -1149,15 +1166,31 @@ int utv2_fcos_rank_keys(const float* logits, const float* box, int box_stride, i
   return utv2_launch_status();
 }
 
-int utv2_fcos_decode(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int reg_max,
-                     int N, int HW, int Wl, int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes,
-                     float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
-                     unsigned char* ovalid, hipStream_t stream) {
-  if (!topkeys || !logits || !box || reg_max != 16 || slot0 + K > MAXC) return UTV2_EARG;
+int utv2_fcos_rank_keys(const float* logits, const float* box, int box_stride, int reg_max, int N, int HW, int C, float thr,
+                        int method, long long* keys, int64_t key_row_stride, hipStream_t stream) {
+  return utv2_fcos_rank_keys_f(logits, box, box_stride, reg_max, N, HW, C, thr, method, 0, keys, key_row_stride, stream);
+}
+
+int utv2_fcos_decode_f(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int reg_max,
+                       int N, int HW, int Wl, int C, int stride, int level, int method, int flags, int MAXC, int slot0, float* oboxes,
+                       float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
+                       unsigned char* ovalid, hipStream_t stream) {
+  method = fcos_kernel_method(method, flags);
+  if (!topkeys || !logits || !box || reg_max != 16 || slot0 + K > MAXC || method < 0) return UTV2_EARG;
   hipLaunchKernelGGL((fcos_decode_kernel<17>), dim3(cdiv(K, 128), N), dim3(128), 0, stream, topkeys, K, logits, box, box_stride,
                      HW, Wl, C, stride, level, method, MAXC, slot0, oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel,
                      ovalid);
   return utv2_launch_status();
+}
+
+int utv2_fcos_decode(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int reg_max,
+                     int N, int HW, int Wl, int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes,
+                     float* oscores, int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel,
+                     unsigned char* ovalid, hipStream_t stream) {
+  // this entry point never checked `method`: whatever was not 1 or 3 wrote the ranking score as it is, like 0 - kept so
+  if (method < 0 || method > 3) method = 0;
+  return utv2_fcos_decode_f(topkeys, K, logits, box, box_stride, reg_max, N, HW, Wl, C, stride, level, method, 0, MAXC, slot0, oboxes,
+                            oscores, ocls, oloc, octr, oconf, ostd, olevel, ovalid, stream);
 }
 
 // ---- continuous regression head (REG_DISCRETE False): rows [ltrb 4 | std 4 | ctr 1 | pad] -------------------------------------------
@@ -1198,17 +1231,26 @@ int utv2_fcos_loc_terms_cont_bwd_acc(const int* labels, const float* box, int bo
   return utv2_launch_status();
 }
 
-int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
-                          int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
-                          float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid, hipStream_t stream) {
+int utv2_fcos_decode_cont_f(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
+                            int C, int stride, int level, int method, int flags, int MAXC, int slot0, float* oboxes, float* oscores,
+                            int* ocls, float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid,
+                            hipStream_t stream) {
+  method = fcos_kernel_method(method, flags);
   if (!topkeys || !logits || !box || !oboxes || !oscores || !ocls || !oloc || !octr || !oconf || !ostd || !olevel || !ovalid ||
       box_stride < CT_COLS || (box_stride & 3) || K < 0 || N < 1 || N > 65535 || HW < 1 || Wl < 1 || Wl > HW || C < 1 || stride < 1 ||
-      method < 0 || method > 3 || slot0 < 0 || MAXC < 0 || (int64_t)slot0 + K > MAXC || (int64_t)HW * C > 0xFFFFFFFFll)
+      method < 0 || slot0 < 0 || MAXC < 0 || (int64_t)slot0 + K > MAXC || (int64_t)HW * C > 0xFFFFFFFFll)
     return UTV2_EARG;
   if (K == 0) return UTV2_OK;
   hipLaunchKernelGGL(fcos_decode_cont_kernel, dim3(cdiv(K, 128), N), dim3(128), 0, stream, topkeys, K, logits, box, box_stride, HW, Wl, C,
                      stride, level, method, MAXC, slot0, oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel, ovalid);
   return utv2_launch_status();
+}
+
+int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, const float* box, int box_stride, int N, int HW, int Wl,
+                          int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
+                          float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid, hipStream_t stream) {
+  return utv2_fcos_decode_cont_f(topkeys, K, logits, box, box_stride, N, HW, Wl, C, stride, level, method, 0, MAXC, slot0, oboxes, oscores,
+                                 ocls, oloc, octr, oconf, ostd, olevel, ovalid, stream);
 }
 
 int utv2_scale_cols(float* y, int64_t rows, int row_stride, int ncols, const float* s, hipStream_t stream) {

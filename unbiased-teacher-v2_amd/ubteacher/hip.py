@@ -584,7 +584,13 @@ def fcos_loc_terms_bwd(labels, box, reg_targets, bvars, num_classes, reg_max, ts
     return out
 
 
-def fcos_rank_keys(logits, box, reg_max, N, HW, thr, method, out=None, row_stride=None):
+# MODEL.FCOS.THRESH_WITH_CTR: the `flags` of fcos_rank_keys / fcos_decode / fcos_decode_cont (UTV2_FCOS_THRESH_WITH_CTR of
+# include/utv2.h; the utv2_fcos_*_f entry points): threshold, ranking score and cls_confid become sigmoid(logit) * sigmoid(ctrness)
+# for every criterion.  flags 0 is what the entry points without the argument compute.
+FCOS_THRESH_WITH_CTR = 1
+
+
+def fcos_rank_keys(logits, box, reg_max, N, HW, thr, method, out=None, row_stride=None, flags=0):
     """keys [N][HW*C] int64 (or written into the first HW*C columns of `out`, whose rows are row_stride apart)"""
     C = logits.shape[-1]
     BS = box.shape[-1]
@@ -592,7 +598,7 @@ def fcos_rank_keys(logits, box, reg_max, N, HW, thr, method, out=None, row_strid
         out = torch.empty((N, HW * C), dtype=torch.int64, device=logits.device)
         row_stride = HW * C
     assert out.stride(1) == 1 and out.stride(0) == row_stride and out.shape[0] == N and out.shape[1] >= HW * C
-    call("utv2_fcos_rank_keys", _p_any(logits), _p_any(box), BS, reg_max, N, HW, C, float(thr), method, c_p(out.data_ptr()),
+    call("utv2_fcos_rank_keys_f", _p_any(logits), _p_any(box), BS, reg_max, N, HW, C, float(thr), method, int(flags), c_p(out.data_ptr()),
          int(row_stride), _stream())
     return out
 
@@ -606,12 +612,12 @@ def topk_rows(keys_flat, row_off, rows, max_width, k):
     return out
 
 
-def fcos_decode(topkeys, logits, box, reg_max, N, HW, Wl, stride, level, method, slot0, outs):
+def fcos_decode(topkeys, logits, box, reg_max, N, HW, Wl, stride, level, method, slot0, outs, flags=0):
     K = topkeys.shape[1]
     C = logits.shape[-1]
     BS = box.shape[-1]
     MAXC = outs["scores"].shape[1]
-    call("utv2_fcos_decode", _p(topkeys), K, _p(logits), _p(box), BS, reg_max, N, HW, Wl, C, stride, level, method, MAXC,
+    call("utv2_fcos_decode_f", _p(topkeys), K, _p(logits), _p(box), BS, reg_max, N, HW, Wl, C, stride, level, method, int(flags), MAXC,
          slot0, _p(outs["boxes"]), _p(outs["scores"]), _p(outs["classes"]), _p(outs["locations"]), _p(outs["centerness"]),
          _p(outs["cls_confid"]), _p(outs["reg_pred_std"]), _p(outs["fpn_levels"]), _p(outs["valid"]), _stream())
 
@@ -647,12 +653,12 @@ def fcos_loc_terms_cont_bwd_acc(labels, box, reg_targets, bvars, num_classes, ts
     return out
 
 
-def fcos_decode_cont(topkeys, logits, box, N, HW, Wl, stride, level, method, slot0, outs):
+def fcos_decode_cont(topkeys, logits, box, N, HW, Wl, stride, level, method, slot0, outs, flags=0):
     K = topkeys.shape[1]
     C = logits.shape[-1]
     BS = box.shape[-1]
     MAXC = outs["scores"].shape[1]
-    call("utv2_fcos_decode_cont", _p(topkeys), K, _p(logits), _p(box), BS, N, HW, Wl, C, stride, level, method, MAXC, slot0,
+    call("utv2_fcos_decode_cont_f", _p(topkeys), K, _p(logits), _p(box), BS, N, HW, Wl, C, stride, level, method, int(flags), MAXC, slot0,
          _p(outs["boxes"]), _p(outs["scores"]), _p(outs["classes"]), _p(outs["locations"]), _p(outs["centerness"]),
          _p(outs["cls_confid"]), _p(outs["reg_pred_std"]), _p(outs["fpn_levels"]), _p(outs["valid"]), _stream())
 

@@ -430,7 +430,7 @@ class FCOSOutputs:
         self.pre_nms_topk_test = fc.PRE_NMS_TOPK_TEST
         self.post_nms_topk_test = fc.POST_NMS_TOPK_TEST
         self.nms_thresh = fc.NMS_TH
-        assert not fc.THRESH_WITH_CTR
+        self.thresh_with_ctr = bool(fc.THRESH_WITH_CTR)   # fcos_outputs.py:148: predict_proposals hands it to the rank / decode kernels
         self.num_classes = fc.NUM_CLASSES
         self.strides = list(fc.FPN_STRIDES)
         assert not cfg.SEMISUPNET.SOFT_CLS_LABEL
@@ -633,6 +633,9 @@ class FCOSOutputs:
         for nm in names:
             if nm not in METHODS:
                 raise ValueError("Undefined nms criteria")
+        # THRESH_WITH_CTR (fcos_outputs.py:1172-1195): a flag next to the criterion the kernels are told - threshold, ranking score and
+        # cls_confid become sigmoid(logit) * sigmoid(ctrness) for every criterion, which then differ in the score transform alone (:1270-1275)
+        twc = hip.FCOS_THRESH_WITH_CTR if self.thresh_with_ctr else 0
         methods = [METHODS[nm] for nm in names]
         M = len(methods)
         meta = head_out["meta"]
@@ -678,7 +681,7 @@ class FCOSOutputs:
                 r0, r1 = meta.rows[l]
                 for method in methods:
                     hip.fcos_rank_keys(logits_all[r0:r1], box_all[r0:r1], self.reg_max, N, h * w, th, method,
-                                       out=keys[o:o + N * widths[l]].view(N, widths[l]), row_stride=widths[l])
+                                       out=keys[o:o + N * widths[l]].view(N, widths[l]), row_stride=widths[l], flags=twc)
                     o += N * widths[l]
             top_all = hip.topk_rows(keys, row_off, L * NV, max(widths), kmax)
             tops = {(l, m): top_all[(l * M + m) * N:(l * M + m + 1) * N, :ks[l]].contiguous() for l in range(L) for m in range(M)}
@@ -693,7 +696,7 @@ class FCOSOutputs:
                         h, w = level_hw[l]
                         r0, r1 = meta.rows[l]
                         hip.fcos_rank_keys(logits_all[r0:r1], box_all[r0:r1], self.reg_max, N, h * w, th, method,
-                                           out=keys[i * N:(i + 1) * N], row_stride=width)
+                                           out=keys[i * N:(i + 1) * N], row_stride=width, flags=twc)
                     top_all = torch.topk(keys, max(ks[l] for l in grp), dim=1, sorted=True).values
                     for i, l in enumerate(grp):
                         tops[(l, m)] = top_all[i * N:(i + 1) * N, :ks[l]].contiguous()
@@ -703,10 +706,11 @@ class FCOSOutputs:
             for l, (h, w) in enumerate(level_hw):
                 r0, r1 = meta.rows[l]
                 if self.reg_max == hip.REG_CONT:
-                    hip.fcos_decode_cont(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], N, h * w, w, self.strides[l], l, method, slot0, outs_m)
+                    hip.fcos_decode_cont(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], N, h * w, w, self.strides[l], l, method, slot0, outs_m,
+                                         flags=twc)
                 else:
                     hip.fcos_decode(tops[(l, m)], logits_all[r0:r1], box_all[r0:r1], self.reg_max, N, h * w, w, self.strides[l], l, method,
-                                    slot0, outs_m)
+                                    slot0, outs_m, flags=twc)
                 slot0 += ks[l]
         keep, cnt = hip.nms_batched(outs["boxes"], outs["scores"], outs["classes"], outs["valid"], self.nms_thresh,
                                     class_aware=True, post_topk=post, max_out=max_det)
