@@ -18,6 +18,18 @@ def r16(t):
 BF = torch.bfloat16
 
 
+@pytest.fixture
+def fp16_build():
+    """the fp16 build of the kernel library (h16_t = _Float16) for the tests written for either 16-bit type; they run on the bf16 build
+    under their own names"""
+    from ubteacher import hip
+    hip.set_h16("fp16")
+    try:
+        yield "fp16"
+    finally:
+        hip.set_h16("bf16")
+
+
 def close16(y, ref):
     """y (bf16 tensor) == RNE(ref') for some ref' within accumulation-order noise of ref"""
     y = y.float()
@@ -588,6 +600,13 @@ def test_big_tile_kernels_bit_identical_across_schedules(tmp_path):
                 {"UTV2_EPI_PLAIN": "0", "UTV2_W8": "0"}):
         lines = [ln for ln in run(env, "cmp", ref).splitlines() if ln.strip()]
         assert len(lines) == 14 and all("bit-identical" in ln and "nan" not in ln for ln in lines), lines
+    # the fp16 build of the same kernels (UTV2_H16_KIND=fp16): the default schedule and the general epilogue against its own 128-tile save
+    f16 = {"UTV2_H16_KIND": "fp16"}
+    ref16 = str(tmp_path / "ref16.pt")
+    run(dict(f16, UTV2_W8="0"), "save", ref16)
+    for env in ({}, {"UTV2_EPI_PLAIN": "0"}):
+        lines = [ln for ln in run(dict(f16, **env), "cmp", ref16).splitlines() if ln.strip()]
+        assert len(lines) == 14 and all("bit-identical" in ln and "nan" not in ln for ln in lines), lines
 
 
 @pytest.mark.parametrize("dt", [torch.float32, BF])
@@ -703,6 +722,13 @@ def test_fused_frozen_bottleneck_equals_the_conv_chain(shape, shortcut):
     assert torch.equal(y, hip.bottleneck_fwd_bf16(x, w1, w2, w3, s1, b1, s2, b2, s3, b3, **kw))     # deterministic
 
 
+@pytest.mark.parametrize("shortcut", [False, True])
+@pytest.mark.parametrize("shape", [(2, 24, 48), (1, 21, 37), (3, 8, 16), (1, 5, 7)])
+def test_fused_frozen_bottleneck_equals_the_conv_chain_on_the_fp16_build(shape, shortcut, fp16_build):
+    """the same test on libutv2_hip_f16.so: its 2^-10 / 3e-3 branches"""
+    test_fused_frozen_bottleneck_equals_the_conv_chain(shape, shortcut)
+
+
 @pytest.mark.parametrize("hw", [(64, 96), (70, 66), (800, 1344), (33, 18)])
 def test_fused_stem_pool_equals_stem_conv_then_maxpool(hw):
     """csrc/stem_pool.hip (round 4): the frozen BasicStem conv (7x7 s2 p3 + FrozenBN + ReLU) and max_pool2d(3, 2, 1) as one kernel with
@@ -739,6 +765,12 @@ def test_fused_stem_pool_equals_stem_conv_then_maxpool(hw):
     t = F.max_pool2d(t, 3, 2, 1)
     assert relerr(y.float().permute(0, 3, 1, 2), t) < (2e-2 if h16 == torch.bfloat16 else 3e-3)
     assert torch.equal(y, hip.stem_pool_fwd_bf16(x4, w16s, sc, sh))
+
+
+@pytest.mark.parametrize("hw", [(64, 96), (70, 66), (800, 1344), (33, 18)])
+def test_fused_stem_pool_equals_stem_conv_then_maxpool_on_the_fp16_build(hw, fp16_build):
+    """the same test on libutv2_hip_f16.so: its 2^-10 / 3e-3 branches"""
+    test_fused_stem_pool_equals_stem_conv_then_maxpool(hw)
 
 
 @pytest.mark.parametrize("case", [(40, 300, 3, 128, 256), (48, 350, 2, 128, 256), (34, 1000, 1, 128, 256), (8, 37, 131, 192, 384), (3, 111, 107, 256, 512)])
@@ -789,6 +821,11 @@ def test_big_tile_weight_gradients_are_deterministic_across_processes(tmp_path):
 
     run({}, "save", ref)
     lines = [ln for ln in run({}, "cmp", ref).splitlines() if ln.strip() and "amdgpu" not in ln]
+    assert len(lines) == 7 and all("bit-identical" in ln and "nan" not in ln for ln in lines), lines
+    f16 = {"UTV2_H16_KIND": "fp16"}       # the fp16 build
+    ref16 = str(tmp_path / "wref16.pt")
+    run(f16, "save", ref16)
+    lines = [ln for ln in run(f16, "cmp", ref16).splitlines() if ln.strip() and "amdgpu" not in ln]
     assert len(lines) == 7 and all("bit-identical" in ln and "nan" not in ln for ln in lines), lines
 
 

@@ -227,3 +227,21 @@ def test_narrow_prediction_convs_on_the_96_wide_tile(K, out_dtype):
     # bit-deterministic
     y3 = hip.conv2d_ml_fwd_bf16(x[:, :C], w, level_hw, N, bias=b, k=3, pad=1, out_dtype=od, relu=True)
     assert torch.equal(y2, y3)
+
+
+@pytest.fixture
+def fp16_build():
+    """the fp16 build of the kernel library (h16_t = _Float16)"""
+    from ubteacher import hip
+    hip.set_h16("fp16")
+    try:
+        yield "fp16"
+    finally:
+        hip.set_h16("bf16")
+
+
+@pytest.mark.parametrize("K", [80, 72, 96])
+@pytest.mark.parametrize("out_dtype", ["f32", "h16"])
+def test_narrow_prediction_convs_on_the_96_wide_tile_on_the_fp16_build(K, out_dtype, fp16_build):
+    """the same test on libutv2_hip_f16.so: its 2^-10 branch"""
+    test_narrow_prediction_convs_on_the_96_wide_tile(K, out_dtype)

@@ -6,7 +6,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "unbiased-teacher-v2_amd"))
 import torch
 from ubteacher import hip
-BF = torch.bfloat16
+hip.set_h16(os.environ.get("UTV2_H16_KIND", "bf16"))   # the build under test: bf16 (default) or fp16
+BF = hip.h16_dtype()
 torch.manual_seed(0)
 outs = {}
 level_hw = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
