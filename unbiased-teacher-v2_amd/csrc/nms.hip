@@ -21,6 +21,7 @@
 
 __device__ __forceinline__ unsigned order_bits_desc(float s) {
   unsigned u = __float_as_uint(s);
+  if ((u << 1) == 0u) u = 0u;  // -0.0 and +0.0 are one score (the oracle compares values): the slot index decides between them
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending-order transform
   return ~u;                                       // descending
 }
