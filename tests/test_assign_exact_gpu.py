@@ -250,7 +250,7 @@ def test_nms_buckets_of_64_and_65_pairs_on_the_threshold_and_signed_zero_scores(
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # top-k and the RPN decode
-@pytest.mark.parametrize("k", [1, 2, 1000, 8192])
+@pytest.mark.parametrize("k", [1, 2, 3, 1000, 8192])
 def test_topk_rows_on_k_boundaries_digits_and_row_shapes(k):
     from ubteacher import hip
     flat, off, width, census = R.topk_case(k)

@@ -212,18 +212,24 @@ def test_decode_nms(fc, method):
         close(r.reg_pred_std, fc["thrcc_%s_%d_std" % (method, i)])
 
 
+def _random_nms_case(g, N, M):
+    """random overlapping float boxes, every 7th score tied at 0.5, 5 classes, ~10 % invalid slots"""
+    ctr = torch.rand(N, M, 2, generator=g) * 300
+    wh = torch.rand(N, M, 2, generator=g) * 80 + 4
+    boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], dim=2)
+    scores = torch.rand(N, M, generator=g)
+    scores[:, ::7] = 0.5  # ties
+    cls = torch.randint(0, 5, (N, M), generator=g, dtype=torch.int32)
+    valid = (torch.rand(N, M, generator=g) > 0.1).to(torch.uint8)
+    return boxes, scores, cls, valid
+
+
 def test_nms_bit_exact_vs_oracle():
     """NMS index selection must be bit-exact (north star): random overlapping boxes incl. score ties."""
     from ubteacher import hip
     g = torch.Generator().manual_seed(5)
     for (N, M, thr, aware) in [(2, 700, 0.6, True), (1, 3000, 0.7, False), (3, 130, 0.5, True), (1, 64, 0.3, True)]:
-        ctr = torch.rand(N, M, 2, generator=g) * 300
-        wh = torch.rand(N, M, 2, generator=g) * 80 + 4
-        boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], dim=2)
-        scores = torch.rand(N, M, generator=g)
-        scores[:, ::7] = 0.5  # ties
-        cls = torch.randint(0, 5, (N, M), generator=g, dtype=torch.int32)
-        valid = (torch.rand(N, M, generator=g) > 0.1).to(torch.uint8)
+        boxes, scores, cls, valid = _random_nms_case(g, N, M)
         keep, cnt = hip.nms_batched(boxes.to(DEV), scores.to(DEV), cls.to(DEV), valid.to(DEV), thr, class_aware=aware,
                                     post_topk=-1, max_out=M)
         keep, cnt = keep.cpu(), cnt.cpu()
@@ -236,6 +242,35 @@ def test_nms_bit_exact_vs_oracle():
             ref = vi[ref]
             assert int(cnt[n]) == len(ref)
             assert torch.equal(keep[n, : len(ref)].long(), ref)
+
+
+def test_nms_class_agnostic_more_than_64_chunks_in_one_bucket():
+    """A call that is not class-aware is the one-bucket case of the bucketed chain: with more than 64 chunks of 64 valid candidates
+    the scanning wave keeps its removed set in two words per lane (chunks 64.. live in the second).  Same generator and oracle as
+    test_nms_bit_exact_vs_oracle; the post_topk leg applies the kthvalue rule to the oracle's result as tests/assign_ref.py states it:
+    with more than post_topk kept, every kept slot whose score >= the post_topk-th kept score stays."""
+    from ubteacher import hip
+    g = torch.Generator().manual_seed(11)
+    M, thr, post = 4800, 0.7, 100
+    boxes, scores, cls, valid = _random_nms_case(g, 1, M)
+    vi = valid[0].bool().nonzero().squeeze(1)
+    assert len(vi) > 65 * 64
+    ref = vi[O.nms(boxes[0][vi], scores[0][vi], thr)]
+    assert len(ref) > post
+    order = vi[np.lexsort((vi.numpy(), -scores[0][vi].numpy().astype(np.float64)))]      # (score desc, slot asc)
+    kept = torch.zeros(M, dtype=torch.bool)
+    kept[ref] = True
+    assert bool((~kept[order[64 * 64:]]).any())     # a candidate of chunk 64.. is suppressed: a bit of the second removed-set word
+    kth = scores[0][ref[post - 1]]
+    ref_post = ref[scores[0][ref] >= kth]
+    assert len(ref_post) >= post
+    for post_topk, want in ((-1, ref), (post, ref_post)):
+        keep, cnt = hip.nms_batched(boxes.to(DEV), scores.to(DEV), cls.to(DEV), valid.to(DEV), thr, class_aware=False,
+                                    post_topk=post_topk, max_out=M)
+        keep, cnt = keep.cpu(), cnt.cpu()
+        assert int(cnt[0]) == len(want)
+        assert torch.equal(keep[0, : len(want)].long(), want)
+        assert bool((keep[0, len(want):] == -1).all())
 
 
 def test_ema_bit_exact():

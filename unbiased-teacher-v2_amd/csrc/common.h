@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define UTV2_OK 0
 #define UTV2_EARG (-1000)
@@ -118,6 +119,52 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
   if (wid == 0) r = wave_reduce_sum(r);
   __syncthreads();
   return r;
+}
+
+// Bitonic sort of keys[0 .. npow2) in LDS (npow2 a power of two >= 2), ascending or DESCending, by the whole block: every thread calls
+// it, any blockDim.x.  The caller's barrier orders its key fill before the call; the sort ends with a barrier, so the sorted keys - and
+// whatever else the block wrote to LDS before the call - may be read right after it.
+template <bool DESC, typename K>
+__device__ __forceinline__ void lds_bitonic_sort(K* keys, int npow2) {
+  for (int k = 2; k <= npow2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (npow2 >> 1); t += blockDim.x) {   // pair t: (i, i + j) with bit j of i clear
+        const int i = 2 * t - (t & (j - 1)), l = i + j;
+        const K a = keys[i], b = keys[l];
+        const bool fwd = (i & k) == 0;   // this run of k sorts in the wanted direction, the next one against it
+        // the comparisons are the callers' own, kept so that their code stays as it was: ascending exchanges on one compare (equal
+        // keys, i.e. padding, may trade places in a reverse run), descending compares strictly both ways
+        if (DESC ? (fwd ? a < b : a > b) : (a > b) == fwd) { keys[i] = b; keys[l] = a; }
+      }
+      __syncthreads();
+    }
+}
+
+// D2 pairwise_iou [D2-recall]: inter > 0 ? inter / (area_a + area_b - inter) : 0.  The matching, low-quality and box_iou kernels
+// agree to the last bit because they share this one expression (and the build's -ffp-contract=off): keep its operand order.
+__device__ __forceinline__ float iou_d2(const float4& a, const float4& b) {
+  const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
+  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
+  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+  const float inter = w * h;
+  return inter > 0.f ? inter / (aa + ab - inter) : 0.f;
+}
+
+// Does image n have a valid gt?  Called by every thread of the block (it holds a barrier); the answer is uniform across the block.
+__device__ __forceinline__ int block_any_gt_valid(const unsigned char* gt_valid, int n, int G) {
+  int any = 0;
+  for (int g = threadIdx.x; g < G; g += blockDim.x) any |= gt_valid[(size_t)n * G + g];
+  return __syncthreads_or(any);
+}
+
+// A/B switches for bench runs and tests.  Callers keep the result in a static: read once per process, never on the launch path.
+static inline bool env_on(const char* name) {   // on unless set to "0..."
+  const char* v = getenv(name);
+  return !(v && v[0] == '0');
+}
+static inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1370,16 +1370,8 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_rs(ConvArgs16 p) {
 
 // A/B switches for bench runs and tests, read ONCE per process (never on the launch path): UTV2_W8=0 keeps every forward / dgrad
 // row on the 128 x 128 kernel, UTV2_WGRAD_W8=0 keeps every wgrad on the 128 x 128 kernel.
-static bool env_flag_on(const char* name) {
-  const char* v = getenv(name);
-  return !(v && v[0] == '0');
-}
-static const bool g_use_w8 = env_flag_on("UTV2_W8");
-static const bool g_use_wgrad_w8 = env_flag_on("UTV2_WGRAD_W8");
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
+static const bool g_use_w8 = env_on("UTV2_W8");
+static const bool g_use_wgrad_w8 = env_on("UTV2_WGRAD_W8");
 static const int g_epi_general = env_int("UTV2_EPI_PLAIN", 1) ? 0 : 2;   // OR-ed into ConvArgs16::relu (see epilogue_rows)
 static const int g_use_pp = env_int("UTV2_PP", 2) == 1 ? 1 : 2;  // 256 x 256 forward tile, ping-pong schedule: 2 = persistent grid of 256 workgroups,
                                                                  // 1 = one tile per workgroup

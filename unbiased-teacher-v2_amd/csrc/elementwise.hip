@@ -1111,7 +1111,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply(GnSegs sg, const T* __restri
   }
 }
 
-static const bool g_gn_reverse = [] { const char* v = getenv("UTV2_GN_REVERSE"); return !(v && v[0] == '0'); }();   // A/B switch, read once
+static const bool g_gn_reverse = env_on("UTV2_GN_REVERSE");   // A/B switch, read once
 
 // chunks of nseg consecutive segments (a chunk never straddles a segment)
 static int64_t gn_chunks(int nseg, const int* seg_rows) {

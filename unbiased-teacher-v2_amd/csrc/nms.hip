@@ -12,11 +12,11 @@
 //   * suppress j (later in the order) when inter / (area_i + area_j - inter) > thr (strict);
 //   * kept slots are returned in descending-score order; optional post-top-k keeps every kept
 //     slot whose score >= the k-th kept score (kthvalue rule, fcos_outputs.py:1309-1318).
-// Stage 1 (one block per image): max-coordinate reduce + LDS bitonic sort of 64-bit keys.
-// Stage 2: 64x64 IoU bit-mask tiles, boxes staged in LDS, upper triangle only.
-// Stage 3 (one wave per image): chunked scan - 64 rows resolved with register bit ops and
-//          v_readlane broadcasts, then the kept rows' mask words OR-ed in coalesced.
-// Class-aware calls run stages 2-3 per class bucket (see "Bucketed pipeline" below).
+// One chain for every call: nms_sort_kernel (one block per image: max-coordinate reduce + LDS bitonic sort of 64-bit keys), then the
+// bucketed pipeline below - partition by class bucket, 64x64 IoU bit-mask tiles per bucket (boxes staged in LDS, upper triangle only),
+// one scanning wave per (bucket, image) (64 rows resolved with register bit ops and v_readlane broadcasts, then the kept rows' mask
+// words OR-ed in coalesced), one emitting wave per image.  A call that is not class-aware sorts every candidate into class 0 with
+// no coordinate offset: it is the one-bucket case of the same kernels.
 #include "common.h"
 
 __device__ __forceinline__ unsigned order_bits_desc(float s) {
@@ -53,19 +53,7 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(const float* __restrict_
   float maxc = -INFINITY;
   int total = 0;
   for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { maxc = fmaxf(maxc, redmax[w]); total += redcnt[w]; }
-  // bitonic sort ascending
-  for (int k = 2; k <= Mpad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (Mpad >> 1); t += blockDim.x) {  // pair t: (i, i + j) with bit j of i clear
-        const int i = 2 * t - (t & (j - 1));
-        const int ixj = i + j;
-        const unsigned long long a = keys[i], c = keys[ixj];
-        const bool up = ((i & k) == 0);
-        if ((a > c) == up) { keys[i] = c; keys[ixj] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort<false>(keys, Mpad);   // the barrier above orders the key fill (and redmax / redcnt) before it
   if (threadIdx.x == 0) nvalid[n] = total;
   const float off1 = maxc + 1.f;
   for (int i = threadIdx.x; i < Mpad; i += blockDim.x) {
@@ -92,107 +80,13 @@ __device__ __forceinline__ bool iou_gt(const float4& a, const float4& b, float t
   return inter / (aa + ab - inter) > thr;
 }
 
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ sboxes, const int* __restrict__ nvalid, int Mpad,
-                                                    float thr, unsigned long long* __restrict__ mask) {
-  const int n = blockIdx.z, rb = blockIdx.y, cb = blockIdx.x;
-  if (cb < rb) return;
-  const int nv = nvalid[n];
-  if (rb * 64 >= nv || cb * 64 >= nv) return;
-  __shared__ float4 cbox[64];
-  const int t = threadIdx.x;
-  cbox[t] = ((const float4*)sboxes)[(size_t)n * Mpad + cb * 64 + t];
-  __syncthreads();
-  const int i = rb * 64 + t;
-  unsigned long long bits = 0;
-  if (i < nv) {
-    const float4 a = ((const float4*)sboxes)[(size_t)n * Mpad + i];
-    const int jn = min(64, nv - cb * 64);
-    for (int j = 0; j < jn; ++j) {
-      const int gj = cb * 64 + j;
-      if (gj > i && iou_gt(a, cbox[j], thr)) bits |= 1ull << j;
-    }
-  }
-  const int W = Mpad >> 6;
-  mask[((size_t)n * Mpad + i) * W + cb] = bits;
-}
-
 __device__ __forceinline__ unsigned long long bcast64(unsigned long long v, int lane) {
   const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)(v & 0xFFFFFFFFull), lane);
   const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
   return ((unsigned long long)hi << 32) | lo;
 }
 
-#define NMS_MAXW 4  // words per lane: Mpad <= 64*64*4 = 16384
-__global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* __restrict__ mask, const int* __restrict__ sidx,
-                                                    const int* __restrict__ nvalid, const float* __restrict__ scores, int M,
-                                                    int Mpad, int post_topk, int max_out, int* __restrict__ keep,
-                                                    int* __restrict__ keep_count) {
-  const int n = blockIdx.x, lane = threadIdx.x;
-  const int W = Mpad >> 6;
-  const int nv = nvalid[n];
-  const int nchunks = (nv + 63) >> 6;
-  unsigned long long removed[NMS_MAXW];
-#pragma unroll
-  for (int s = 0; s < NMS_MAXW; ++s) removed[s] = 0ull;
-  int count = 0;
-  const unsigned long long* mrow = mask + (size_t)n * Mpad * W;
-  for (int c = 0; c < nchunks; ++c) {
-    // removed word c lives in lane c%64, slot c/64
-    unsigned long long rw = 0ull;
-#pragma unroll
-    for (int s = 0; s < NMS_MAXW; ++s)
-      if ((c >> 6) == s) rw = bcast64(removed[s], c & 63);
-    const int row = c * 64 + lane;
-    const unsigned long long diag = (row < nv) ? mrow[(size_t)row * W + c] : 0ull;
-    const int rows_here = min(64, nv - c * 64);
-    unsigned long long keepbits = 0ull;
-    for (int b = 0; b < rows_here; ++b) {
-      const unsigned long long db = bcast64(diag, b);
-      if (!((rw >> b) & 1ull)) { keepbits |= 1ull << b; rw |= db; }
-    }
-    // emit kept slots of this chunk in order
-    if (row < nv && ((keepbits >> lane) & 1ull)) {
-      const int pos = count + __popcll(keepbits & ((1ull << lane) - 1ull));
-      if (pos < max_out) keep[(size_t)n * max_out + pos] = sidx[(size_t)n * Mpad + row];
-    }
-    count += __popcll(keepbits);
-    // OR the kept rows' mask words into removed (words > c only matter)
-    unsigned long long kb = keepbits;
-    while (kb) {
-      const int b = __ffsll((long long)kb) - 1;
-      kb &= kb - 1ull;
-      const unsigned long long* r = mrow + (size_t)(c * 64 + b) * W;
-#pragma unroll
-      for (int s = 0; s < NMS_MAXW; ++s) {
-        const int w = s * 64 + lane;
-        if (w < nchunks && w > c) removed[s] |= r[w];
-      }
-    }
-    // kthvalue rule below keeps only scores >= the post_topk-th kept score; candidates are in descending score order,
-    // so once post_topk are kept and the next chunk starts below that score nothing later can survive: stop scanning
-    if (post_topk > 0 && post_topk <= max_out && count >= post_topk && (c + 1) * 64 < nv) {
-      __syncthreads();  // single wave: keep[] stores of this wave are visible to its loads
-      const float kth = scores[(size_t)n * M + keep[(size_t)n * max_out + post_topk - 1]];
-      const float nxt = scores[(size_t)n * M + sidx[(size_t)n * Mpad + (c + 1) * 64]];
-      if (nxt < kth) break;
-    }
-  }
-  if (count > max_out) count = max_out;
-  __syncthreads();  // single wave: orders the keep[] stores before the reads below
-  // kthvalue rule: keep all with score >= score of the post_topk-th kept
-  if (post_topk > 0 && count > post_topk) {
-    const float thr = scores[(size_t)n * M + keep[(size_t)n * max_out + post_topk - 1]];
-    int c2 = 0;
-    for (int base = 0; base < count; base += 64) {
-      const int i = base + lane;
-      const bool ok = i < count && scores[(size_t)n * M + keep[(size_t)n * max_out + i]] >= thr;
-      c2 += __popcll(__ballot(ok));
-    }
-    count = c2;
-  }
-  if (lane == 0) keep_count[n] = count;
-  for (int i = count + lane; i < max_out; i += 64) keep[(size_t)n * max_out + i] = -1;
-}
+#define NMS_MAXW 4  // removed-set words per lane of a scanning wave: a bucket holds <= 64 * NMS_MAXW chunks, Mpad <= 64*64*4 = 16384
 
 // ---------------------------------------------------------------------------------------------
 // Bucketed pipeline.  Boxes of different classes never suppress each other (the coordinate trick makes their IoU exactly 0), so the
@@ -200,8 +94,9 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* 
 // buckets by class % NMS_NB (any class ids: two classes that share a bucket still have IoU 0 through the trick); every bucket gets its
 // own small IoU bit matrix (rows of W_b = chunks of the bucket words, instead of one M x M matrix: 13x fewer tiles and 8x shorter rows
 // for the RPN's 5 levels x 2000) and its own scanning wave (grid NMS_NB x N instead of one block per image walking every chunk of
-// the image); the kept candidates are marked in a global-order bit array from which one wave per image emits the result, exactly as
-// the single-chain scan does.  Non-class-aware calls are the one-bucket case.
+// the image); the kept candidates are marked in a global-order bit array from which one wave per image emits the result.  Non-class-aware
+// calls are the one-bucket case: nms_sort_kernel gives every candidate class 0, so all of them land in bucket 0 (up to 64 * NMS_MAXW
+// chunks, which is why the scanning wave carries NMS_MAXW removed-set words per lane).
 #define NMS_NB 32
 #define NMS_BTAB (2 * NMS_NB + 2)  // per image: boff[NMS_NB + 1] (64-aligned first position of each bucket in bucket order), bcnt[NMS_NB], tiles
 
@@ -429,7 +324,7 @@ __global__ __launch_bounds__(64) void nms_emit_kernel(const unsigned long long* 
   for (int i = cnt + lane; i < max_out; i += 64) keep[(size_t)n * max_out + i] = -1;
 }
 
-// pairwise IoU  (D2 pairwise_iou [D2-recall]): iou = inter > 0 ? inter / (a1 + a2 - inter) : 0
+// pairwise IoU  (D2 pairwise_iou [D2-recall]): iou_d2 of common.h, the rule the matching kernels use
 __global__ __launch_bounds__(256) void box_iou_kernel(const float* __restrict__ a, const float* __restrict__ b, int A, int B,
                                                     float* __restrict__ out) {
   // out[A][B]; block covers 256 columns of b for one row tile of 8 a-boxes
@@ -437,17 +332,11 @@ __global__ __launch_bounds__(256) void box_iou_kernel(const float* __restrict__ 
   const int i0 = blockIdx.y * 8;
   float4 bb = make_float4(0, 0, 0, 0);
   if (j < B) bb = ((const float4*)b)[j];
-  const float ab = (bb.z - bb.x) * (bb.w - bb.y);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int i = i0 + k;
     if (i >= A || j >= B) continue;
-    const float4 aa = ((const float4*)a)[i];
-    const float area = (aa.z - aa.x) * (aa.w - aa.y);
-    const float w = fmaxf(fminf(aa.z, bb.z) - fmaxf(aa.x, bb.x), 0.f);
-    const float h = fmaxf(fminf(aa.w, bb.w) - fmaxf(aa.y, bb.y), 0.f);
-    const float inter = w * h;
-    out[(size_t)i * B + j] = inter > 0.f ? inter / (area + ab - inter) : 0.f;
+    out[(size_t)i * B + j] = iou_d2(((const float4*)a)[i], bb);
   }
 }
 
@@ -463,12 +352,11 @@ int utv2_nms_mpad(int M) { return next_pow2(M); }
 
 static inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
-// workspace layout: sorted boxes, sorted idx, sorted class, nvalid, then either the single M x M mask (non-class-aware) or the bucket
-// tables + per-bucket masks (class-aware)
+// workspace layout: sorted boxes, sorted idx, sorted class, nvalid, then the bucket tables, the kept bits and the per-bucket masks
 struct NmsLayout {
   int Mpad, Wt, Ptot;
-  int64_t maskwords;  // per image, bucketed
-  int64_t sboxes, sidx, scls, nvalid, tail;          // byte offsets
+  int64_t maskwords;  // per image: >= sum over buckets of 64 * wb^2 for any split of <= Wt chunks, all in one bucket included
+  int64_t sboxes, sidx, scls, nvalid;                // byte offsets
   int64_t cbox, gpos, btab, toff, moff, keepw, bmask, total;
 };
 static NmsLayout nms_layout(int N, int M) {
@@ -482,8 +370,6 @@ static NmsLayout nms_layout(int N, int M) {
   L.sidx = o; o += (int64_t)N * L.Mpad * 4;
   L.scls = o; o += (int64_t)N * L.Mpad * 4;
   L.nvalid = o; o += 64 * (int64_t)N;
-  L.tail = o;
-  const int64_t single = o + (int64_t)N * L.Mpad * (L.Mpad / 64) * 8;
   L.cbox = o; o = align16(o + (int64_t)N * L.Ptot * 16);
   L.gpos = o; o = align16(o + (int64_t)N * L.Ptot * 4);
   L.btab = o; o = align16(o + (int64_t)N * NMS_BTAB * 4);
@@ -491,7 +377,7 @@ static NmsLayout nms_layout(int N, int M) {
   L.moff = o; o = align16(o + (int64_t)N * NMS_NB * 8);
   L.keepw = o; o = align16(o + (int64_t)N * (L.Mpad / 64) * 8);
   L.bmask = o; o += (int64_t)N * L.maskwords * 8;
-  L.total = o > single ? o : single;
+  L.total = o;
   return L;
 }
 
@@ -505,7 +391,7 @@ int utv2_nms_batched(const float* boxes, const float* scores, const int* cls, co
   if (!boxes || !scores || !valid || !keep || !keep_count || !ws || M < 1 || (class_aware && !cls)) return UTV2_EARG;
   const NmsLayout L = nms_layout(N, M);
   const int Mpad = L.Mpad;
-  if (Mpad > 64 * 64 * NMS_MAXW) return UTV2_EARG;
+  if (Mpad > 64 * 64 * NMS_MAXW) return UTV2_EARG;   // one bucket may hold every candidate: ceil(M / 64) <= 64 * NMS_MAXW chunks
   char* p = (char*)ws;
   float* sboxes = (float*)(p + L.sboxes);
   int* sidx = (int*)(p + L.sidx);
@@ -515,15 +401,6 @@ int utv2_nms_batched(const float* boxes, const float* scores, const int* cls, co
   (void)hipFuncSetAttribute((const void*)nms_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(nms_sort_kernel, dim3(N), dim3(1024), lds, stream, boxes, scores, cls, valid, M, Mpad, class_aware, sboxes,
                      sidx, scls, nvalid);
-  if (!class_aware) {
-    unsigned long long* mask = (unsigned long long*)(p + L.tail);
-    const int nb = Mpad / 64;
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(nb, nb, N), dim3(64), 0, stream, (const float*)sboxes, (const int*)nvalid, Mpad,
-                       iou_thr, mask);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(N), dim3(64), 0, stream, (const unsigned long long*)mask, (const int*)sidx,
-                       (const int*)nvalid, scores, M, Mpad, post_topk, max_out, keep, keep_count);
-    return utv2_launch_status();
-  }
   float* cbox = (float*)(p + L.cbox);
   int* gpos = (int*)(p + L.gpos);
   int* btab = (int*)(p + L.btab);

@@ -10,13 +10,6 @@
 //   arg[n][p]      = first g (compacted order) attaining it
 //   gt_max[n][g]   = max_p IoU (as float bits, via atomicMax; IoU >= 0 so bit order == value order)
 #define MB_MAXG 256
-__device__ __forceinline__ float iou_d2(const float4& a, const float4& b) {
-  const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-  const float inter = w * h;
-  return inter > 0.f ? inter / (aa + ab - inter) : 0.f;
-}
 
 // valid gts of image n, compacted in their original order (256 threads, G <= MB_MAXG): sidx[k] = k-th valid slot; returns their number
 __device__ __forceinline__ int compact_valid_gts(const unsigned char* __restrict__ gt_valid, int n, int G, int* sidx, int* wcnt) {
@@ -90,11 +83,6 @@ __global__ __launch_bounds__(256) void match_lowq_kernel(const float* __restrict
   for (int k = 0; k < scount; ++k)
     if (iou_d2(sg[k], b) == smax[k]) f = 1;
   lowq[(size_t)n * P + p] = f;
-}
-
-static bool env_on(const char* name) {   // A/B switches, read once per process: on unless set to "0"
-  const char* v = getenv(name);
-  return !(v && v[0] == '0');
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1066,9 +1054,7 @@ __global__ __launch_bounds__(256) void rpn_sample_keys_kernel(const float* __res
                                                             const float* __restrict__ keys, int N, int R, float lo, float hi,
                                                             long long* __restrict__ out) {
   const int n = blockIdx.y;
-  int any = 0;
-  for (int g = threadIdx.x; g < G; g += blockDim.x) any |= gt_valid[(size_t)n * G + g];
-  const int has_gt = __syncthreads_or(any);
+  const int has_gt = block_any_gt_valid(gt_valid, n, G);
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   const size_t o = (size_t)n * R + r;
@@ -1088,8 +1074,8 @@ __global__ __launch_bounds__(256) void rpn_sample_unpack_kernel(const long long*
                                                               long long* __restrict__ neg_idx, unsigned char* __restrict__ neg_valid,
                                                               unsigned char* __restrict__ has_gt) {
   const int n = blockIdx.x;
-  int any = 0, cnt = 0;
-  for (int g = threadIdx.x; g < G; g += blockDim.x) any |= gt_valid[(size_t)n * G + g];
+  const int any = block_any_gt_valid(gt_valid, n, G);
+  int cnt = 0;
   for (int j = threadIdx.x; j < npos_max; j += blockDim.x) {
     const long long key = j < k ? top[(size_t)n * k + j] : -1;
     const bool ok = key >= 0;
@@ -1097,7 +1083,6 @@ __global__ __launch_bounds__(256) void rpn_sample_unpack_kernel(const long long*
     pos_valid[(size_t)n * npos_max + j] = ok;
     cnt += ok;
   }
-  any = __syncthreads_or(any);
   __shared__ int npos;
   if (threadIdx.x == 0) npos = 0;
   __syncthreads();
@@ -1131,10 +1116,8 @@ __global__ __launch_bounds__(512) void roi_sample_kernel(const float* __restrict
   __shared__ unsigned long long sk[ROI_SAMPLE_MAX];
   __shared__ int cnt[2];
   const int n = blockIdx.x, t = threadIdx.x;
-  int any = 0;
-  for (int g = t; g < G; g += blockDim.x) any |= gt_valid[(size_t)n * G + g];
   if (t < 2) cnt[t] = 0;
-  const int has_gt = __syncthreads_or(any);
+  const int has_gt = block_any_gt_valid(gt_valid, n, G);   // its barrier also orders the zeroing of cnt[] before the atomics below
   for (int i = t; i < npow2; i += blockDim.x) {
     unsigned long long grp = 2, kb = 0;
     if (i < P && pv[(size_t)n * P + i]) {
@@ -1147,16 +1130,7 @@ __global__ __launch_bounds__(512) void roi_sample_kernel(const float* __restrict
     sk[i] = (grp << 60) | (kb << 20) | (unsigned long long)i;
   }
   __syncthreads();
-  for (int k = 2; k <= npow2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int q = t; q < (npow2 >> 1); q += blockDim.x) {
-        const int i = 2 * q - (q & (j - 1)), l = i + j;   // i has bit j clear, l = i | j
-        const unsigned long long a = sk[i], b = sk[l];
-        const bool up = (i & k) == 0;
-        if ((a > b) == up) { sk[i] = b; sk[l] = a; }
-      }
-      __syncthreads();
-    }
+  lds_bitonic_sort<false>(sk, npow2);   // ends with a barrier: cnt[] is complete for every thread
   const int nfg = cnt[0], nbg = cnt[1];
   const int fsel = nfg < nfg_max ? nfg : nfg_max;
   const int bsel = nbg < B - fsel ? nbg : B - fsel;

@@ -174,18 +174,7 @@ __global__ __launch_bounds__(256) void topk_sort_kernel(const int* __restrict__ 
       if (s0 + i < kpad) sk[s0 + i] = src[i];
   }
   __syncthreads();
-  for (int size = 2; size <= kpad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = threadIdx.x; i < kpad / 2; i += blockDim.x) {
-        const int lo = 2 * i - (i & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const long long a = sk[lo], b = sk[hi];
-        if (desc ? a < b : a > b) { sk[lo] = b; sk[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort<true>(sk, kpad);
   long long* o = out + (size_t)row * k;
   for (int i = threadIdx.x; i < k; i += blockDim.x) o[i] = sk[i];
 }

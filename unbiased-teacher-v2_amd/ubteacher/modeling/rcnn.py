@@ -438,6 +438,55 @@ class PseudoLabRPN:
 
 
 # ---------------------------------------------------------------------------------------------------
+_DEVICE_CONSTS = {}
+
+
+def _device_const(key, make):
+    """Small device tensors that depend on shapes / image sizes only, built once: a fresh torch.tensor(..., device=cuda) is a
+    synchronizing pageable copy."""
+    t = _DEVICE_CONSTS.get(key)
+    if t is None:
+        if len(_DEVICE_CONSTS) >= 16:
+            _DEVICE_CONSTS.clear()
+        t = _DEVICE_CONSTS[key] = make()
+    return t
+
+
+def _image_hwt(image_sizes, device):
+    """[N, 1, 4] (w, h, w, h) per image: the clip bounds of the decoded boxes"""
+    return _device_const(("hwt", tuple(image_sizes), str(device)),
+                         lambda: torch.tensor([[s[1], s[0], s[1], s[0]] for s in image_sizes], dtype=torch.float32, device=device)[:, None, :])
+
+
+def _roi_inference_aten(probs, boxes, ok, proposals, K, nbox, thr, nms_thr, D, kk, std=None):
+    """The ATen chain of D2 fast_rcnn_inference behind a predictor's own decode: probs [N, P, K] foreground probabilities, boxes
+    [N, P, nbox, 4] decoded, ok [N, P] rows that are valid and finite.  Clip, score > thr, the kk best (probability desc, flat index
+    asc) candidates, class-aware NMS, the first D survivors; returns (padded detections, kept proposal rows).  pred_boxes_std = the
+    kept rows' std logits when the predictor has them (std [N * P, 4 * nbox])."""
+    N, P = ok.shape
+    boxes = torch.minimum(boxes.clamp(min=0), _image_hwt(proposals.image_sizes, boxes.device)[:, :, None, :])
+    cand = (probs > thr) & ok[:, :, None]
+    flat = torch.where(cand, probs, torch.full_like(probs, -1.0)).reshape(N, P * K)
+    top = torch.topk(float_order_key(flat), kk, dim=1, sorted=True).values
+    idx = 4294967295 - (top & 4294967295)
+    sc = torch.gather(flat, 1, idx)
+    r, c = idx // K, (idx % K).to(torch.int32)
+    # the box of the row (nbox == 1) or of (row, class)
+    cb = torch.gather(boxes.reshape(N, P * nbox, 4), 1, (r if nbox == 1 else idx)[:, :, None].expand(-1, -1, 4)).contiguous()
+    valid = (sc > thr).to(torch.uint8)
+    kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), nms_thr, class_aware=True, post_topk=-1, max_out=D)
+    ix = kidx.clamp(min=0).long()
+    keep_rows = torch.gather(r, 1, ix)
+    extra = {}
+    if std is not None:
+        extra["pred_boxes_std"] = torch.gather(std.reshape(N, P, 4 * nbox), 1, keep_rows[:, :, None].expand(-1, -1, 4 * nbox)).contiguous()
+    out = PaddedBoxes(proposals.image_sizes,
+                      boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
+                      scores=torch.gather(sc, 1, ix).contiguous(), classes=torch.gather(c, 1, ix).contiguous(),
+                      valid=(torch.arange(D, device=cb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt, **extra)
+    return out, keep_rows
+
+
 class FastRCNNFocaltLossBoundaryVarOutputLayers:
     """Predictor + losses + inference (reference fast_rcnn.py:715-1292)."""
     focal_gamma = 1.5  # comput_focal_loss, fast_rcnn.py:925-936
@@ -524,13 +573,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
         pb = proposals["boxes"]
         D = self.test_topk_per_image
         kk = min(max_cand, P * K)
-        cache = self.__dict__.setdefault("_hwt_cache", {})   # a fresh torch.tensor(..., device=cuda) is a synchronizing pageable copy
-        ck = (tuple(proposals.image_sizes), str(pb.device))
-        hwt = cache.get(ck)
-        if hwt is None:
-            if len(cache) >= 16:
-                cache.clear()
-            hwt = cache[ck] = torch.tensor([[s[1], s[0], s[1], s[0]] for s in proposals.image_sizes], dtype=torch.float32, device=pb.device)[:, None, :]
+        hwt = _image_hwt(proposals.image_sizes, pb.device)
         if os.environ.get("UTV2_FUSED_ROI_INFERENCE", "1") != "0" and scores.dtype == deltas.dtype == std.dtype == torch.float32 and P * K < (1 << 32):
             # round 4: decode + clip + candidate keys, the gather behind the top-k and the packing of the NMS survivors as three launches
             # (utv2_roi_infer_*) around softmax / topk / utv2_nms_batched - the chain below is ~55 ATen launches per teacher pass.
@@ -543,9 +586,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
             # (utv2_topk_rows_i64, 9 launches) - torch.topk on an [N, P*K = 80 000] matrix with k = 8192 is ~40 launches (multi-block radix
             # select + segmented sort); same keys, same order (distinct keys: the selected set and its order are unique)
             if os.environ.get("UTV2_ROI_TOPK", "1") != "0" and kk <= 8192:
-                ro = cache.get(("row_off", N, P * K, str(pb.device)))
-                if ro is None:
-                    ro = cache[("row_off", N, P * K, str(pb.device))] = (torch.arange(N + 1, dtype=torch.int64) * (P * K)).to(pb.device)
+                ro = _device_const(("row_off", N, P * K, str(pb.device)), lambda: (torch.arange(N + 1, dtype=torch.int64) * (P * K)).to(pb.device))
                 top = hip.topk_rows(keys.view(-1), ro, N, P * K, kk)
             else:
                 top = torch.topk(keys, kk, dim=1, sorted=True).values
@@ -556,27 +597,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
         boxes = self.box2box_transform.apply_deltas(deltas.view(N, P, nbox, 4), pb[:, :, None, :])      # [N, P, nbox, 4]
         probs = F.softmax(scores, dim=-1).view(N, P, K + 1)[:, :, :K]
         ok = proposals["valid"].bool() & torch.isfinite(boxes).all(dim=3).all(dim=2) & torch.isfinite(probs).all(dim=2)
-        boxes = torch.minimum(boxes.clamp(min=0), hwt[:, :, None, :])
-        cand = (probs > self.test_score_thresh) & ok[:, :, None]
-        flat = torch.where(cand, probs, torch.full_like(probs, -1.0)).reshape(N, P * K)
-        top = torch.topk(float_order_key(flat), kk, dim=1, sorted=True).values
-        idx = 4294967295 - (top & 4294967295)
-        sc = torch.gather(flat, 1, idx)
-        r, c = idx // K, (idx % K).to(torch.int32)
-        # the box of the row (nbox == 1) or of (row, class)
-        cb = torch.gather(boxes.reshape(N, P * nbox, 4), 1, (r if nbox == 1 else idx)[:, :, None].expand(-1, -1, 4)).contiguous()
-        valid = (sc > self.test_score_thresh).to(torch.uint8)
-        kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), self.test_nms_thresh,
-                                    class_aware=True, post_topk=-1, max_out=D)
-        ix = kidx.clamp(min=0).long()
-        keep_rows = torch.gather(r, 1, ix)
-        out = PaddedBoxes(proposals.image_sizes,
-                          boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
-                          scores=torch.gather(sc, 1, ix).contiguous(),
-                          classes=torch.gather(c, 1, ix).contiguous(),
-                          pred_boxes_std=torch.gather(std.reshape(N, P, 4 * nbox), 1, keep_rows[:, :, None].expand(-1, -1, 4 * nbox)).contiguous(),
-                          valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
-        return out, keep_rows
+        return _roi_inference_aten(probs, boxes, ok, proposals, K, nbox, self.test_score_thresh, self.test_nms_thresh, D, kk, std=std)
 
 
 class FastRCNNFocaltLossOutputLayers:
@@ -676,31 +697,10 @@ class FastRCNNFocaltLossOutputLayers:
         K, nbx = self.K, self.nbox
         pb = proposals["boxes"]
         boxes = rpn_apply_deltas(deltas.float().view(N, P, nbx, 4), pb[:, :, None, :], self.box_weights)      # [N, P, nbx, 4]
-        hwt = torch.tensor([[s[1], s[0], s[1], s[0]] for s in proposals.image_sizes], dtype=torch.float32, device=pb.device)[:, None, None, :]
         probs = F.softmax(scores.float(), dim=-1).view(N, P, K + 1)
         ok = proposals["valid"].bool() & torch.isfinite(boxes).all(dim=3).all(dim=2) & torch.isfinite(probs).all(dim=2)
-        probs = probs[:, :, :K]
-        boxes = torch.minimum(boxes.clamp(min=0), hwt)
-        cand = (probs > self.test_score_thresh) & ok[:, :, None]
-        flat = torch.where(cand, probs, torch.full_like(probs, -1.0)).reshape(N, P * K)
-        k = min(max_cand, P * K)
-        top = torch.topk(float_order_key(flat), k, dim=1, sorted=True).values
-        idx = 4294967295 - (top & 4294967295)
-        sc = torch.gather(flat, 1, idx)
-        r, c = idx // K, (idx % K).to(torch.int32)
-        bsel = r if nbx == 1 else idx                                   # the box of (row, class)
-        cb = torch.gather(boxes.reshape(N, P * nbx, 4), 1, bsel[:, :, None].expand(-1, -1, 4)).contiguous()
-        valid = (sc > self.test_score_thresh).to(torch.uint8)
-        D = self.test_topk_per_image
-        kidx, cnt = hip.nms_batched(cb, sc.contiguous(), c.contiguous(), valid.contiguous(), self.test_nms_thresh,
-                                    class_aware=True, post_topk=-1, max_out=D)
-        ix = kidx.clamp(min=0).long()
-        keep_rows = torch.gather(r, 1, ix)
-        out = PaddedBoxes(proposals.image_sizes,
-                          boxes=torch.gather(cb, 1, ix[:, :, None].expand(-1, -1, 4)).contiguous(),
-                          scores=torch.gather(sc, 1, ix).contiguous(), classes=torch.gather(c, 1, ix).contiguous(),
-                          valid=(torch.arange(D, device=pb.device)[None, :] < cnt[:, None]).to(torch.uint8), count=cnt)
-        return out, keep_rows
+        return _roi_inference_aten(probs[:, :, :K], boxes, ok, proposals, K, nbx, self.test_score_thresh, self.test_nms_thresh,
+                                   self.test_topk_per_image, min(max_cand, P * K))
 
 
 class FastRCNNCrossEntropyBoundaryVarOutputLayers(FastRCNNFocaltLossBoundaryVarOutputLayers):
