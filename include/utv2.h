@@ -547,7 +547,20 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
  * mode 0..3, and mode 2 with nbox == 1 only (tsbetter has no per-class form in the reference); anything else: UTV2_EARG.
  * The caller's contract, NOT checked: cls (device data) in [-1, num_classes] (a value outside is treated as background); prop, gtb,
  * gdeltas and gstd_out are dense and 16-byte aligned (float4 accesses) - deltas / stdl are read as scalars: any 4-byte aligned
- * address and any pitch ld >= 4*nbox. */
+ * address and any pitch ld >= 4*nbox.
+ * _f: the same with MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA and BBOX_REG_LOSS_TYPE "giou".  smooth_l1_beta: the L1 terms of modes 0, 1 and 3
+ * become fvcore's smooth_l1_loss - beta < 1e-5: |d| (derivative sign(d)); else 0.5 d^2 / beta where |d| < beta (derivative d / beta) and
+ * |d| - 0.5 beta from |d| == beta on (derivative sign(d)).  Mode 0's NLL term does not depend on it: the reference's nl_loss takes
+ * `beta` and never reads it (fast_rcnn.py:1228-1292).  Mode 2 ignores it (the reference calls its smooth-L1 at 0.0, :1070-1075).
+ * mode 4: "giou" (fast_rcnn.py:998-1002) - the foreground row's deltas of its class decoded by Box2BoxXYXYTransform.apply_deltas
+ * (wx, wy, scale_clamp), fvcore's giou_loss (eps 1e-7) against the matched gt box, summed; gdeltas = its derivative through the decode
+ * (0 where the clamp cuts), gstd_out all 0 (the std head has no part in it); stdl and smooth_l1_beta have no effect.
+ * Accepted: what utv2_roi_box_loss accepts, mode 0..4, smooth_l1_beta >= 0 (+inf included); a negative or NaN beta, mode 5..: UTV2_EARG.
+ * utv2_roi_box_loss = _f at beta 0 (the same arithmetic as ever: nothing divides by beta there) with mode 0..3; its mode 4: UTV2_EARG. */
+int utv2_roi_box_loss_f(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
+                        const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp,
+                        float ts_better, float t_cert, float smooth_l1_beta, float* sum, float* gdeltas, float* gstd_out,
+                        utv2_stream_t stream);
 int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
                       const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
                       float t_cert, float* sum, float* gdeltas, float* gstd_out, utv2_stream_t stream);

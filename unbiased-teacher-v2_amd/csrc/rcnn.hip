@@ -1166,7 +1166,9 @@ __global__ __launch_bounds__(512) void roi_sample_kernel(const float* __restrict
 // Box regression losses of the boundary-variance predictor on the sampled ROIs (roi_heads/fast_rcnn.py:938-1090: `box_reg_loss`
 // nlloss / smooth_l1(beta 0) and `box_reg_pseudo_loss` tsbetter / smooth_l1), summed, with the derivatives w.r.t. the predicted
 // deltas and std logits.  mode 0: L1 + 0.05 * sum(NLL * IoU(gt, decoded box)) with the gradient flowing through the IoU;
-// 1: L1; 2: L1 on the boundaries where the teacher is more certain than the student by ts_better and above t_cert; 3: L1.
+// 1: L1; 2: L1 on the boundaries where the teacher is more certain than the student by ts_better and above t_cert; 3: L1;
+// 4: "giou" (fast_rcnn.py:998-1002), fvcore's GIoU loss of the decoded box against the gt box, no gradient to the std logits.
+// The L1 of modes 0, 1 and 3 is fvcore's smooth-L1 at `beta` (MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA; mode 2 is at beta 0 in the reference).
 // Box2BoxXYXYTransform (box_regression.py:11-129): get_deltas divides by (side + 1), apply_deltas multiplies by the side (B3 kept).
 // Layout: 4 * nbox delta / std columns per row, nbox = 1 (class-agnostic) or num_classes (CLS_AGNOSTIC_BBOX_REG False): a foreground row
 // reads - and its derivatives go to - the four columns of its class, 4 * cls .. 4 * cls + 3 (fast_rcnn.py:950-959, :1036-1045); gd / gs
@@ -1182,8 +1184,8 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
                                                          const long long* __restrict__ cls, const float* __restrict__ prop,
                                                          const float* __restrict__ gtb, const float* __restrict__ gstd, int R,
                                                          int num_classes, int nbox, int mode, float wx, float wy, float clampv,
-                                                         float ts_better, float t_cert, float* __restrict__ sum, float* __restrict__ gd,
-                                                         float* __restrict__ gs) {
+                                                         float ts_better, float t_cert, float beta, float* __restrict__ sum,
+                                                         float* __restrict__ gd, float* __restrict__ gs) {
   if (!PER_CLASS) nbox = 1;
   if (PER_CLASS && blockIdx.x != 0) {
     const long long groups = (long long)R * nbox, step = (long long)(gridDim.x - 1) * blockDim.x;
@@ -1200,6 +1202,7 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
   }
   __shared__ float red[256];
   float acc = 0.f;
+  const bool l1 = beta < 1e-5f;   // fvcore smooth_l1_loss: plain L1 below 1e-5 - beta 0 adds |d| and writes sign(d), nothing divides by it
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     const long long c = cls[r];
     const bool fg = c >= 0 && c < num_classes;
@@ -1227,13 +1230,17 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
         g_d[k] = (df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * m;
       }
     } else {
+      if (mode != 4) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float df = d[k] - t[k];
-        if (fg) acc += fabsf(df);
-        g_d[k] = (df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * fgf;
+        for (int k = 0; k < 4; ++k) {
+          const float df = d[k] - t[k], a = fabsf(df);
+          const bool quad = !l1 && a < beta;   // |d| == beta is on the linear side (fvcore: where(n < beta, ...))
+          if (fg) acc += quad ? 0.5f * df * df / beta : l1 ? a : a - 0.5f * beta;
+          g_d[k] = (quad ? df / beta : df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * fgf;
+        }
       }
-      if (mode == 0) {
+      if (mode == 0 || mode == 4) {
+        const bool giou = mode == 4;
         const float w = pb.z - pb.x, h = pb.w - pb.y;
         const float wd[4] = {wx, wx, wy, wy};
         const float side[4] = {w, w, h, h};
@@ -1248,34 +1255,56 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
         const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
         const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
         const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
-        const float I = whx * why, U = a1 + a2 - I;
-        const float iou = fg ? I / U : 0.f;
-        float nll = 0.f, sig[4], sq[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sig[k] = sigmoidf_(sl[k]);
-          sq[k] = sig[k] * sig[k];
-          const float df = t[k] - d[k];
-          nll += df * df / (2.f * sq[k]) + 0.5f * logf(sq[k]);
-        }
-        nll += 2.f * 1.8378770664093453f;  // 2 log(2 pi)
-        // (foreground rows only, as the reference indexes them: on a background row a std logit below -88 makes nll = inf - inf, and
-        // NaN * 0 would put a NaN into the loss VALUE - the gradients below were always guarded)
-        if (fg) acc += 0.05f * (nll * iou);
-        if (fg) {
-          // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
-          const float cx = (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = (rby - lty) >= 0.f ? 1.f : 0.f;
-          const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-          const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-          // order of the deltas: x1, x2, y1, y2
-          const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
-          const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
+        // nlloss: D2 pairwise IoU, both sides clamped at 0; giou: fvcore's intersection, non-zero where both sides are > 0 (the same value
+        // for finite boxes; the derivatives differ on a side that is exactly 0)
+        const bool open = rbx > ltx && rby > lty;
+        const float I = (giou && !open) ? 0.f : whx * why, U = a1 + a2 - I;
+        // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
+        const float cx = giou ? (open ? 1.f : 0.f) : (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = giou ? cx : (rby - lty) >= 0.f ? 1.f : 0.f;
+        const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
+        const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+        // order of the deltas: x1, x2, y1, y2
+        const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
+        const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
+        if (!giou) {
+          const float iou = fg ? I / U : 0.f;
+          float nll = 0.f, sig[4], sq[4];   // (nl_loss takes the smooth-L1 beta and never reads it, fast_rcnn.py:1228-1292: no beta here)
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float diou = (dI[k] * (U + I) - I * dA[k]) / (U * U) * dq[k];
-            const float df = d[k] - t[k];
-            g_d[k] += 0.05f * (iou * df / sq[k] + nll * diou);
-            g_s[k] = 0.05f * iou * (1.f - sig[k]) * (1.f - df * df / sq[k]);
+            sig[k] = sigmoidf_(sl[k]);
+            sq[k] = sig[k] * sig[k];
+            const float df = t[k] - d[k];
+            nll += df * df / (2.f * sq[k]) + 0.5f * logf(sq[k]);
+          }
+          nll += 2.f * 1.8378770664093453f;  // 2 log(2 pi)
+          // (foreground rows only, as the reference indexes them: on a background row a std logit below -88 makes nll = inf - inf, and
+          // NaN * 0 would put a NaN into the loss VALUE - the gradients below were always guarded)
+          if (fg) acc += 0.05f * (nll * iou);
+          if (fg) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const float diou = (dI[k] * (U + I) - I * dA[k]) / (U * U) * dq[k];
+              const float df = d[k] - t[k];
+              g_d[k] += 0.05f * (iou * df / sq[k] + nll * diou);
+              g_s[k] = 0.05f * iou * (1.f - sig[k]) * (1.f - df * df / sq[k]);
+            }
+          }
+        } else if (fg) {
+          // fvcore giou_loss (eps 1e-7): 1 - (I / (U + eps) - (C - U) / (C + eps)), C = the area of the smallest enclosing box; the std
+          // head gets no gradient (g_s stays 0)
+          const float Ue = U + 1e-7f;
+          const float ew = fmaxf(px2, gb.z) - fminf(px1, gb.x), eh = fmaxf(py2, gb.w) - fminf(py1, gb.y);
+          const float C = ew * eh, Ce = C + 1e-7f;
+          acc += 1.f - (I / Ue - (C - U) / Ce);
+          const float nx1 = px1 < gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, nx2 = px2 > gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
+          const float ny1 = py1 < gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, ny2 = py2 > gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+          const float dC[4] = {-eh * nx1, eh * nx2, -ew * ny1, ew * ny2};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float dU = dA[k] - dI[k];
+            const float diou = (dI[k] * Ue - I * dU) / (Ue * Ue);
+            const float dpen = ((dC[k] - dU) * Ce - (C - U) * dC[k]) / (Ce * Ce);
+            g_d[k] = (dpen - diou) * dq[k];
           }
         }
       }
@@ -1825,17 +1854,26 @@ int utv2_roi_sample(const float* boxes, const unsigned char* valid, const float*
   return utv2_launch_status();
 }
 
-int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
-                      const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
-                      float t_cert, float* sum, float* gdeltas, float* gstd_out, hipStream_t stream) {
+int utv2_roi_box_loss_f(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
+                        const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
+                        float t_cert, float smooth_l1_beta, float* sum, float* gdeltas, float* gstd_out, hipStream_t stream) {
   if (!deltas || !stdl || !cls || !prop || !gtb || !sum || !gdeltas || !gstd_out || R < 0 || num_classes < 1 ||
-      (nbox != num_classes && nbox != 1) || ld < 4 * (int64_t)nbox || mode < 0 || mode > 3 || (mode == 2 && nbox > 1))
+      (nbox != num_classes && nbox != 1) || ld < 4 * (int64_t)nbox || mode < 0 || mode > 4 || (mode == 2 && nbox > 1) ||
+      !(smooth_l1_beta >= 0.f))   // (a NaN beta fails the comparison too)
     return UTV2_EARG;
   const long long fill = nbox > 1 ? cdiv((long long)R * nbox, 256) : 0;   // the zero-filling workgroups
   hipLaunchKernelGGL(nbox > 1 ? roi_box_loss_kernel<true> : roi_box_loss_kernel<false>, dim3(1 + (unsigned)(fill < 1024 ? fill : 1024)), dim3(256), 0,
                      stream, deltas, stdl, (long long)ld, (const long long*)cls, prop, gtb, gstd, R, num_classes, nbox, mode, wx, wy, scale_clamp,
-                     ts_better, t_cert, sum, gdeltas, gstd_out);
+                     ts_better, t_cert, smooth_l1_beta, sum, gdeltas, gstd_out);
   return utv2_launch_status();
+}
+
+int utv2_roi_box_loss(const float* deltas, const float* stdl, int64_t ld, const int64_t* cls, const float* prop, const float* gtb,
+                      const float* gstd, int R, int num_classes, int nbox, int mode, float wx, float wy, float scale_clamp, float ts_better,
+                      float t_cert, float* sum, float* gdeltas, float* gstd_out, hipStream_t stream) {
+  if (mode == 4) return UTV2_EARG;   // modes 0..3 as ever; "giou" is the _f entry point's
+  return utv2_roi_box_loss_f(deltas, stdl, ld, cls, prop, gtb, gstd, R, num_classes, nbox, mode, wx, wy, scale_clamp, ts_better, t_cert, 0.f,
+                             sum, gdeltas, gstd_out, stream);
 }
 
 }  // extern "C"

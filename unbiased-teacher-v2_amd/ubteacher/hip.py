@@ -985,9 +985,10 @@ def roi_infer_pack(kidx, cnt, cb, sc, cls, rows, std, P, D, nbox=1):
     return ob, osc, oc, ostd, orows, ov
 
 
-def roi_box_loss(deltas, std, cls, prop, gtb, gstd, num_classes, mode, wx, wy, scale_clamp, ts_better, t_cert, nbox=1):
+def roi_box_loss(deltas, std, cls, prop, gtb, gstd, num_classes, mode, wx, wy, scale_clamp, ts_better, t_cert, nbox=1, smooth_l1_beta=0.0):
     """(sum [1], d sum / d deltas [R, 4*nbox], d sum / d std [R, 4*nbox]); nbox > 1: a foreground row's four columns are chosen by its
-    class.  deltas / std may be column slices of the predictor output (row pitch = stride(0))"""
+    class.  deltas / std may be column slices of the predictor output (row pitch = stride(0)).  mode 0..4 (4 = "giou"), smooth_l1_beta
+    = the beta of the smooth-L1 terms of modes 0, 1 and 3 (utv2_roi_box_loss_f)"""
     R = deltas.shape[0]
     assert deltas.dtype == torch.float32 and std.dtype == torch.float32 and deltas.stride(1) == 1 and std.stride(1) == 1
     assert deltas.stride(0) == std.stride(0) and cls.dtype == torch.int64
@@ -996,8 +997,9 @@ def roi_box_loss(deltas, std, cls, prop, gtb, gstd, num_classes, mode, wx, wy, s
     out = torch.empty(1, dtype=torch.float32, device=dev)
     gd = torch.empty((R, 4 * nbox), dtype=torch.float32, device=dev)
     gs = torch.empty((R, 4 * nbox), dtype=torch.float32, device=dev)
-    call("utv2_roi_box_loss", c_p(deltas.data_ptr()), c_p(std.data_ptr()), deltas.stride(0), _p(cls), _p(prop), _p(gtb), _p(gstd), R, num_classes,
-         nbox, mode, float(wx), float(wy), float(scale_clamp), float(ts_better), float(t_cert), _p(out), _p(gd), _p(gs), _stream())
+    call("utv2_roi_box_loss_f", c_p(deltas.data_ptr()), c_p(std.data_ptr()), deltas.stride(0), _p(cls), _p(prop), _p(gtb), _p(gstd), R, num_classes,
+         nbox, mode, float(wx), float(wy), float(scale_clamp), float(ts_better), float(t_cert), float(smooth_l1_beta), _p(out), _p(gd), _p(gs),
+         _stream())
     return out, gd, gs
 
 

@@ -138,7 +138,7 @@ class _RoiBoxLossFn(torch.autograd.Function):
     def forward(ctx, deltas, std, cls, prop, gtb, gstd, pred, mode):
         t = pred.box2box_transform   # (pred.nbox > 1, per-class regression: the four columns of each foreground row's class)
         out, gd, gs = hip.roi_box_loss(deltas.detach(), std.detach(), cls, prop, gtb, gstd, pred.num_classes, mode, t.weights[0], t.weights[1],
-                                       t.scale_clamp, pred.ts_better, pred.t_cert, pred.nbox)
+                                       t.scale_clamp, pred.ts_better, pred.t_cert, pred.nbox, smooth_l1_beta=pred.smooth_l1_beta)
         ctx.save_for_backward(gd, gs)
         return out
 
@@ -490,6 +490,7 @@ def _roi_inference_aten(probs, boxes, ok, proposals, K, nbox, thr, nms_thr, D, k
 class FastRCNNFocaltLossBoundaryVarOutputLayers:
     """Predictor + losses + inference (reference fast_rcnn.py:715-1292)."""
     focal_gamma = 1.5  # comput_focal_loss, fast_rcnn.py:925-936
+    BOX_LOSS_MODE = {"nlloss": 0, "smooth_l1": 1, "giou": 4}   # BBOX_REG_LOSS_TYPE -> mode of utv2_roi_box_loss_f (fast_rcnn.py:961-1004)
 
     def __init__(self, cfg, store, in_dim, prefix):
         rh, bh = cfg.MODEL.ROI_HEADS, cfg.MODEL.ROI_BOX_HEAD
@@ -532,7 +533,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
         self.loss_weight = {"loss_box_reg": bh.BBOX_REG_LOSS_WEIGHT}
         self.ts_better = cfg.SEMISUPNET.TS_BETTER
         self.t_cert = cfg.SEMISUPNET.T_CERT
-        if self.box_reg_loss_type not in ("nlloss", "smooth_l1"):
+        if self.box_reg_loss_type not in self.BOX_LOSS_MODE:
             raise ValueError("Invalid bbox reg loss type '{}'".format(self.box_reg_loss_type))
         if self.box_pseudo_reg_loss_type not in ("tsbetter", "smooth_l1"):
             raise ValueError("Invalid bbox pseudo reg loss type '{}'".format(self.box_pseudo_reg_loss_type))
@@ -548,7 +549,7 @@ class FastRCNNFocaltLossBoundaryVarOutputLayers:
         tgt = cls.to(torch.int32).contiguous()
         focal = ops.softmax_focal_sum(scores, tgt, self.focal_gamma)
         pseudo = branch == "unsup_data_train"
-        mode = (2 if self.box_pseudo_reg_loss_type == "tsbetter" else 3) if pseudo else (0 if self.box_reg_loss_type == "nlloss" else 1)
+        mode = (2 if self.box_pseudo_reg_loss_type == "tsbetter" else 3) if pseudo else self.BOX_LOSS_MODE[self.box_reg_loss_type]
         gstd = sampled["gt_loc_std"].reshape(-1, 4).contiguous() if (mode == 2 and "gt_loc_std" in sampled) else None
         box = _RoiBoxLossFn.apply(deltas, std, cls.long().contiguous(), sampled["proposal_boxes"].reshape(-1, 4).contiguous(),
                                   sampled["gt_boxes"].reshape(-1, 4).contiguous(), gstd, self, mode)
