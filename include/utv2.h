@@ -513,6 +513,27 @@ int utv2_rpn_loss_bwd_range(const float* gobj, const float* gdl, const float* go
                             const int* hw_host, int N, int batch, int img0, int A, int ch, int R, const int64_t* pos_idx,
                             const unsigned char* pos_valid, int npos, const int64_t* neg_idx, const unsigned char* neg_valid, int nneg,
                             float* grad_obj, float* grad_deltas, utv2_stream_t stream);
+/* _f: the same with MODEL.RPN.SMOOTH_L1_BETA and BBOX_REG_LOSS_TYPE "giou" (D2 _dense_box_regression_loss [D2-recall], rpn.py:194-202).
+ * loc_mode 0, "smooth_l1": sums[1] / gdl are fvcore's smooth_l1_loss of (delta - target) at `beta` - beta < 1e-5: |d| (derivative
+ * sign(d)); else 0.5 d^2 / beta where |d| < beta (derivative d / beta) and |d| - 0.5 beta from |d| == beta on (derivative sign(d)).  At
+ * beta 0 the arithmetic and the order of the additions are utv2_rpn_loss_fwd's: nothing divides by beta there.  scale_clamp is not read.
+ * loc_mode 1, "giou": the positive's deltas decoded on its anchor by Box2BoxTransform.apply_deltas (divide by weights_host, dw / dh
+ * clamped from above at scale_clamp, exp - utv2_rpn_decode's arithmetic without the clip to the image), fvcore's giou_loss (eps 1e-7)
+ * of that box against the matched gt box, summed; gdl = its derivative through the decode, 0 through a clamped dw / dh.  beta is not
+ * read (it must still be valid).  The BCE sum, gobj, the layouts, the one-workgroup fixed summation order and "every element of gobj /
+ * gdl is written; a slot without weight contributes nothing" are as above; utv2_rpn_loss_bwd(_range) serves both modes.
+ * Accepted: what the plain entries accept, loc_mode 0 or 1, beta >= 0 (+inf included), scale_clamp not NaN; loc_mode outside {0, 1}, a
+ * negative or NaN beta, a NaN scale_clamp: UTV2_EARG, nothing is launched.  utv2_rpn_loss_fwd(_range) = _f at (0, 0.f). */
+int utv2_rpn_loss_fwd_f(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int A, int ch, int R,
+                        const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos, const int64_t* neg_idx,
+                        const unsigned char* neg_valid, int nneg, const int* matched, const unsigned char* has_gt, const float* gt_boxes,
+                        const float* gt_scores, int G, const float* weights_host, int loc_mode, float beta, float scale_clamp, float* sums,
+                        float* gobj, float* gdl, utv2_stream_t stream);
+int utv2_rpn_loss_fwd_range_f(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int batch, int img0,
+                              int A, int ch, int R, const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos,
+                              const int64_t* neg_idx, const unsigned char* neg_valid, int nneg, const int* matched,
+                              const unsigned char* has_gt, const float* gt_boxes, const float* gt_scores, int G, const float* weights_host,
+                              int loc_mode, float beta, float scale_clamp, float* sums, float* gobj, float* gdl, utv2_stream_t stream);
 /* Labelling + random subsampling of anchors / proposals (rpn.py:112-148 -> D2 label_and_sample_anchors + subsample_labels;
  * roi_heads.py:141-270 -> D2 Matcher + _sample_proposals).  Random choice = the k smallest of one uniform key in [0, 1) per slot (keys
  * from the caller); equal keys are taken in slot order.
@@ -526,6 +547,15 @@ int utv2_rpn_loss_bwd_range(const float* gobj, const float* gdl, const float* go
  * gt_scores / gt_std [N][G] / [N][G][4] and the outputs are given - the matched pseudo box's score and std logits. */
 int utv2_rpn_sample_keys(const float* max_iou, const unsigned char* lowq, const unsigned char* gt_valid, int G, const float* keys, int N,
                          int R, float lo, float hi, int64_t* out, utv2_stream_t stream);
+/* _b: rpn_sample_keys with MODEL.RPN.BOUNDARY_THRESH (rpn.py:125-131).  boundary_thresh >= 0: once an anchor's label is final - after the
+ * IoU thresholds, the low-quality matches and the all-negative labels of an image without gt - D2's Boxes.inside_box decides: anchors
+ * [R][4] row r is inside image n (image_hw [N][2]: its own height and width, not the padded canvas) if x1 >= -t && y1 >= -t &&
+ * x2 < W + t && y2 < H + t; an anchor that is not inside is a candidate for neither row.  boundary_thresh < 0: anchors / image_hw are
+ * not read (NULL allowed) and the output is utv2_rpn_sample_keys', which forwards here with (NULL, NULL, -1).
+ * boundary_thresh >= 0 with anchors or image_hw NULL, a NaN boundary_thresh: UTV2_EARG, nothing is launched. */
+int utv2_rpn_sample_keys_b(const float* max_iou, const unsigned char* lowq, const unsigned char* gt_valid, int G, const float* keys, int N,
+                           int R, float lo, float hi, const float* anchors, const float* image_hw, float boundary_thresh, int64_t* out,
+                           utv2_stream_t stream);
 int utv2_rpn_sample_unpack(const int64_t* top, int k, int N, int npos_max, int nneg_max, const unsigned char* gt_valid, int G,
                            int64_t* pos_idx, unsigned char* pos_valid, int64_t* neg_idx, unsigned char* neg_valid, unsigned char* has_gt,
                            utv2_stream_t stream);

@@ -928,6 +928,9 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(RpnLevels L, const long
 // over the positives, plus d(sum)/d(logit) per slot and d(sum)/d(delta) per positive slot.  The logits / deltas are read either from
 // dense [N][R] / [N][R][4] tensors or straight from the level-first head output (rows (level, image, pixel) x ch: A logits, then 4A
 // anchor-major deltas).  One workgroup, fixed summation order: deterministic.
+// MODEL.RPN.SMOOTH_L1_BETA / BBOX_REG_LOSS_TYPE (D2 _dense_box_regression_loss, rpn.py:194-202): loc_mode 0 is fvcore's smooth-L1 of
+// (delta - target) at beta - at beta 0 the |delta - target| above, same expressions and same order of additions -, loc_mode 1 fvcore's
+// GIoU loss of the decoded box against the matched gt box; gdl carries d(sum)/d(delta) either way, so the backward kernel is one.
 struct RpnLossArgs {
   RpnLevels L;
   int head, N, A, ch, R, npos, nneg, G;
@@ -943,7 +946,40 @@ struct RpnLossArgs {
   const float* gt_boxes;
   const float* gt_scores;
   float wx, wy, ww, wh;
+  int loc_mode;             // 0: smooth-L1 at beta on the deltas, 1: "giou" on the decoded boxes (forward only)
+  float beta, scale_clamp;
 };
+
+// fvcore giou_loss (eps 1e-7) of the box (px1, py1, px2, py2) against gb: 1 - (I / (U + eps) - (C - U) / (C + eps)), I = fvcore's
+// intersection (non-zero where both sides are > 0), C = the area of the smallest enclosing box; dL = its derivative w.r.t. px1, px2,
+// py1, py2 (in this order).  torch.max / torch.min send the gradient to the selected operand (half on a tie).  The one copy for
+// roi_box_loss_kernel (mode 4) and rpn_loss_fwd_kernel (loc_mode 1).
+__device__ __forceinline__ float giou_loss_grad(float px1, float py1, float px2, float py2, const float4& gb, float (&dL)[4]) {
+  const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
+  const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
+  const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
+  const bool open = rbx > ltx && rby > lty;
+  const float I = !open ? 0.f : whx * why, U = a1 + a2 - I;
+  const float cx = open ? 1.f : 0.f, cy = cx;
+  const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
+  const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+  const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
+  const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
+  const float Ue = U + 1e-7f;
+  const float ew = fmaxf(px2, gb.z) - fminf(px1, gb.x), eh = fmaxf(py2, gb.w) - fminf(py1, gb.y);
+  const float C = ew * eh, Ce = C + 1e-7f;
+  const float nx1 = px1 < gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, nx2 = px2 > gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
+  const float ny1 = py1 < gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, ny2 = py2 > gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+  const float dC[4] = {-eh * nx1, eh * nx2, -ew * ny1, ew * ny2};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float dU = dA[k] - dI[k];
+    const float diou = (dI[k] * Ue - I * dU) / (Ue * Ue);
+    const float dpen = ((dC[k] - dU) * Ce - (C - U) * dC[k]) / (Ce * Ce);
+    dL[k] = dpen - diou;
+  }
+  return 1.f - (I / Ue - (C - U) / Ce);
+}
 
 // element offsets of anchor r's logit and of its first delta for image n
 __device__ __forceinline__ void rpn_locate(const RpnLevels& L, int head, int n, int r, int A, int ch, int R, size_t& o_obj, size_t& o_dl) {
@@ -966,6 +1002,7 @@ __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs p, float*
                                                          float* __restrict__ gdl) {
   __shared__ float red[2][256];
   const int S = p.npos + p.nneg;
+  const bool l1 = p.beta < 1e-5f;   // fvcore smooth_l1_loss: plain L1 below 1e-5 - beta 0 adds |d| and writes sign(d), nothing divides by it
   float cls = 0.f, loc = 0.f;
   for (int slot = threadIdx.x; slot < p.N * S; slot += blockDim.x) {
     const int n = slot / S, j = slot - n * S;
@@ -992,14 +1029,37 @@ __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs p, float*
         b = *(const float4*)(p.gt_boxes + ((size_t)n * p.G + g) * 4);
       }
       const float sw = a.z - a.x, sh = a.w - a.y, sx = a.x + 0.5f * sw, sy = a.y + 0.5f * sh;
-      const float tw = b.z - b.x, th = b.w - b.y, tx = b.x + 0.5f * tw, ty = b.y + 0.5f * th;
-      const float tgt[4] = {p.wx * (tx - sx) / sw, p.wy * (ty - sy) / sh, p.ww * logf(tw / sw), p.wh * logf(th / sh)};
-      const float m = pv ? 1.f : 0.f;
+      float* gout = gdl + ((size_t)n * p.npos + j) * 4;
+      if (p.loc_mode == 0) {
+        const float tw = b.z - b.x, th = b.w - b.y, tx = b.x + 0.5f * tw, ty = b.y + 0.5f * th;
+        const float tgt[4] = {p.wx * (tx - sx) / sw, p.wy * (ty - sy) / sh, p.ww * logf(tw / sw), p.wh * logf(th / sh)};
+        const float m = pv ? 1.f : 0.f;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float d = p.deltas[od + c] - tgt[c];
-        if (pv) loc += fabsf(d);
-        gdl[((size_t)n * p.npos + j) * 4 + c] = (d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f) * m;
+        for (int c = 0; c < 4; ++c) {
+          const float d = p.deltas[od + c] - tgt[c], ad = fabsf(d);
+          const bool quad = !l1 && ad < p.beta;   // |d| == beta is on the linear side (fvcore: where(n < beta, ...))
+          if (pv) loc += quad ? 0.5f * d * d / p.beta : l1 ? ad : ad - 0.5f * p.beta;
+          gout[c] = (quad ? d / p.beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f) * m;
+        }
+      } else {
+        // "giou": Box2BoxTransform.apply_deltas on the anchor (rpn_decode_kernel's arithmetic, no clip to the image), then fvcore's GIoU
+        // loss against the matched gt box; x1 / x2 = pcx -+ pw / 2: the derivative w.r.t. dx is the sum of the two corner derivatives times
+        // w / wx, w.r.t. dw their difference times pw / (2 ww) - 0 where torch.clamp(max=) cut (its bound itself passes the gradient)
+        const float dx = p.deltas[od] / p.wx, dy = p.deltas[od + 1] / p.wy;
+        float dw = p.deltas[od + 2] / p.ww, dh = p.deltas[od + 3] / p.wh;
+        const bool cutw = dw > p.scale_clamp, cuth = dh > p.scale_clamp;
+        dw = cutw ? p.scale_clamp : dw;
+        dh = cuth ? p.scale_clamp : dh;
+        const float pcx = dx * sw + sx, pcy = dy * sh + sy;
+        const float pw = expf(dw) * sw, ph = expf(dh) * sh;
+        float dL[4];
+        const float gl = giou_loss_grad(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph, b, dL);
+        if (pv) loc += gl;
+        // (selects: the deltas an empty slot's index names may be non-finite)
+        gout[0] = pv ? (dL[0] + dL[1]) * (sw / p.wx) : 0.f;
+        gout[1] = pv ? (dL[2] + dL[3]) * (sh / p.wy) : 0.f;
+        gout[2] = (pv && !cutw) ? (dL[1] - dL[0]) * (0.5f * pw / p.ww) : 0.f;
+        gout[3] = (pv && !cuth) ? (dL[3] - dL[2]) * (0.5f * ph / p.wh) : 0.f;
       }
     }
   }
@@ -1046,13 +1106,14 @@ __global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnLossArgs p, const 
 // the caller: device RNG in training, injected in the parity tests); equal keys are taken in slot order.
 //
 // RPN, R ~ 2e5 anchors per image: rpn_sample_keys_kernel labels every anchor (IoU < lo: negative, >= hi or low-quality match: positive,
-// image without gt: all negative) and writes one sortable 63-bit key per anchor into a row of positives and a row of negatives
+// image without gt: all negative; then, boundary_thresh >= 0: not inside its image by the threshold: ignored) and writes one sortable 63-bit key per anchor into a row of positives and a row of negatives
 // (-1 = not a candidate; descending key order == ascending random key, then ascending anchor index) - the input of the exact radix
 // select utv2_topk_rows_i64; rpn_sample_unpack_kernel turns the selected keys into the sampler's index / valid arrays.
 __global__ __launch_bounds__(256) void rpn_sample_keys_kernel(const float* __restrict__ mx, const unsigned char* __restrict__ lowq,
                                                             const unsigned char* __restrict__ gt_valid, int G,
                                                             const float* __restrict__ keys, int N, int R, float lo, float hi,
-                                                            long long* __restrict__ out) {
+                                                            const float* __restrict__ anchors, const float* __restrict__ image_hw,
+                                                            float boundary_thresh, long long* __restrict__ out) {
   const int n = blockIdx.y;
   const int has_gt = block_any_gt_valid(gt_valid, n, G);
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1063,6 +1124,12 @@ __global__ __launch_bounds__(256) void rpn_sample_keys_kernel(const float* __res
   if (v >= hi) label = 1;
   if (lowq[o]) label = 1;
   if (!has_gt) label = 0;
+  if (boundary_thresh >= 0.f) {
+    // MODEL.RPN.BOUNDARY_THRESH (rpn.py:125-131), on the final label: D2 Boxes.inside_box against the image's own (H, W)
+    const float4 a = *(const float4*)(anchors + (size_t)r * 4);
+    const float H = image_hw[n * 2], W = image_hw[n * 2 + 1], t = boundary_thresh;
+    if (!(a.x >= -t && a.y >= -t && a.z < W + t && a.w < H + t)) label = -1;
+  }
   const long long k = ((long long)(0x7fffffff - (__float_as_int(keys[o]) & 0x7fffffff)) << 32) | (long long)(0xffffffffu - (unsigned)r);
   out[o] = label == 1 ? k : -1;
   out[(size_t)N * R + o] = label == 0 ? k : -1;
@@ -1252,21 +1319,20 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
           dq[k] = (v >= -clampv && v <= clampv) ? side[k] / wd[k] : 0.f;
         }
         const float px1 = q[0] * w + pb.x, px2 = q[1] * w + pb.z, py1 = q[2] * h + pb.y, py2 = q[3] * h + pb.w;
-        const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
-        const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
-        const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
-        // nlloss: D2 pairwise IoU, both sides clamped at 0; giou: fvcore's intersection, non-zero where both sides are > 0 (the same value
-        // for finite boxes; the derivatives differ on a side that is exactly 0)
-        const bool open = rbx > ltx && rby > lty;
-        const float I = (giou && !open) ? 0.f : whx * why, U = a1 + a2 - I;
-        // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
-        const float cx = giou ? (open ? 1.f : 0.f) : (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = giou ? cx : (rby - lty) >= 0.f ? 1.f : 0.f;
-        const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-        const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-        // order of the deltas: x1, x2, y1, y2
-        const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
-        const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
         if (!giou) {
+          const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
+          const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
+          const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
+          // D2 pairwise IoU, both sides clamped at 0 (giou_loss_grad has fvcore's intersection, non-zero where both sides are > 0: the same
+          // value for finite boxes; the derivatives differ on a side that is exactly 0)
+          const float I = whx * why, U = a1 + a2 - I;
+          // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
+          const float cx = (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = (rby - lty) >= 0.f ? 1.f : 0.f;
+          const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
+          const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+          // order of the deltas: x1, x2, y1, y2
+          const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
+          const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
           const float iou = fg ? I / U : 0.f;
           float nll = 0.f, sig[4], sq[4];   // (nl_loss takes the smooth-L1 beta and never reads it, fast_rcnn.py:1228-1292: no beta here)
 #pragma unroll
@@ -1290,22 +1356,11 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
             }
           }
         } else if (fg) {
-          // fvcore giou_loss (eps 1e-7): 1 - (I / (U + eps) - (C - U) / (C + eps)), C = the area of the smallest enclosing box; the std
-          // head gets no gradient (g_s stays 0)
-          const float Ue = U + 1e-7f;
-          const float ew = fmaxf(px2, gb.z) - fminf(px1, gb.x), eh = fmaxf(py2, gb.w) - fminf(py1, gb.y);
-          const float C = ew * eh, Ce = C + 1e-7f;
-          acc += 1.f - (I / Ue - (C - U) / Ce);
-          const float nx1 = px1 < gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, nx2 = px2 > gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-          const float ny1 = py1 < gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, ny2 = py2 > gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-          const float dC[4] = {-eh * nx1, eh * nx2, -ew * ny1, ew * ny2};
+          // fvcore giou_loss of the decoded box (giou_loss_grad, shared with the RPN loss); the std head gets no gradient (g_s stays 0)
+          float dL[4];
+          acc += giou_loss_grad(px1, py1, px2, py2, gb, dL);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float dU = dA[k] - dI[k];
-            const float diou = (dI[k] * Ue - I * dU) / (Ue * Ue);
-            const float dpen = ((dC[k] - dU) * Ce - (C - U) * dC[k]) / (Ce * Ce);
-            g_d[k] = (dpen - diou) * dq[k];
-          }
+          for (int k = 0; k < 4; ++k) g_d[k] = dL[k] * dq[k];
         }
       }
     }
@@ -1772,29 +1827,52 @@ static int fill_rpn_loss_args(RpnLossArgs& a, const float* obj, const float* del
   a.matched = matched; a.has_gt = has_gt; a.gt_boxes = gt_boxes; a.gt_scores = gt_scores;
   a.wx = weights_host ? weights_host[0] : 1.f; a.wy = weights_host ? weights_host[1] : 1.f;
   a.ww = weights_host ? weights_host[2] : 1.f; a.wh = weights_host ? weights_host[3] : 1.f;
+  a.loc_mode = 0; a.beta = 0.f; a.scale_clamp = 0.f;
   return UTV2_OK;
 }
 
+int utv2_rpn_loss_fwd_range_f(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int batch, int img0,
+                              int A, int ch, int R, const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos,
+                              const int64_t* neg_idx, const unsigned char* neg_valid, int nneg, const int* matched, const unsigned char* has_gt,
+                              const float* gt_boxes, const float* gt_scores, int G, const float* weights_host, int loc_mode, float beta,
+                              float scale_clamp, float* sums, float* gobj, float* gdl, hipStream_t stream) {
+  RpnLossArgs a;
+  if (!anchors || !matched || !has_gt || !gt_boxes || !weights_host || !sums || !gobj || !gdl || G < 1) return UTV2_EARG;
+  if ((loc_mode != 0 && loc_mode != 1) || !(beta >= 0.f) || scale_clamp != scale_clamp) return UTV2_EARG;   // (a NaN beta fails >= too)
+  if (int e = fill_rpn_loss_args(a, obj, deltas, head, num_levels, hw_host, N, batch, img0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx,
+                                 neg_valid, nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host))
+    return e;
+  a.loc_mode = loc_mode; a.beta = beta; a.scale_clamp = scale_clamp;
+  hipLaunchKernelGGL(rpn_loss_fwd_kernel, dim3(1), dim3(256), 0, stream, a, sums, gobj, gdl);
+  return utv2_launch_status();
+}
+
+int utv2_rpn_loss_fwd_f(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int A, int ch, int R,
+                        const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos, const int64_t* neg_idx,
+                        const unsigned char* neg_valid, int nneg, const int* matched, const unsigned char* has_gt, const float* gt_boxes,
+                        const float* gt_scores, int G, const float* weights_host, int loc_mode, float beta, float scale_clamp, float* sums,
+                        float* gobj, float* gdl, hipStream_t stream) {
+  return utv2_rpn_loss_fwd_range_f(obj, deltas, head, num_levels, hw_host, N, N, 0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx,
+                                   neg_valid, nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host, loc_mode, beta, scale_clamp, sums, gobj,
+                                   gdl, stream);
+}
+
+// the plain entries: smooth-L1 at beta 0 (scale_clamp is not read in that mode)
 int utv2_rpn_loss_fwd_range(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int batch, int img0,
                             int A, int ch, int R, const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos,
                             const int64_t* neg_idx, const unsigned char* neg_valid, int nneg, const int* matched, const unsigned char* has_gt,
                             const float* gt_boxes, const float* gt_scores, int G, const float* weights_host, float* sums, float* gobj,
                             float* gdl, hipStream_t stream) {
-  RpnLossArgs a;
-  if (!anchors || !matched || !has_gt || !gt_boxes || !weights_host || !sums || !gobj || !gdl || G < 1) return UTV2_EARG;
-  if (int e = fill_rpn_loss_args(a, obj, deltas, head, num_levels, hw_host, N, batch, img0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx,
-                                 neg_valid, nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host))
-    return e;
-  hipLaunchKernelGGL(rpn_loss_fwd_kernel, dim3(1), dim3(256), 0, stream, a, sums, gobj, gdl);
-  return utv2_launch_status();
+  return utv2_rpn_loss_fwd_range_f(obj, deltas, head, num_levels, hw_host, N, batch, img0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx,
+                                   neg_valid, nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host, 0, 0.f, 0.f, sums, gobj, gdl, stream);
 }
 
 int utv2_rpn_loss_fwd(const float* obj, const float* deltas, int head, int num_levels, const int* hw_host, int N, int A, int ch, int R,
                       const float* anchors, const int64_t* pos_idx, const unsigned char* pos_valid, int npos, const int64_t* neg_idx,
                       const unsigned char* neg_valid, int nneg, const int* matched, const unsigned char* has_gt, const float* gt_boxes,
                       const float* gt_scores, int G, const float* weights_host, float* sums, float* gobj, float* gdl, hipStream_t stream) {
-  return utv2_rpn_loss_fwd_range(obj, deltas, head, num_levels, hw_host, N, N, 0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx, neg_valid,
-                                 nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host, sums, gobj, gdl, stream);
+  return utv2_rpn_loss_fwd_range_f(obj, deltas, head, num_levels, hw_host, N, N, 0, A, ch, R, anchors, pos_idx, pos_valid, npos, neg_idx,
+                                   neg_valid, nneg, matched, has_gt, gt_boxes, gt_scores, G, weights_host, 0, 0.f, 0.f, sums, gobj, gdl, stream);
 }
 
 int utv2_rpn_loss_bwd_range(const float* gobj, const float* gdl, const float* gout_cls, const float* gout_loc, int head, int num_levels,
@@ -1820,12 +1898,19 @@ int utv2_rpn_loss_bwd(const float* gobj, const float* gdl, const float* gout_cls
                                  neg_valid, nneg, grad_obj, grad_deltas, stream);
 }
 
+int utv2_rpn_sample_keys_b(const float* max_iou, const unsigned char* lowq, const unsigned char* gt_valid, int G, const float* keys, int N,
+                           int R, float lo, float hi, const float* anchors, const float* image_hw, float boundary_thresh, int64_t* out,
+                           hipStream_t stream) {
+  if (!max_iou || !lowq || !gt_valid || !keys || !out || N < 1 || R < 1 || G < 1) return UTV2_EARG;
+  if (boundary_thresh != boundary_thresh || (boundary_thresh >= 0.f && (!anchors || !image_hw))) return UTV2_EARG;
+  hipLaunchKernelGGL(rpn_sample_keys_kernel, dim3(cdiv(R, 256), N), dim3(256), 0, stream, max_iou, lowq, gt_valid, G, keys, N, R, lo, hi,
+                     anchors, image_hw, boundary_thresh, (long long*)out);
+  return utv2_launch_status();
+}
+
 int utv2_rpn_sample_keys(const float* max_iou, const unsigned char* lowq, const unsigned char* gt_valid, int G, const float* keys, int N,
                          int R, float lo, float hi, int64_t* out, hipStream_t stream) {
-  if (!max_iou || !lowq || !gt_valid || !keys || !out || N < 1 || R < 1 || G < 1) return UTV2_EARG;
-  hipLaunchKernelGGL(rpn_sample_keys_kernel, dim3(cdiv(R, 256), N), dim3(256), 0, stream, max_iou, lowq, gt_valid, G, keys, N, R, lo, hi,
-                     (long long*)out);
-  return utv2_launch_status();
+  return utv2_rpn_sample_keys_b(max_iou, lowq, gt_valid, G, keys, N, R, lo, hi, nullptr, nullptr, -1.f, out, stream);
 }
 
 int utv2_rpn_sample_unpack(const int64_t* top, int k, int N, int npos_max, int nneg_max, const unsigned char* gt_valid, int G,

@@ -6,6 +6,7 @@ library is missing the import of any product op fails loudly (build it with
 `python __graft_entry__.py`).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -854,9 +855,11 @@ def _u8(t):
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
-def rpn_loss_fwd(obj, deltas, head_hw, N, A, R, anchors, s, gt_boxes, gt_scores, weights, batch=None, img0=0):
+def rpn_loss_fwd(obj, deltas, head_hw, N, A, R, anchors, s, gt_boxes, gt_scores, weights, batch=None, img0=0, loc_mode=0, smooth_l1_beta=0.0,
+                 scale_clamp=math.log(1000.0 / 16)):
     """(sums [2], gobj [N, npos+nneg], gdl [N, npos, 4]); head_hw = None: dense obj [N,R] / deltas [N,R,4]; else obj is deltas is the
-    level-first head output and head_hw the pixels per level.  s: the sampler's dict (pos_idx, pos_valid, neg_idx, neg_valid, matched32, has_gt)."""
+    level-first head output and head_hw the pixels per level.  s: the sampler's dict (pos_idx, pos_valid, neg_idx, neg_valid, matched32, has_gt).
+    loc_mode 0: smooth-L1 at smooth_l1_beta on the deltas, 1: "giou" on the boxes decoded with scale_clamp (utv2_rpn_loss_fwd_range_f)."""
     dev = obj.device
     npos, nneg = s["pos_idx"].shape[1], s["neg_idx"].shape[1]
     sums = torch.empty(2, dtype=torch.float32, device=dev)
@@ -865,10 +868,11 @@ def rpn_loss_fwd(obj, deltas, head_hw, N, A, R, anchors, s, gt_boxes, gt_scores,
     head = head_hw is not None
     hw = _iarr(head_hw if head else [1])
     G = gt_boxes.shape[1]
-    call("utv2_rpn_loss_fwd_range", _p(obj), _p(deltas), int(head), len(head_hw) if head else 1, ctypes.cast(hw, c_p), N,
+    call("utv2_rpn_loss_fwd_range_f", _p(obj), _p(deltas), int(head), len(head_hw) if head else 1, ctypes.cast(hw, c_p), N,
          N if batch is None else batch, img0, A, obj.shape[-1] if head else 0, R,
          _p(anchors), _p(s["pos_idx"]), _p(_u8(s["pos_valid"])), npos, _p(s["neg_idx"]), _p(_u8(s["neg_valid"])), nneg, _p(s["matched32"]),
-         _p(_u8(s["has_gt"])), _p(gt_boxes), _p(gt_scores), G, ctypes.cast(_farr(weights), c_p), _p(sums), _p(gobj), _p(gdl), _stream())
+         _p(_u8(s["has_gt"])), _p(gt_boxes), _p(gt_scores), G, ctypes.cast(_farr(weights), c_p), int(loc_mode), float(smooth_l1_beta),
+         float(scale_clamp), _p(sums), _p(gobj), _p(gdl), _stream())
     return sums, gobj, gdl
 
 
@@ -881,17 +885,24 @@ def rpn_loss_bwd(gobj, gdl, gout_cls, gout_loc, head_hw, N, A, ch, R, s, grad_ob
          _p(s["pos_idx"]), _p(_u8(s["pos_valid"])), npos, _p(s["neg_idx"]), _p(_u8(s["neg_valid"])), nneg, _p(grad_obj), _p(grad_deltas), _stream())
 
 
-def rpn_sample(mx, lowq, gt_valid, keys, lo, hi, npos_max, batch):
+def rpn_sample(mx, lowq, gt_valid, keys, lo, hi, npos_max, batch, anchors=None, image_hw=None, boundary_thresh=-1.0):
     """PseudoLabRPN.label_and_sample after the matching: labels + "k smallest keys" subsampling of positives / negatives as three
     launches (sortable keys, exact radix select, unpack).  -> pos_idx [N,npos_max] int64, pos_valid uint8, neg_idx [N,batch], neg_valid,
-    has_gt [N,1] uint8."""
+    has_gt [N,1] uint8.  boundary_thresh >= 0 (MODEL.RPN.BOUNDARY_THRESH): anchors [R,4] that leave their image (image_hw [N,2] float32:
+    h, w) by the threshold or more are candidates for neither draw (utv2_rpn_sample_keys_b)."""
     N, R = mx.shape
     dev = mx.device
     G = gt_valid.shape[1]
     k = max(npos_max, batch)
     assert k <= 2048 and keys.dtype == torch.float32 and tuple(keys.shape) == (N, R)
     skeys = torch.empty((2 * N, R), dtype=torch.int64, device=dev)
-    call("utv2_rpn_sample_keys", _p(mx), _p(_u8(lowq)), _p(gt_valid), G, _p(keys.contiguous()), N, R, float(lo), float(hi), _p(skeys), _stream())
+    if boundary_thresh >= 0:
+        assert anchors is not None and image_hw is not None and tuple(anchors.shape) == (R, 4) and tuple(image_hw.shape) == (N, 2)
+        assert anchors.dtype == torch.float32 and image_hw.dtype == torch.float32
+        call("utv2_rpn_sample_keys_b", _p(mx), _p(_u8(lowq)), _p(gt_valid), G, _p(keys.contiguous()), N, R, float(lo), float(hi), _p(anchors),
+             _p(image_hw), float(boundary_thresh), _p(skeys), _stream())
+    else:
+        call("utv2_rpn_sample_keys", _p(mx), _p(_u8(lowq)), _p(gt_valid), G, _p(keys.contiguous()), N, R, float(lo), float(hi), _p(skeys), _stream())
     ck = (N, R, str(dev))
     row_off = _rpn_sample_rows.get(ck)
     if row_off is None:

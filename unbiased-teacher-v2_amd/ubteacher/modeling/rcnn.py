@@ -26,8 +26,15 @@ from .backbone import _nchw_view, _xavier_init
 from .fcos import PaddedBoxes
 
 SCALE_CLAMP = math.log(1000.0 / 16)
-RPN_CH = 16   # 3 objectness + 12 deltas + 1 pad
+RPN_CH = 16   # 3 objectness + 12 deltas + 1 pad: rpn_channels(3), the shipped anchor count
+RPN_CH_ALIGN = 16   # the channel multiple the 1x1 fp32-output conv route takes
+RPN_MAX_A = 15
 PRED_CH = 96  # 81 cls + 4 deltas + 4 std + 7 pad
+
+
+def rpn_channels(A):
+    """channels of the fused RPN prediction conv for A anchors per cell: A objectness rows, 4A anchor-major delta rows, zero pad rows"""
+    return -(-5 * A // RPN_CH_ALIGN) * RPN_CH_ALIGN
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -114,7 +121,8 @@ class _RpnLossFn(torch.autograd.Function):
         R = anchors.shape[0]
         hw = [h * w for (h, w) in head_hw] if head_hw is not None else None
         sums, gobj, gdl = hip.rpn_loss_fwd(obj.detach(), deltas.detach(), hw, N, rpn.A, R, anchors, s, gt["boxes"],
-                                           gt["scores"] if "scores" in gt else None, rpn.box_weights, batch=batch, img0=img0)
+                                           gt["scores"] if "scores" in gt else None, rpn.box_weights, batch=batch, img0=img0,
+                                           loc_mode=rpn.loc_mode, smooth_l1_beta=rpn.smooth_l1_beta, scale_clamp=SCALE_CLAMP)
         ctx.meta = (hw, N, rpn.A, R, s, tuple(obj.shape), tuple(deltas.shape), head_hw is not None, batch, img0)
         ctx.save_for_backward(gobj, gdl)
         return sums
@@ -150,20 +158,47 @@ class _RoiBoxLossFn(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------------------
 class AnchorGenerator:
-    """D2 DefaultAnchorGenerator [D2-recall]: sizes per level x aspect ratios, offset 0, order (H, W, A)."""
+    """D2 DefaultAnchorGenerator [D2-recall]: SIZES and ASPECT_RATIOS are each one list for every level or one list per level, the cell
+    is sizes outer x ratios inner, the shifts start at OFFSET * stride, order (H, W, A).  The RPN head predicts the same number of
+    anchors per cell on every level: unequal counts are refused."""
 
     def __init__(self, cfg, strides):
-        self.sizes = [list(s) for s in cfg.MODEL.ANCHOR_GENERATOR.SIZES]
-        self.ratios = list(cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS[0])
+        ag = cfg.MODEL.ANCHOR_GENERATOR
+        if ag.NAME != "DefaultAnchorGenerator":
+            raise NotImplementedError("MODEL.ANCHOR_GENERATOR.NAME %r: only \"DefaultAnchorGenerator\" is built" % (ag.NAME,))
         self.strides = strides
-        self.A = len(self.sizes[0]) * len(self.ratios)
+        self.sizes = self._per_level(ag.SIZES, len(strides), "MODEL.ANCHOR_GENERATOR.SIZES")
+        self.level_ratios = self._per_level(ag.ASPECT_RATIOS, len(strides), "MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS")
+        self.ratios = self.level_ratios[0]
+        self.offset = float(ag.OFFSET)
+        if not 0.0 <= self.offset < 1.0:
+            raise ValueError("MODEL.ANCHOR_GENERATOR.OFFSET must be in [0, 1), got %r" % (ag.OFFSET,))
+        counts = [len(s) * len(r) for s, r in zip(self.sizes, self.level_ratios)]
+        if len(set(counts)) != 1 or counts[0] < 1:
+            raise ValueError("MODEL.ANCHOR_GENERATOR.SIZES x MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS must give the same number (>= 1) of anchors "
+                             "per cell on every level, got %s" % (counts,))
+        self.A = counts[0]
         self._cache = {}
 
-    def cell(self, sizes):
+    @staticmethod
+    def _per_level(params, n, name):
+        """D2 _broadcast_params: a flat list or a one-element list of lists stands for every level"""
+        params = list(params)
+        if not params:
+            raise ValueError("%s is empty" % name)
+        if not isinstance(params[0], (list, tuple)):
+            return [[float(v) for v in params] for _ in range(n)]
+        if len(params) == 1:
+            return [[float(v) for v in params[0]] for _ in range(n)]
+        if len(params) != n:
+            raise ValueError("%s has %d lists for %d feature levels" % (name, len(params), n))
+        return [[float(v) for v in p] for p in params]
+
+    def cell(self, sizes, ratios=None):
         out = []
         for s in sizes:
             area = s ** 2.0
-            for r in self.ratios:
+            for r in (self.ratios if ratios is None else ratios):
                 w = math.sqrt(area / r)
                 h = r * w
                 out.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
@@ -173,12 +208,13 @@ class AnchorGenerator:
         key = (tuple(level_hw), str(device))
         if key not in self._cache:
             per = []
-            for (h, w), s, sz in zip(level_hw, self.strides, self.sizes):
-                sx = torch.arange(0, w * s, step=s, dtype=torch.float32)
-                sy = torch.arange(0, h * s, step=s, dtype=torch.float32)
+            for (h, w), s, sz, rt in zip(level_hw, self.strides, self.sizes, self.level_ratios):
+                o = self.offset * s
+                sx = torch.arange(o, w * s + o, step=s, dtype=torch.float32)[:w]
+                sy = torch.arange(o, h * s + o, step=s, dtype=torch.float32)[:h]
                 yy, xx = torch.meshgrid(sy, sx, indexing="ij")
                 shifts = torch.stack((xx.reshape(-1), yy.reshape(-1), xx.reshape(-1), yy.reshape(-1)), dim=1)
-                per.append((shifts.view(-1, 1, 4) + self.cell(sz).view(1, -1, 4)).reshape(-1, 4))
+                per.append((shifts.view(-1, 1, 4) + self.cell(sz, rt).view(1, -1, 4)).reshape(-1, 4))
             self._cache[key] = [p.to(device) for p in per]
         return self._cache[key]
 
@@ -191,9 +227,16 @@ class PseudoLabRPN:
         self.strides = [2 ** int(f[1:]) for f in self.in_features]
         self.anchor_generator = AnchorGenerator(cfg, self.strides)
         A = self.anchor_generator.A
-        assert A == 3
-        self.A = A
+        if A > RPN_MAX_A:
+            raise NotImplementedError("MODEL.ANCHOR_GENERATOR.SIZES x ASPECT_RATIOS give %d anchors per cell: the RPN head is built for "
+                                      "1 .. %d" % (A, RPN_MAX_A))
+        if r.HEAD_NAME != "StandardRPNHead":
+            raise NotImplementedError("MODEL.RPN.HEAD_NAME %r: only \"StandardRPNHead\" is built" % (r.HEAD_NAME,))
         C = in_channels
+        if list(r.CONV_DIMS) not in ([-1], [C]):
+            raise NotImplementedError("MODEL.RPN.CONV_DIMS %r: only one conv of the input width ([-1] or [%d]) is built" % (list(r.CONV_DIMS), C))
+        self.A = A
+        self.ch = ch = rpn_channels(A)
         w = store.new((C, 9 * C), "decay", lambda t: t.normal_(0.0, 0.01)).export(prefix + ".rpn_head.conv.weight", _nchw_view(C, C, 3))
         b = store.new((C,), "decay", lambda t: t.zero_()).export(prefix + ".rpn_head.conv.bias")
         self.conv = ops.Conv(w, C, C, 3, 1, 1, bias=b, relu=True)
@@ -201,13 +244,13 @@ class PseudoLabRPN:
         def init_pred(t):
             t.zero_()
             t[:A + 4 * A].normal_(0.0, 0.01)
-        wp = store.new((RPN_CH, C), "decay", init_pred)
+        wp = store.new((ch, C), "decay", init_pred)
         wp.export(prefix + ".rpn_head.objectness_logits.weight", lambda t: t[0:A].view(A, 1, 1, C).permute(0, 3, 1, 2))
         wp.export(prefix + ".rpn_head.anchor_deltas.weight", lambda t: t[A:5 * A].view(4 * A, 1, 1, C).permute(0, 3, 1, 2))
-        bp = store.new((RPN_CH,), "decay", lambda t: t.zero_())
+        bp = store.new((ch,), "decay", lambda t: t.zero_())
         bp.export(prefix + ".rpn_head.objectness_logits.bias", lambda t: t[0:A])
         bp.export(prefix + ".rpn_head.anchor_deltas.bias", lambda t: t[A:5 * A])
-        self.pred = ops.Conv(wp, C, RPN_CH, 1, 1, 0, bias=bp, out_fp32=True)
+        self.pred = ops.Conv(wp, C, ch, 1, 1, 0, bias=bp, out_fp32=True)
         # the 3x3 conv's ReLU output has one consumer, the prediction conv: its dgrad epilogue applies the mask (ops.premask_on) instead of
         # a pass over the [all levels x images, 256] gradient at the top of the 3x3 conv's backward (450 us per step)
         self.pred.premask_input = True
@@ -221,7 +264,15 @@ class PseudoLabRPN:
         self.min_box_size = cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE
         self.loss_weight = {"loss_rpn_cls": r.LOSS_WEIGHT, "loss_rpn_loc": r.BBOX_REG_LOSS_WEIGHT * r.LOSS_WEIGHT}
         self.box_weights = tuple(r.BBOX_REG_WEIGHTS)
-        assert r.BOUNDARY_THRESH < 0 and r.BBOX_REG_LOSS_TYPE == "smooth_l1" and r.SMOOTH_L1_BETA == 0.0
+        # D2 _dense_box_regression_loss: "smooth_l1" at SMOOTH_L1_BETA on the deltas, "giou" on the decoded boxes (utv2_rpn_loss_fwd_f)
+        if r.BBOX_REG_LOSS_TYPE not in ("smooth_l1", "giou"):
+            raise ValueError("Invalid dense box regression loss type '%s' (MODEL.RPN.BBOX_REG_LOSS_TYPE: \"smooth_l1\" or \"giou\")"
+                             % (r.BBOX_REG_LOSS_TYPE,))
+        self.loc_mode = 1 if r.BBOX_REG_LOSS_TYPE == "giou" else 0
+        self.smooth_l1_beta = float(r.SMOOTH_L1_BETA)
+        if not self.smooth_l1_beta >= 0.0:
+            raise ValueError("MODEL.RPN.SMOOTH_L1_BETA must be >= 0, got %r" % (r.SMOOTH_L1_BETA,))
+        self.boundary_thresh = float(r.BOUNDARY_THRESH)   # < 0: every anchor takes part (D2 RPN.anchor_boundary_thresh)
         self.training = True
         self.sample_keys = None  # tests inject [N, R] keys in [0,1)
 
@@ -247,7 +298,7 @@ class PseudoLabRPN:
         obj, dl = [], []
         r = 0
         for (h, w) in hw:
-            blk = big[r:r + N * h * w].view(N, h * w, RPN_CH)
+            blk = big[r:r + N * h * w].view(N, h * w, self.ch)
             obj.append(blk[:, :, :A].reshape(N, -1))
             dl.append(blk[:, :, A:5 * A].reshape(N, h * w * A, 4))
             r += N * h * w
@@ -258,7 +309,7 @@ class PseudoLabRPN:
         anchors = self.anchor_generator(hw, big.device)
         losses = {}
         if (self.training and compute_loss) or compute_val_loss:
-            losses = self.losses(self._anchors_cat(anchors, hw, big.device), big, None, gt, head_hw=hw)
+            losses = self.losses(self._anchors_cat(anchors, hw, big.device), big, None, gt, head_hw=hw, image_sizes=image_sizes)
             losses = {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}  # applied twice
         with torch.no_grad():
             sel = self._pre_nms_topk(big.detach(), N, hw)
@@ -276,7 +327,7 @@ class PseudoLabRPN:
         big, hw, N = self._head(features)
         anchors = self.anchor_generator(hw, big.device)
         acat = self._anchors_cat(anchors, hw, big.device)
-        losses = self.losses(acat, big, None, gt_labeled, head_hw=hw, batch=N, img0=0, raw=raw)
+        losses = self.losses(acat, big, None, gt_labeled, head_hw=hw, batch=N, img0=0, raw=raw, image_sizes=list(image_sizes)[:n_labeled])
         if not raw:
             losses = {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}  # applied twice, as in forward()
         sample_l = self._last_sample
@@ -287,11 +338,12 @@ class PseudoLabRPN:
             else:
                 obj, dl = self._per_image_views(big.detach(), N, hw)
                 proposals = self.predict_proposals(anchors, obj, dl, image_sizes)
-        return dict(big=big, hw=hw, N=N, acat=acat, n_labeled=n_labeled, sample_l=sample_l), proposals, losses
+        return dict(big=big, hw=hw, N=N, acat=acat, n_labeled=n_labeled, sample_l=sample_l, image_sizes=list(image_sizes)), proposals, losses
 
     def forward_joint_finish(self, ctx, gt_unlabeled, raw=False):
         """the pseudo-labeled images' losses of a forward_joint_begin batch"""
-        losses = self.losses(ctx["acat"], ctx["big"], None, gt_unlabeled, head_hw=ctx["hw"], batch=ctx["N"], img0=ctx["n_labeled"], raw=raw)
+        losses = self.losses(ctx["acat"], ctx["big"], None, gt_unlabeled, head_hw=ctx["hw"], batch=ctx["N"], img0=ctx["n_labeled"], raw=raw,
+                             image_sizes=ctx["image_sizes"][ctx["n_labeled"]:])
         if raw:
             return losses
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in losses.items()}
@@ -369,9 +421,19 @@ class PseudoLabRPN:
 
     # -- labels + sampling (rpn.py:78-150 and D2 label_and_sample_anchors) -----------------------------------
     @torch.no_grad()
-    def label_and_sample(self, anchors, gt):
+    def label_and_sample(self, anchors, gt, image_sizes=None):
+        """image_sizes: the (h, w) of gt's images - needed when MODEL.RPN.BOUNDARY_THRESH >= 0 only: an anchor that leaves its image (not
+        the padded canvas) by the threshold or more is ignored (label -1), after everything else has been decided (rpn.py:117-134)"""
         N = gt.n
         R = anchors.shape[0]
+        bt = self.boundary_thresh
+        image_hw = None
+        if bt >= 0:
+            if image_sizes is None or len(image_sizes) != N:
+                raise ValueError("MODEL.RPN.BOUNDARY_THRESH >= 0 needs the size of each of the %d images" % N)
+            sizes = tuple((int(s[0]), int(s[1])) for s in image_sizes)
+            image_hw = _device_const(("rpn_hw", sizes, str(anchors.device)),
+                                     lambda: torch.tensor(sizes, dtype=torch.float32, device=anchors.device).view(N, 2))
         mx, arg, gmax = hip.match_boxes(anchors, gt["boxes"], gt["valid"], want_gt_max=True)
         lowq = hip.match_lowq(anchors, gt["boxes"], gt["valid"], gmax)
         lo, hi = self.iou_thresholds
@@ -379,7 +441,8 @@ class PseudoLabRPN:
         npos_max = int(self.batch_size_per_image * self.positive_fraction)
         if max(npos_max, self.batch_size_per_image) <= 2048 and os.environ.get("UTV2_FUSED_SAMPLERS", "1") != "0":
             # labels (IoU thresholds, allow_low_quality_matches, images without gt) and both "k smallest keys" draws in three launches
-            pidx, pval, nidx, nval, has_gt = hip.rpn_sample(mx, lowq, gt["valid"], keys, lo, hi, npos_max, self.batch_size_per_image)
+            pidx, pval, nidx, nval, has_gt = hip.rpn_sample(mx, lowq, gt["valid"], keys, lo, hi, npos_max, self.batch_size_per_image,
+                                                            anchors=anchors, image_hw=image_hw, boundary_thresh=bt)
             return dict(pos_idx=pidx, pos_valid=pval, neg_idx=nidx, neg_valid=nval, matched32=arg, has_gt=has_gt)
         has_gt = gt["valid"].bool().any(dim=1, keepdim=True)
         one = torch.ones((), dtype=torch.int8, device=anchors.device)
@@ -387,20 +450,26 @@ class PseudoLabRPN:
         labels = torch.where(mx >= hi, one, labels)
         labels = torch.where(lowq.bool(), one, labels)   # allow_low_quality_matches
         labels = torch.where(has_gt, labels, torch.zeros_like(labels))
+        if bt >= 0:   # Boxes.inside_box(image_size, BOUNDARY_THRESH) [D2-recall]
+            inside = ((anchors[None, :, 0] >= -bt) & (anchors[None, :, 1] >= -bt) & (anchors[None, :, 2] < image_hw[:, 1:2] + bt)
+                      & (anchors[None, :, 3] < image_hw[:, 0:1] + bt))
+            labels = torch.where(inside, labels, one * -1)
         pidx, pval = sample_k_smallest(keys, labels == 1, npos_max)
         npos = pval.sum(1, keepdim=True)
         nidx, nval = sample_k_smallest(keys, labels == 0, self.batch_size_per_image)
         nval = nval & (torch.arange(nidx.shape[1], device=anchors.device)[None, :] < (self.batch_size_per_image - npos))
         return dict(pos_idx=pidx, pos_valid=pval, neg_idx=nidx, neg_valid=nval, matched32=arg, has_gt=has_gt)
 
-    def losses(self, anchors, obj, deltas, gt, head_hw=None, batch=None, img0=0, raw=False):
+    def losses(self, anchors, obj, deltas, gt, head_hw=None, batch=None, img0=0, raw=False, image_sizes=None):
         """rpn.py:153-225: BCE(sum) over sampled anchors (optionally weighted by the matched pseudo-box score,
-        negatives too - SURVEY B4) + L1 on positives, both / (batch_size_per_image * N), weights applied here too.
-        One fused forward launch and one backward launch (utv2_rpn_loss_fwd / _bwd).  obj [N,R] + deltas [N,R,4], or - head_hw given -
-        obj = the level-first head output [P, RPN_CH] (deltas ignored): no per-image copies of the logits / deltas are made.
-        batch / img0 (head form): the head output covers `batch` images and gt's are images [img0, img0 + gt.n) of it."""
+        negatives too - SURVEY B4) + the localisation loss on positives (L1 at the shipped keys; MODEL.RPN.SMOOTH_L1_BETA /
+        BBOX_REG_LOSS_TYPE "giou"), both / (batch_size_per_image * N), weights applied here too.
+        One fused forward launch and one backward launch (utv2_rpn_loss_fwd_f / _bwd).  obj [N,R] + deltas [N,R,4], or - head_hw given -
+        obj = the level-first head output [P, self.ch] (deltas ignored): no per-image copies of the logits / deltas are made.
+        batch / img0 (head form): the head output covers `batch` images and gt's are images [img0, img0 + gt.n) of it.
+        image_sizes: (h, w) of gt's images, read when MODEL.RPN.BOUNDARY_THRESH >= 0."""
         N = gt.n
-        s = self.label_and_sample(anchors, gt)
+        s = self.label_and_sample(anchors, gt, image_sizes)
         sums = _RpnLossFn.apply(obj, obj if head_hw is not None else deltas, self, anchors, s, gt, head_hw, N, batch, img0)
         norm = self.batch_size_per_image * N
         self._last_sample = s
