@@ -386,12 +386,8 @@ int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, 
                           int C, int stride, int level, int method, int MAXC, int slot0, float* oboxes, float* oscores, int* ocls,
                           float* oloc, float* octr, float* oconf, float* ostd, int* olevel, unsigned char* ovalid,
                           utv2_stream_t stream);
-/* Scale layer fcos/fcos.py:22-28,356-357 on the first ncols columns of strided rows */
-int utv2_scale_cols(float* y, int64_t rows, int row_stride, int ncols, const float* s, utv2_stream_t stream);
-int utv2_scale_cols_bwd(float* g, const float* ypost, int64_t rows, int row_stride, int ncols, const float* s, float* dsum,
-                        float* ws, utv2_stream_t stream);
-/* the Scale layers of ALL levels of a level-first matrix at once (one launch forward, two backward instead of four per level):
- * row0_host = host int64[nlev + 1] (first row of each level, then the end), s_host / sgrad_host = host arrays of nlev DEVICE pointers
+/* Scale layers fcos/fcos.py:22-28,356-357 (one learnable scalar per level on the first ncols columns of strided rows) of ALL levels of a
+ * level-first matrix at once (one launch forward, two backward): row0_host = host int64[nlev + 1] (first row of each level, then the end), s_host / sgrad_host = host arrays of nlev DEVICE pointers
  * (the per-level scalar and its gradient, accumulated: sgrad_l += sum(g_in * ypost) / s_l).  nlev <= 8; ws >= nlev * 1024 floats */
 int utv2_scale_cols_ml(float* y, int nlev, const int64_t* row0_host, int row_stride, int ncols, const float* const* s_host,
                        utv2_stream_t stream);

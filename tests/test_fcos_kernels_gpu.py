@@ -630,48 +630,50 @@ def test_two_criteria_in_one_launch_set_equal_two_calls(fc):
         outm.predict_proposals(head_out, level_hw, sizes, ("cls", "nope"))
 
 
-def test_scale_cols_ml_forward_backward_vs_torch():
-    """the per-level Scale layers (reference fcos/fcos.py:22-41,338-364: bbox_pred * scale_l) of all levels in one launch forward / two
-    backward, against plain torch arithmetic: y[:, :68] *= s_l; dL/dx = g * s_l; dL/ds_l = sum(g * x) (= sum(g * y) / s_l)"""
+FIVE_LEVELS = [(0, 4033), (4033, 5050), (5050, 5301), (5301, 5367), (5367, 5387)]
+
+
+def check_scale_ml(rows, BS, nc, seed):
+    """y[:, :nc] *= s_l; dL/dx = g * s_l; dL/ds_l = sum(g * x) (= sum(g * y) / s_l), against plain torch arithmetic"""
     from ubteacher import hip
-    g = torch.Generator().manual_seed(21)
-    rows = [(0, 4033), (4033, 5050), (5050, 5301), (5301, 5367), (5367, 5387)]
-    P, BS, nc = rows[-1][1], 80, 68
+    g = torch.Generator().manual_seed(seed)
+    P, L = rows[-1][1], len(rows)
     x = torch.randn(P, BS, generator=g).to(DEV)
     gy = torch.randn(P, BS, generator=g).to(DEV)
-    scales = [torch.tensor([0.5 + 0.37 * l], device=DEV) for l in range(5)]
+    scales = [torch.tensor([0.5 + 0.37 * l], device=DEV) for l in range(L)]
     y = x.clone()
     hip.scale_cols_ml(y, rows, nc, scales)
     want = x.clone()
     for (a, b), s in zip(rows, scales):
         want[a:b, :nc] *= s
     assert torch.equal(y, want)
-    sgr = [torch.full((1,), 0.25, device=DEV) for _ in range(5)]          # accumulated into
+    sgr = [torch.full((1,), 0.25, device=DEV) for _ in range(L)]          # accumulated into
     gin = gy.clone()
     hip.scale_cols_bwd_ml(gin, y, rows, nc, scales, sgr)
     for l, ((a, b), s) in enumerate(zip(rows, scales)):
         assert torch.equal(gin[a:b, :nc], gy[a:b, :nc] * s) and torch.equal(gin[a:b, nc:], gy[a:b, nc:])
         ds = (gy[a:b, :nc].double() * x[a:b, :nc].double()).sum()
         assert abs(float(sgr[l]) - 0.25 - float(ds)) <= 2e-5 * float((gy[a:b, :nc].double() * x[a:b, :nc].double()).abs().sum()) + 1e-6
+        if a == b:
+            assert float(sgr[l]) == 0.25                                   # an empty level: its gradient is unchanged
     # bit-deterministic (fixed-order partial sums)
-    sgr2 = [torch.full((1,), 0.25, device=DEV) for _ in range(5)]
+    sgr2 = [torch.full((1,), 0.25, device=DEV) for _ in range(L)]
     gin2 = gy.clone()
     hip.scale_cols_bwd_ml(gin2, y, rows, nc, scales, sgr2)
-    assert all(torch.equal(a, b) for a, b in zip(sgr, sgr2))
+    assert torch.equal(gin, gin2) and all(torch.equal(a, b) for a, b in zip(sgr, sgr2))
 
 
-def test_scale_cols_bwd_pad16_equals_scale_then_pad():
-    """utv2_scale_cols_bwd_ml_pad16 (Scale backward + conversion + zero padding in one out-of-place pass) == utv2_scale_cols_bwd_ml on
-    a clone followed by utv2_pad_cols_bf16, bit for bit (values and the Scale gradients), and leaves the incoming gradient untouched"""
+def check_scale_pad16(rows, BS, nc, cpad, seed):
+    """utv2_scale_cols_bwd_ml_pad16 == utv2_scale_cols_bwd_ml on a clone followed by utv2_pad_cols_bf16, bit for bit (values and the
+    Scale gradients to another partition of the same sum), and leaves the incoming gradient untouched"""
     from ubteacher import hip
-    g = torch.Generator().manual_seed(22)
-    rows = [(0, 4033), (4033, 5050), (5050, 5301), (5301, 5367), (5367, 5387)]
-    P, BS, nc, cpad = rows[-1][1], 80, 68, 96
+    g = torch.Generator().manual_seed(seed)
+    P, L = rows[-1][1], len(rows)
     y = torch.randn(P, BS, generator=g).to(DEV)
     gy = torch.randn(P, BS, generator=g).to(DEV)
-    scales = [torch.tensor([0.5 + 0.37 * l], device=DEV) for l in range(5)]
-    sg_a = [torch.zeros(1, device=DEV) for _ in range(5)]
-    sg_b = [torch.zeros(1, device=DEV) for _ in range(5)]
+    scales = [torch.tensor([0.5 + 0.37 * l], device=DEV) for l in range(L)]
+    sg_a = [torch.zeros(1, device=DEV) for _ in range(L)]
+    sg_b = [torch.zeros(1, device=DEV) for _ in range(L)]
     ref = gy.clone()
     hip.scale_cols_bwd_ml(ref, y, rows, nc, scales, sg_a)
     want = hip.pad_cols_bf16(ref, cpad)
@@ -681,3 +683,187 @@ def test_scale_cols_bwd_pad16_equals_scale_then_pad():
     assert got.dtype == hip.h16_dtype() and tuple(got.shape) == (P, cpad) and torch.equal(got, want)
     assert float(got[:, BS:].abs().max()) == 0.0
     assert all(abs(float(a) - float(b)) <= 1e-5 * max(abs(float(a)), 1.0) for a, b in zip(sg_a, sg_b))   # another partition of the same sum
+
+
+def test_scale_cols_ml_forward_backward_vs_torch():
+    """the per-level Scale layers (reference fcos/fcos.py:22-41,338-364: bbox_pred * scale_l) of all levels in one launch forward / two
+    backward, against plain torch arithmetic (row stride and column count multiples of 4: the float4 walk of the backward)"""
+    check_scale_ml(FIVE_LEVELS, 80, 68, 21)
+
+
+def test_scale_cols_bwd_pad16_equals_scale_then_pad():
+    """utv2_scale_cols_bwd_ml_pad16 (Scale backward + conversion + zero padding in one out-of-place pass) == utv2_scale_cols_bwd_ml on
+    a clone followed by utv2_pad_cols_bf16, bit for bit (values and the Scale gradients), and leaves the incoming gradient untouched"""
+    check_scale_pad16(FIVE_LEVELS, 80, 68, 96, 22)
+
+
+def test_scale_cols_ml_general_walk_odd_sizes_and_an_empty_level():
+    """5 scaled columns of 12: the scalar walk of the backward (scale_cols_bwd_ml_kernel<false>), which no model shape reaches; 37 and 13
+    rows are multiples of nothing and the middle level is empty - its Scale gradient stays as it was"""
+    check_scale_ml([(0, 37), (37, 37), (37, 50)], 12, 5, 23)
+
+
+def test_scale_cols_one_level():
+    """a single level - the shape the per-level entry points (removed) served - through the three multi-level entry points"""
+    check_scale_ml([(0, 37)], 80, 68, 24)
+    check_scale_pad16([(0, 37)], 80, 68, 96, 25)
+
+
+def test_conv_with_scale_end_to_end_vs_fp64():
+    """ops.Conv with one Scale per level (the FCOS box head, fcos/fcos.py:338-364: bbox_pred * scale_l on the first `colscale` channels) in
+    exact-fp32 mode, forward and backward, against F.conv2d per level in fp64 followed by the multiply: y, dx, dw, db and every d s_l.
+    Shape: the exact-fp32 level-first kernel takes C % 16 == 0 only, so not 8 -> 16 channels but the smallest shape of the conv tests that
+    goes down this route: 3x3, 32 -> 32 channels, N = 3, five levels (tests/test_conv_ml_gpu.py::test_ml_conv_fwd_dgrad_wgrad).
+    Tolerance: 2e-4 of the max-norm, the bound of those tests (tests/test_conv_gpu.py:47 forward, :60 dx, :65 dw, :68 db; the same figure at
+    tests/test_conv_ml_gpu.py:35,40,43).  d s_l = sum g * u over the scaled columns of the conv output u: the conv's 2e-4 max|u| on every
+    term, plus the Scale kernel's own summation bound of the neighbouring test, 2e-5 sum|g u| + 1e-6."""
+    from ubteacher import ops
+    from ubteacher.params import ParamStore
+    g = torch.Generator().manual_seed(31)
+    N, C, K, nc = 3, 32, 32, 8
+    level_hw = [(12, 16), (6, 8), (3, 4), (2, 2), (1, 1)]
+    L = len(level_hw)
+    meta = ops.LevelMeta(N, level_hw)
+    before = ops.PRECISION[0]
+    try:
+        ops.set_precision("fp32")
+        store = ParamStore()
+        w = store.new((K, 9 * C), "decay", lambda t: t.normal_(0.0, 0.1))
+        b = store.new((K,), "decay", lambda t: t.normal_(0.0, 0.5))
+        hs = [store.new((1,), "decay", lambda t, l=l: t.fill_(0.6 + 0.35 * l)) for l in range(L)]
+        conv = ops.Conv(w, C, K, 3, 1, 1, bias=b, colscale=nc, out_fp32=True)
+        store.finalize("cuda")
+        store.grad.zero_()
+        xs = [torch.randn(N, C, h, w_, generator=g) for h, w_ in level_hw]
+        x = torch.cat([t.permute(0, 2, 3, 1).reshape(-1, C) for t in xs]).to(DEV).requires_grad_(True)
+        with pytest.raises(AssertionError):
+            conv(x, meta=meta, colscale_handle=hs[0])          # a single Handle
+        with pytest.raises(AssertionError):
+            conv(x.detach().view(1, -1, 1, C), colscale_handle=hs)   # no meta
+        y = conv(x, meta=meta, colscale_handle=hs)
+        assert y.dtype == torch.float32 and tuple(y.shape) == (meta.P, K)
+        dys = [torch.randn(N, K, h, w_, generator=g) for h, w_ in level_hw]
+        y.backward(torch.cat([t.permute(0, 2, 3, 1).reshape(-1, K) for t in dys]).to(DEV))
+        torch.cuda.synchronize()
+        # fp64 reference
+        wr = w.t.detach().cpu().double().view(K, 3, 3, C).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+        br = b.t.detach().cpu().double().clone().requires_grad_(True)
+        sr = [h.t.detach().cpu().double().clone().requires_grad_(True) for h in hs]
+        xr = [t.double().requires_grad_(True) for t in xs]
+        us = [F.conv2d(t, wr, br, 1, 1) for t in xr]
+        yr = [torch.cat([u[:, :nc] * s, u[:, nc:]], dim=1) for u, s in zip(us, sr)]
+        torch.autograd.backward(yr, [t.double() for t in dys])
+
+        def relerr(a, ref):
+            return (a.double() - ref).abs().max().item() / (ref.abs().max().item() + 1e-12)
+
+        for l in range(L):
+            assert relerr(meta.level_view(y.detach(), l).permute(0, 3, 1, 2).cpu(), yr[l].detach()) < 2e-4, l
+            assert relerr(meta.level_view(x.grad, l).permute(0, 3, 1, 2).cpu(), xr[l].grad) < 2e-4, l
+            gu = dys[l][:, :nc].double() * us[l][:, :nc].detach()
+            bound = 2e-4 * us[l][:, :nc].detach().abs().max().item() * dys[l][:, :nc].double().abs().sum().item() + 2e-5 * gu.abs().sum().item() + 1e-6
+            assert abs(float(hs[l].g) - float(sr[l].grad)) <= bound, (l, float(hs[l].g), float(sr[l].grad), bound)
+        assert relerr(w.g.cpu(), wr.grad.permute(0, 2, 3, 1).reshape(K, -1)) < 2e-4
+        assert relerr(b.g.cpu(), br.grad) < 2e-4
+    finally:
+        ops.set_precision(before)
+
+
+def _decode_outs(N, MAXC):
+    return dict(boxes=torch.full((N, MAXC, 4), 9.0, device=DEV), scores=torch.full((N, MAXC), 9.0, device=DEV),
+                classes=torch.full((N, MAXC), 9, dtype=torch.int32, device=DEV), locations=torch.full((N, MAXC, 2), 9.0, device=DEV),
+                centerness=torch.full((N, MAXC), 9.0, device=DEV), cls_confid=torch.full((N, MAXC), 9.0, device=DEV),
+                reg_pred_std=torch.full((N, MAXC, 4), 9.0, device=DEV), fpn_levels=torch.full((N, MAXC), 9, dtype=torch.int32, device=DEV),
+                valid=torch.full((N, MAXC), 9, dtype=torch.uint8, device=DEV))
+
+
+def test_decode_keys_outside_the_level_are_empty_slots_in_both_heads():
+    """A key whose flat index is HW * C or beyond cannot come from utv2_fcos_rank_keys; both decode kernels write it as an empty slot (valid 0,
+    score -1, zeros, the level) like a -1 key and never follow it - one shared test of the key (the discrete kernel used to read out of
+    bounds there).  The valid key between them is decoded as ever."""
+    import math
+    from ubteacher import hip
+    g = torch.Generator().manual_seed(5)
+    N, HW, Wl, C, K, stride, level = 1, 6, 3, 2, 4, 8, 2
+    logits = torch.randn((HW, C), generator=g)
+    rank = torch.rand(K, generator=g)
+    flat = torch.tensor([0, 7, HW * C, 0xFFFFFFFE], dtype=torch.int64)
+    keys = ((rank.view(torch.int32).long() << 32) | (0xFFFFFFFF - flat)).view(1, K)
+    keys[0, 0] = -1
+    assert int(keys[0, 3]) > 0 and int(keys[0, 3]) & 0xFFFFFFFF == 1
+    hw, c = 7 // C, 7 % C
+    x, y = float((hw % Wl) * stride + stride // 2), float((hw // Wl) * stride + stride // 2)
+    box_d = torch.zeros((HW, 80))
+    box_d[:, :73] = torch.randn((HW, 73), generator=g) * 2
+    box_c = torch.randn((HW, 16), generator=g) * 2
+    d_disc = (torch.softmax(box_d[hw, :68].double().view(4, 17), dim=1) * torch.arange(17, dtype=torch.float64)).sum(1)
+    d_cont = torch.clamp(box_c[hw, :4], min=0).double()
+    for name, box, d, std, ctr in (("discrete", box_d, d_disc, box_d[hw, 68:72], box_d[hw, 72]),
+                                   ("continuous", box_c, d_cont, box_c[hw, 4:8], box_c[hw, 8])):
+        outs = _decode_outs(N, K)
+        if name == "discrete":
+            hip.fcos_decode(keys.to(DEV), logits.to(DEV), box.to(DEV), 16, N, HW, Wl, stride, level, 1, 0, outs)
+        else:
+            hip.fcos_decode_cont(keys.to(DEV), logits.to(DEV), box.to(DEV), N, HW, Wl, stride, level, 1, 0, outs)
+        o = {k: v.cpu()[0] for k, v in outs.items()}
+        for sl in (0, 2, 3):
+            assert int(o["valid"][sl]) == 0 and float(o["scores"][sl]) == -1.0 and int(o["fpn_levels"][sl]) == level, (name, sl)
+            assert int(o["classes"][sl]) == 0 and float(o["centerness"][sl]) == 0.0 and float(o["cls_confid"][sl]) == 0.0, (name, sl)
+            assert torch.all(o["boxes"][sl] == 0) and torch.all(o["reg_pred_std"][sl] == 0) and torch.all(o["locations"][sl] == 0), (name, sl)
+        want = torch.tensor([x, y, x, y], dtype=torch.float64) + torch.tensor([-1.0, -1.0, 1.0, 1.0], dtype=torch.float64) * d * stride
+        close(o["boxes"][1], want, rtol=1e-5, atol=1e-4)
+        assert int(o["classes"][1]) == c and int(o["fpn_levels"][1]) == level and int(o["valid"][1]) == 1, name
+        assert torch.equal(o["reg_pred_std"][1], std) and o["locations"][1].tolist() == [x, y], name
+        assert abs(float(o["scores"][1]) - math.sqrt(float(rank[1]))) <= 1e-6
+        assert abs(float(o["centerness"][1]) - float(torch.sigmoid(ctr))) <= 1e-6
+        assert abs(float(o["cls_confid"][1]) - float(torch.sigmoid(logits[hw, c]))) <= 1e-6
+
+
+def test_discrete_and_continuous_heads_agree_on_one_hot_rows():
+    """A discrete row whose four softmaxes are one-hot (logit 60 at bin j_b >= 1, 0 elsewhere) has the Integral exactly j_b: in the kernels'
+    around-the-mode form d = j_b + sum_j p_j (j - j_b), the sum is ~1e-24 (fp32, checked below in numpy, and in double) and vanishes against
+    j_b >= 1 - it would not against j_b = 0, so bin 0 is not used.  A continuous row holding float(j_b) has the same distances.  With the
+    same std / ctr logits, targets and bvars the two heads then run the SAME arithmetic - there is one copy of every formula on (d, t, std,
+    ctr) in csrc/fcos.hip - so for every legal flag value the eight forward sums and the std / ctr gradient columns are equal bit for bit
+    (the distance gradients live in different spaces: softmax Jacobian against ReLU gate)."""
+    from tests.loss_ref64 import LEGAL_FLAGS
+    from ubteacher import hip
+    g = torch.Generator().manual_seed(41)
+    P, LOGIT = 8, 60.0
+    jb = torch.randint(1, 17, (P, 4), generator=g)
+    jb[0] = torch.tensor([1, 16, 8, 3])
+    for j in range(1, 17):                        # the kernel's fp32 Integral of such a row, step by step
+        e = np.exp(np.where(np.arange(17) == j, np.float32(0), np.float32(-LOGIT)).astype(np.float32)).astype(np.float32)
+        s, acc = np.float32(0), np.float32(0)
+        for q in range(17):
+            s = np.float32(s + e[q])
+        for q in range(17):
+            acc = np.float32(acc + np.float32(e[q] / s) * np.float32(q - j))
+        assert np.float32(np.float32(j) + acc) == np.float32(j) and float(j) + float(acc) == float(j)
+    t = jb.float() + torch.randn((P, 4), generator=g) * 1.5
+    t = t.abs() + 0.05
+    t[1] = jb[1].float()                          # ties d == t on a whole row
+    t[2, 0] = jb[2, 0].float() + 1.0              # the smooth-L1 switch
+    sc = torch.randn((P, 5), generator=g)         # std 4 | ctr 1
+    bv = torch.randn((P, 4), generator=g) * 2
+    lab = torch.randint(0, 80, (P,), generator=g, dtype=torch.int32)
+    disc = torch.zeros((P, 80))
+    disc[:, :68] = torch.nn.functional.one_hot(jb, 17).float().view(P, 68) * LOGIT
+    disc[:, 68:73] = sc
+    cont = torch.zeros((P, 16))
+    cont[:, :4] = jb.float()
+    cont[:, 4:9] = sc
+    coef = torch.tensor([0.7, 1.3, 0.9, 1.1]).to(DEV)
+    nsel = []
+    for flags in LEGAL_FLAGS:
+        for bvars in (None, bv.to(DEV)):
+            ad = (lab.to(DEV), disc.to(DEV), t.to(DEV), bvars, 80, 16, 0.1, 0.5)
+            ac = (lab.to(DEV), cont.to(DEV), t.to(DEV), bvars, 80, 0.1, 0.5)
+            sd, scn = hip.fcos_loc_terms_fwd(*ad, flags=flags).cpu(), hip.fcos_loc_terms_cont_fwd(*ac, flags=flags).cpu()
+            assert torch.equal(sd, scn) and float(sd[0]) == P, (flags, sd, scn)
+            gd, gc = hip.fcos_loc_terms_bwd(*ad, coef, flags=flags).cpu(), hip.fcos_loc_terms_cont_bwd(*ac, coef, flags=flags).cpu()
+            assert torch.equal(gd[:, 68:73], gc[:, 4:9]), flags
+            assert bool(torch.isfinite(gd).all()) and float(gc[:, 4:9].abs().sum()) > 0
+            if bvars is not None:
+                nsel.append(float(sd[5]))
+    assert 0 < nsel[0] < 4 * P                    # some boundaries selected as "teacher better", some not

@@ -261,22 +261,34 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // Fused positive-location terms (fcos_outputs.py:340-416 supervised; :514-590 pseudo;
 // Integral :44-77; compute_ctrness_targets :80-88; compute_iou_targets :91-129;
-// IOULoss giou layers/iou_loss.py:26-76; NLLoss layers/kl_loss.py:69-105).
-// box rows: [reg logits 4*(R+1) | std 4 | ctr 1 | pad], row stride BS floats.
+// IOULoss giou layers/iou_loss.py:26-76; NLLoss layers/kl_loss.py:69-105) and the box decode, for both regression heads.
+// box rows, row stride BS floats:
+//   discrete   (MODEL.FCOS.REG_DISCRETE True):  [reg logits 4*(R+1) | std 4 | ctr 1 | pad]; d_b = Integral of the b-th softmax
+//   continuous (REG_DISCRETE False: the plain FCOS head, fcos/fcos.py:294-297,363-364; the scalar distances go straight into the losses,
+//               fcos_outputs.py:349-350,545-546, and into the decode, :1107-1108):  [ltrb 4 | std 4 | ctr 1 | pad].  The buffer holds the
+//               Scale layer's output BEFORE the ReLU: d_b = max(row[b], 0) is taken on read, and the backward writes 0 where the stored
+//               value is <= 0 (torch's convention at exactly 0, and at -0.0) - the conv epilogue and the Scale kernels are the same.
+// The heads differ in how d comes out of a row, how a gradient of d goes back into it and where std / ctr sit; every formula on
+// (d, t, std, ctr) is written once below (giou_ltrb, teacher_better, loc_row_fwd, loc_row_bwd, decode_empty_slot, decode_live_slot).
 // Sums produced (LT_NSUM columns):
 //   0 n_pos  1 sum ctr_t  2 sum bce(ctr)  3 sum (1-giou)*ctr_t  4 sum nll_i*iou_i
 //   5 n_sel  6 sum_sel |d - t|
 #define LT_NSUM 8
-struct LocTerms {
-  float d[4];      // Integral ltrb
-  float ctr_t, iou, giou_l, nll;
-};
+#define CT_STD 4    // columns of a continuous row
+#define CT_CTR 8
+#define CT_COLS 9
+// flags of the positive-location kernels (config-reachable variants; every shipped YAML uses 0)
+#define LT_QUALITY_IOU 1  // MODEL.FCOS.QUALITY_EST "iou": the centerness target is IoU(pred.detach, target) (fcos_outputs.py:355-359)
+#define LT_KLLOSS 2       // MODEL.FCOS.KL_LOSS_TYPE "klloss": column 4 = sum_b exp(-std_b)*smoothL1_1(d_b - t_b) + std_b/2 (kl_loss.py:11-66)
+#define LT_LOC_SHIFT 2    // bits 2-3: loc_type
+#define LT_KL_WCTR 16     // with LT_KLLOSS: each positive's KL term is weighted by its centerness / quality target (MODEL.FCOS.LOC_FUN_ALL
+                          // "weight_ctr_sum" / "weight_ctr_mean", kl_loss.py:52-58) instead of 1 ("sum" / "mean")
 
 // d = sum_j p_j j taken around the mode: d = jm + delta, delta = sum_j p_j (j - jm).  On a sharply peaked row (delta ~ 1e-4) the plain sum
 // carries u d of rounding, and the backward's (j - d) at the mode - and (t - d) next to it - lost up to 9e-2 of their value to it
 // (tests/test_loss_kernels_fp64_gpu.py); the backward kernel does the same in double.
 template <int R1>
-__device__ __forceinline__ void integral4(const float* __restrict__ z, float* d, float (*prob)[R1]) {
+__device__ __forceinline__ void integral4(const float* __restrict__ z, float* d) {
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     float m = -INFINITY;
@@ -291,103 +303,167 @@ __device__ __forceinline__ void integral4(const float* __restrict__ z, float* d,
     for (int j = 0; j < R1; ++j) { e[j] = expf(z[b * R1 + j] - m); s += e[j]; }
     float acc = 0.f;
 #pragma unroll
-    for (int j = 0; j < R1; ++j) {
-      const float pj = e[j] / s;
-      if (prob) prob[b][j] = pj;
-      acc += pj * (float)(j - jm);
-    }
+    for (int j = 0; j < R1; ++j) acc += (e[j] / s) * (float)(j - jm);
     d[b] = (float)jm + acc;
   }
 }
 
-__device__ __forceinline__ float min_grad(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }  // d min(a,b)/da
-__device__ __forceinline__ float max_grad(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
+// the float instantiations call the f-suffixed functions, as the float code always did
+__device__ __forceinline__ float t_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double t_min(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float t_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double t_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float t_log(float a) { return logf(a); }
+__device__ __forceinline__ double t_log(double a) { return log(a); }
+__device__ __forceinline__ float t_sqrt(float a) { return sqrtf(a); }
+__device__ __forceinline__ double t_sqrt(double a) { return sqrt(a); }
+template <typename T> __device__ __forceinline__ T min_grad(T a, T b) { return a < b ? T(1) : (a == b ? T(0.5) : T(0)); }  // d min(a,b)/da
+template <typename T> __device__ __forceinline__ T max_grad(T a, T b) { return a > b ? T(1) : (a == b ? T(0.5) : T(0)); }
 
-// giou loss (1 - giou) on ltrb with +1 smoothing on the IoU only; optionally its gradient wrt d
+// giou loss (1 - giou) on ltrb with +1 smoothing on the IoU only; optionally its gradient wrt d.  T = float in the forward and decode
+// kernels, double in the backward kernels.
 // loc_type (MODEL.FCOS.LOC_LOSS_TYPE, iou_loss.py:64-69): 0 giou (1 - giou), 1 iou (-log iou), 2 linear_iou (1 - iou)
-__device__ __forceinline__ float giou_ltrb(const float* d, const float* t, float* iou_out, float* grad, int loc_type = 0) {
-  const float ta = (t[0] + t[2]) * (t[1] + t[3]);
-  const float pw = d[0] + d[2], ph = d[1] + d[3];
-  const float pa = pw * ph;
-  const float wi = fminf(d[0], t[0]) + fminf(d[2], t[2]);
-  const float hi = fminf(d[3], t[3]) + fminf(d[1], t[1]);
-  const float gw = fmaxf(d[0], t[0]) + fmaxf(d[2], t[2]);
-  const float gh = fmaxf(d[3], t[3]) + fmaxf(d[1], t[1]);
-  const float ac = gw * gh;
-  const float I = wi * hi;
-  const float U = ta + pa - I;
-  const float iou = (I + 1.f) / (U + 1.f);
-  const float giou = iou - (ac - U) / ac;
+template <typename T>
+__device__ __forceinline__ T giou_ltrb(const T* d, const T* t, T* iou_out, T* grad, int loc_type) {
+  const T ta = (t[0] + t[2]) * (t[1] + t[3]);
+  const T pw = d[0] + d[2], ph = d[1] + d[3];
+  const T pa = pw * ph;
+  const T wi = t_min(d[0], t[0]) + t_min(d[2], t[2]);
+  const T hi = t_min(d[3], t[3]) + t_min(d[1], t[1]);
+  const T gw = t_max(d[0], t[0]) + t_max(d[2], t[2]);
+  const T gh = t_max(d[3], t[3]) + t_max(d[1], t[1]);
+  const T ac = gw * gh;
+  const T I = wi * hi;
+  const T U = ta + pa - I;
+  const T iou = (I + T(1)) / (U + T(1));
+  const T giou = iou - (ac - U) / ac;
   if (iou_out) *iou_out = iou;
   if (grad) {
     // index 0: left, 1: top, 2: right, 3: bottom
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const bool horiz = (b == 0 || b == 2);
-      const float dpa = horiz ? ph : pw;
-      const float dI = horiz ? min_grad(d[b], t[b]) * hi : min_grad(d[b], t[b]) * wi;
-      const float dac = horiz ? max_grad(d[b], t[b]) * gh : max_grad(d[b], t[b]) * gw;
-      const float dU = dpa - dI;
-      const float diou = (dI * (U + 1.f) - (I + 1.f) * dU) / ((U + 1.f) * (U + 1.f));
+      const T dpa = horiz ? ph : pw;
+      const T dI = horiz ? min_grad(d[b], t[b]) * hi : min_grad(d[b], t[b]) * wi;
+      const T dac = horiz ? max_grad(d[b], t[b]) * gh : max_grad(d[b], t[b]) * gw;
+      const T dU = dpa - dI;
+      const T diou = (dI * (U + T(1)) - (I + T(1)) * dU) / ((U + T(1)) * (U + T(1)));
       // giou = iou - 1 + U/ac
-      const float dgiou = diou + dU / ac - U * dac / (ac * ac);
+      const T dgiou = diou + dU / ac - U * dac / (ac * ac);
       // three plain assignments, not one nested ?: - hipcc (ROCm 7.2) mis-folded `t == 1 ? -diou / iou : -diou` into the un-divided
       // numerator for t == 2 (caught by tests/test_fcos_kernels_gpu.py::test_supervised_loss_variants_vs_reference_golden[loclinear])
-      float g = -diou;
+      T g = -diou;
       if (loc_type == 1) g = g / iou;
       if (loc_type == 0) g = -dgiou;
       grad[b] = g;
     }
   }
-  return loc_type == 0 ? 1.f - giou : (loc_type == 1 ? -logf(iou) : 1.f - iou);
+  return loc_type == 0 ? T(1) - giou : (loc_type == 1 ? -t_log(iou) : T(1) - iou);
 }
 
-// the same in double, for the backward kernel
-__device__ __forceinline__ double min_grad_f64(double a, double b) { return a < b ? 1.0 : (a == b ? 0.5 : 0.0); }
-__device__ __forceinline__ double max_grad_f64(double a, double b) { return a > b ? 1.0 : (a == b ? 0.5 : 0.0); }
-__device__ __forceinline__ double giou_ltrb_f64(const double* d, const double* t, double* iou_out, double* grad, int loc_type) {
-  const double ta = (t[0] + t[2]) * (t[1] + t[3]);
-  const double pw = d[0] + d[2], ph = d[1] + d[3];
-  const double pa = pw * ph;
-  const double wi = fmin(d[0], t[0]) + fmin(d[2], t[2]);
-  const double hi = fmin(d[3], t[3]) + fmin(d[1], t[1]);
-  const double gw = fmax(d[0], t[0]) + fmax(d[2], t[2]);
-  const double gh = fmax(d[3], t[3]) + fmax(d[1], t[1]);
-  const double ac = gw * gh;
-  const double I = wi * hi;
-  const double U = ta + pa - I;
-  const double iou = (I + 1.0) / (U + 1.0);
-  const double giou = iou - (ac - U) / ac;
-  if (iou_out) *iou_out = iou;
-  if (grad) {
-    // index 0: left, 1: top, 2: right, 3: bottom
+// centerness target sqrt(min(l, r) / max(l, r) * min(t, b) / max(t, b)) of the regression target
+template <typename T>
+__device__ __forceinline__ T ctrness_target(const T* t) {
+  return t_sqrt((t_min(t[0], t[2]) / t_max(t[0], t[2])) * (t_min(t[1], t[3]) / t_max(t[1], t[3])));
+}
+
+// "teacher better" selection of one boundary of a pseudo-labelled positive (fcos_outputs.py:556-583): the teacher's certainty
+// 1 - sigmoid(bvar) passes ts_cert and beats the student's 1 - sigmoid(std logit) by more than ts_better (both strict).  fp32 in the
+// forward AND in the double backward: n_sel, the L1 sum and the L1 gradient must count the same boundaries, bit for bit.
+__device__ __forceinline__ bool teacher_better(float std_logit, float bvar, float ts_better, float ts_cert) {
+  const float cs = 1.f - 1.f / (1.f + expf(-std_logit));
+  const float ct = 1.f - 1.f / (1.f + expf(-bvar));
+  return ct > ts_cert && ct > cs + ts_better;
+}
+
+// One positive row of the forward, for both heads: adds the row's terms to acc[LT_NSUM].  d: the head's four distances, t: the targets,
+// sp: the four std logits, c: the centerness logit, bv: the row's teacher std (bvars), or nullptr.
+__device__ __forceinline__ void loc_row_fwd(const float (&d)[4], const float (&t)[4], const float* sp, float c, const float* bv,
+                                            float ts_better, float ts_cert, int flags, float (&acc)[LT_NSUM]) {
+  float ctr_t = ctrness_target<float>(t);
+  float iou;
+  const float gl = giou_ltrb<float>(d, t, &iou, nullptr, (flags >> LT_LOC_SHIFT) & 3);
+  if (flags & LT_QUALITY_IOU) ctr_t = iou;
+  float nll = 0.f;
+  if (flags & LT_KLLOSS) {
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const bool horiz = (b == 0 || b == 2);
-      const double dpa = horiz ? ph : pw;
-      const double dI = horiz ? min_grad_f64(d[b], t[b]) * hi : min_grad_f64(d[b], t[b]) * wi;
-      const double dac = horiz ? max_grad_f64(d[b], t[b]) * gh : max_grad_f64(d[b], t[b]) * gw;
-      const double dU = dpa - dI;
-      const double diou = (dI * (U + 1.0) - (I + 1.0) * dU) / ((U + 1.0) * (U + 1.0));
-      // giou = iou - 1 + U/ac
-      const double dgiou = diou + dU / ac - U * dac / (ac * ac);
-      // three plain assignments, not one nested ?: - hipcc (ROCm 7.2) mis-folded `t == 1 ? -diou / iou : -diou` into the un-divided
-      // numerator for t == 2 (caught by tests/test_fcos_kernels_gpu.py::test_supervised_loss_variants_vs_reference_golden[loclinear])
-      double g = -diou;
-      if (loc_type == 1) g = g / iou;
-      if (loc_type == 0) g = -dgiou;
-      grad[b] = g;
+      const float n = fabsf(d[b] - t[b]);
+      nll += expf(-sp[b]) * (n < 1.f ? 0.5f * n * n : n - 0.5f) + 0.5f * sp[b];
     }
+    iou = (flags & LT_KL_WCTR) ? ctr_t : 1.f;  // KLLoss ignores the IoU weight; LOC_FUN_ALL weight_ctr_*: the centerness target
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float sg = 1.f / (1.f + expf(-sp[b]));
+      const float sq = sg * sg;
+      const float df = t[b] - d[b];
+      nll += (df * df) / (2.f * sq) + 0.5f * logf(sq);
+    }
+    nll += 2.f * logf(2.f * 3.14159265358979323846f);
   }
-  return loc_type == 0 ? 1.0 - giou : (loc_type == 1 ? -log(iou) : 1.0 - iou);
+  const float bce = fmaxf(c, 0.f) - c * ctr_t + log1pf(expf(-fabsf(c)));
+  acc[0] += 1.f;
+  acc[1] += ctr_t;
+  acc[2] += bce;
+  acc[3] += gl * ctr_t;
+  acc[4] += nll * iou;
+  if (bv) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (teacher_better(sp[b], bv[b], ts_better, ts_cert)) {
+        acc[5] += 1.f;
+        acc[6] += fabsf(d[b] - t[b]);
+      }
+  }
 }
 
-// flags of the positive-location kernels (config-reachable variants; every shipped YAML uses 0)
-#define LT_QUALITY_IOU 1  // MODEL.FCOS.QUALITY_EST "iou": the centerness target is IoU(pred.detach, target) (fcos_outputs.py:355-359)
-#define LT_KLLOSS 2       // MODEL.FCOS.KL_LOSS_TYPE "klloss": column 4 = sum_b exp(-std_b)*smoothL1_1(d_b - t_b) + std_b/2 (kl_loss.py:11-66)
-#define LT_LOC_SHIFT 2    // bits 2-3: loc_type
-#define LT_KL_WCTR 16     // with LT_KLLOSS: each positive's KL term is weighted by its centerness / quality target (MODEL.FCOS.LOC_FUN_ALL
-                          // "weight_ctr_sum" / "weight_ctr_mean", kl_loss.py:52-58) instead of 1 ("sum" / "mean")
+// One positive row of the backward, for both heads, in DOUBLE (the callers round once per output element).  Only positive locations get
+// here (hundreds to a few thousand rows per step), so the fp64 rate does not show; in fp32 the softmax - Integral - (t - d) - IoU quotient
+// chain left errors of 1e-5 .. 9e-2 relative on sharply peaked rows and of 30 - 70 roundings next to d ~ t, against fp64 autograd
+// (tests/test_loss_kernels_fp64_gpu.py).
+//   df = t - d as the CALLER takes it: the discrete head forms it around the mode with a tie kept a tie, the continuous one subtracts.
+//   c_*: the fully normalised upstream factors d(total)/d(sum bce), d/d(sum giou*ctr), d/d(sum nll*iou), d/d(sum_sel |d-t|)
+//   out: dd = d total / d d_b, ds = d total / d std logit_b; returns d total / d centerness logit.
+// The sign of d - t (KL term and L1 term) is read off df.  Both heads' df have the sign of t - d exactly: the continuous one is a single
+// IEEE subtraction, which is 0 only for t == d; the discrete one is 0 by construction when d == t and otherwise (t - jm) - dl, where
+// t - jm (a float minus an integer <= 16) is exact in double unless jm >= 1 and |t| < 2^-24 - and then d >= jm / 17 (the mode holds at
+// least 1/17 of the mass) is far from t - and t, a float, lies on the double grid d = fl(jm + dl) is rounded to, so that rounding cannot
+// carry jm + dl across t.  The discrete kernel used to compare d with t for the L1 term and the continuous one to test df: the same.
+__device__ __forceinline__ float loc_row_bwd(const double (&d)[4], const double (&t)[4], const double (&df)[4], const float* sp, float c,
+                                             const float* bv, float c_bce, float c_giou, float c_nll, float c_l1, float ts_better,
+                                             float ts_cert, int flags, double (&dd)[4], double (&ds)[4]) {
+  double ctr_t = ctrness_target<double>(t);
+  double iou, gg[4];
+  giou_ltrb<double>(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
+  if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const double sgn = df[b] < 0.0 ? 1.0 : (df[b] > 0.0 ? -1.0 : 0.0);   // sign(d - t)
+    if (flags & LT_KLLOSS) {
+      // kl_b = exp(-s) * sl1(n) + s/2, n = |d - t|: d/dd = exp(-s) * min(n, 1) * sign(d - t); d/ds = 1/2 - exp(-s) * sl1(n)
+      const double n = fabs(df[b]), es = exp(-(double)sp[b]);
+      const double wk = (flags & LT_KL_WCTR) ? ctr_t : 1.0;   // a detached target
+      dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * wk * es * fmin(n, 1.0) * sgn;
+      ds[b] = (double)c_nll * wk * (0.5 - es * (n < 1.0 ? 0.5 * n * n : n - 0.5));
+    } else {
+      // nll_b = df^2/(2 sg^2) + log(sg);  d/dd = -df/sg^2 ; d/ds = (1-sg) * (1 - df^2/sg^2)
+      const double sg = 1.0 / (1.0 + exp(-(double)sp[b]));
+      dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * iou * (-df[b] / (sg * sg));
+      ds[b] = (double)c_nll * iou * (1.0 - sg) * (1.0 - (df[b] * df[b]) / (sg * sg));
+    }
+    if (bv && teacher_better(sp[b], bv[b], ts_better, ts_cert)) dd[b] += (double)c_l1 * sgn;
+  }
+  return (float)((double)c_bce * (1.0 / (1.0 + exp(-(double)c)) - ctr_t));
+}
+
+// coef of the backward kernels: device floats [c_bce, c_giou, c_nll, c_l1], or with coef8 d total / d sums[8] of the forward (the factors
+// sit at [2], [3], [4], [6]); gscale: optional further device factor
+struct LocCoef { float bce, giou, nll, l1; };
+__device__ __forceinline__ LocCoef load_loc_coef(const float* coef, int coef8, const float* gscale) {
+  const float gs = gscale ? gscale[0] : 1.f;
+  return {coef[coef8 ? 2 : 0] * gs, coef[coef8 ? 3 : 1] * gs, coef[coef8 ? 4 : 2] * gs, coef[coef8 ? 6 : 3] * gs};
+}
 
 template <int R1>
 __global__ __launch_bounds__(128) void fcos_loc_fwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
@@ -405,50 +481,10 @@ __global__ __launch_bounds__(128) void fcos_loc_fwd_kernel(const int* __restrict
     if (lab < 0 || lab == num_classes) continue;
     const float* row = box + i * BS;
     float d[4], t[4];
-    integral4<R1>(row, d, (float(*)[R1]) nullptr);
+    integral4<R1>(row, d);
 #pragma unroll
     for (int b = 0; b < 4; ++b) t[b] = reg_targets[i * 4 + b];
-    float ctr_t = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
-    float iou;
-    const float gl = giou_ltrb(d, t, &iou, nullptr, (flags >> LT_LOC_SHIFT) & 3);
-    if (flags & LT_QUALITY_IOU) ctr_t = iou;
-    float nll = 0.f;
-    const float* sp = row + 4 * R1;
-    if (flags & LT_KLLOSS) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float n = fabsf(d[b] - t[b]);
-        nll += expf(-sp[b]) * (n < 1.f ? 0.5f * n * n : n - 0.5f) + 0.5f * sp[b];
-      }
-      iou = (flags & LT_KL_WCTR) ? ctr_t : 1.f;  // KLLoss ignores the IoU weight; LOC_FUN_ALL weight_ctr_*: the centerness target
-    } else {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float sg = 1.f / (1.f + expf(-sp[b]));
-        const float sq = sg * sg;
-        const float df = t[b] - d[b];
-        nll += (df * df) / (2.f * sq) + 0.5f * logf(sq);
-      }
-      nll += 2.f * logf(2.f * 3.14159265358979323846f);
-    }
-    const float c = row[4 * R1 + 4];
-    const float bce = fmaxf(c, 0.f) - c * ctr_t + log1pf(expf(-fabsf(c)));
-    acc[0] += 1.f;
-    acc[1] += ctr_t;
-    acc[2] += bce;
-    acc[3] += gl * ctr_t;
-    acc[4] += nll * iou;
-    if (bvars) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
-        const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
-        if (ct > ts_cert && ct > cs + ts_better) {
-          acc[5] += 1.f;
-          acc[6] += fabsf(d[b] - t[b]);
-        }
-      }
-    }
+    loc_row_fwd(d, t, row + 4 * R1, row[4 * R1 + 4], bvars ? bvars + i * 4 : nullptr, ts_better, ts_cert, flags, acc);
   }
 #pragma unroll
   for (int k = 0; k < LT_NSUM; ++k) {
@@ -457,22 +493,17 @@ __global__ __launch_bounds__(128) void fcos_loc_fwd_kernel(const int* __restrict
   }
 }
 
-// coef: device floats [c_bce, c_giou, c_nll, c_l1]: the fully normalised upstream factors
-//   d(total)/d(sum bce), d/d(sum giou*ctr), d/d(sum nll*iou), d/d(sum_sel |d-t|)
-// writes the whole gradient row (zeros for background / pad channels).
+// coef / coef8 / gscale: see load_loc_coef.  Writes the whole gradient row (zeros for background / pad channels); accumulate: only the
+// positive rows are touched, their gradient ADDED to dbox (see focal_bwd_kernel).
 template <int R1>
 __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
                                                          const float* __restrict__ reg_targets, const float* __restrict__ bvars,
                                                          size_t P, int num_classes, float ts_better, float ts_cert, int flags,
                                                          const float* __restrict__ coef, float* __restrict__ dbox,
                                                          const float* __restrict__ gscale, int coef8, int accumulate) {
-  // coef8: coef = d total / d sums[8] of the forward (the factors sit at [2], [3], [4], [6]); gscale: optional further device factor;
-  // accumulate: only the positive rows are touched, their gradient ADDED to dbox (see focal_bwd_kernel)
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const float gs = gscale ? gscale[0] : 1.f;
-  const float c_bce = coef[coef8 ? 2 : 0] * gs, c_giou = coef[coef8 ? 3 : 1] * gs, c_nll = coef[coef8 ? 4 : 2] * gs,
-              c_l1 = coef[coef8 ? 6 : 3] * gs;
+  const LocCoef cf = load_loc_coef(coef, coef8, gscale);
   for (; i < P; i += stride) {
     const int lab = labels[i];
     float* grow = dbox + i * BS;
@@ -482,12 +513,8 @@ __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict
       continue;
     }
     const float* row = box + i * BS;
-    // The row's arithmetic is done in DOUBLE and rounded once per output element.  Only positive locations get here (hundreds to a
-    // few thousand rows per step), so the fp64 rate does not show; in fp32 the softmax - Integral - (t - d) - IoU quotient chain
-    // left errors of 1e-5 .. 9e-2 relative on sharply peaked rows and of 30 - 70 roundings next to d ~ t, against fp64 autograd
-    // (tests/test_loss_kernels_fp64_gpu.py).  The Integral is taken around the mode, d = jm + sum_j p_j (j - jm), so that (j - d) at
-    // the mode keeps its value where even the fp64 plain sum cancels to 0.  The teacher-better SELECTION stays in fp32, bit for bit
-    // the forward kernel's (n_sel and the L1 sum must count the same boundaries).
+    // The Integral is taken around the mode in double, d = jm + dl, dl = sum_j p_j (j - jm), so that (j - d) at the mode keeps its value
+    // where even the fp64 plain sum cancels to 0.
     double d[4], t[4], dl[4], prob[4][R1];
     int jm[4];
 #pragma unroll
@@ -508,36 +535,11 @@ __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict
       jm[b] = q; dl[b] = acc; d[b] = (double)q + acc;
       t[b] = (double)reg_targets[i * 4 + b];
     }
-    double ctr_t = sqrt((fmin(t[0], t[2]) / fmax(t[0], t[2])) * (fmin(t[1], t[3]) / fmax(t[1], t[3])));
-    double iou, gg[4];
-    giou_ltrb_f64(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
-    if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
-    const float* sp = row + 4 * R1;
-    double dd[4], ds[4];
+    double df[4], dd[4], ds[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const double sg = 1.0 / (1.0 + exp(-(double)sp[b]));
-      const double df = d[b] == t[b] ? 0.0 : (t[b] - (double)jm[b]) - dl[b];   // a tie stays a tie
-      if (flags & LT_KLLOSS) {
-        // kl_b = exp(-s) * sl1(n) + s/2, n = |d - t|: d/dd = exp(-s) * min(n, 1) * sign(d - t); d/ds = 1/2 - exp(-s) * sl1(n)
-        const double n = fabs(df), es = exp(-(double)sp[b]);
-        const double sgn = df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0);
-        const double wk = (flags & LT_KL_WCTR) ? ctr_t : 1.0;   // a detached target
-        dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * wk * es * fmin(n, 1.0) * sgn;
-        ds[b] = (double)c_nll * wk * (0.5 - es * (n < 1.0 ? 0.5 * n * n : n - 0.5));
-      } else {
-        // nll_b = df^2/(2 sg^2) + log(sg);  d/dd = -df/sg^2 ; d/ds = (1-sg) * (1 - df^2/sg^2)
-        dd[b] = (double)c_giou * ctr_t * gg[b] + (double)c_nll * iou * (-df / (sg * sg));
-        ds[b] = (double)c_nll * iou * (1.0 - sg) * (1.0 - (df * df) / (sg * sg));
-      }
-      if (bvars) {
-        const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
-        const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
-        if (ct > ts_cert && ct > cs + ts_better) dd[b] += (double)c_l1 * (d[b] > t[b] ? 1.0 : (d[b] < t[b] ? -1.0 : 0.0));
-      }
-    }
-    const double c = (double)row[4 * R1 + 4];
-    const float dctr = (float)((double)c_bce * (1.0 / (1.0 + exp(-c)) - ctr_t));
+    for (int b = 0; b < 4; ++b) df[b] = d[b] == t[b] ? 0.0 : (t[b] - (double)jm[b]) - dl[b];   // a tie stays a tie
+    const float dctr = loc_row_bwd(d, t, df, row + 4 * R1, row[4 * R1 + 4], bvars ? bvars + i * 4 : nullptr, cf.bce, cf.giou, cf.nll, cf.l1,
+                                   ts_better, ts_cert, flags, dd, ds);
     if (accumulate) {
 #pragma unroll
       for (int b = 0; b < 4; ++b)
@@ -557,6 +559,75 @@ __global__ __launch_bounds__(128) void fcos_loc_bwd_kernel(const int* __restrict
     grow[4 * R1 + 4] = dctr;
     for (int k = 4 * R1 + 5; k < BS; ++k) grow[k] = 0.f;
   }
+}
+
+// The continuous head's forward: d_b = max(row[b], 0)
+__global__ __launch_bounds__(128) void fcos_loc_cont_fwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
+                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
+                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
+                                                              float* __restrict__ partial) {
+  __shared__ float red[2];
+  float acc[LT_NSUM];
+#pragma unroll
+  for (int k = 0; k < LT_NSUM; ++k) acc[k] = 0.f;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < P; i += stride) {
+    const int lab = labels[i];
+    if (lab < 0 || lab == num_classes) continue;
+    const float* row = box + i * BS;
+    float d[4], t[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { d[b] = fmaxf(row[b], 0.f); t[b] = reg_targets[i * 4 + b]; }
+    loc_row_fwd(d, t, row + CT_STD, row[CT_CTR], bvars ? bvars + i * 4 : nullptr, ts_better, ts_cert, flags, acc);
+  }
+#pragma unroll
+  for (int k = 0; k < LT_NSUM; ++k) {
+    const float s = block_reduce_sum(acc[k], red);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * LT_NSUM + k] = s;
+  }
+}
+
+// coef / coef8 / gscale / accumulate: as fcos_loc_bwd_kernel.  One thread per row; the gradient of d_b goes back through the ReLU gate.
+__global__ __launch_bounds__(128) void fcos_loc_cont_bwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
+                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
+                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
+                                                              const float* __restrict__ coef, float* __restrict__ dbox,
+                                                              const float* __restrict__ gscale, int coef8, int accumulate) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const LocCoef cf = load_loc_coef(coef, coef8, gscale);
+  const int lab = labels[i];
+  float* grow = dbox + i * BS;
+  if (lab < 0 || lab == num_classes) {
+    if (!accumulate)
+      for (int k = 0; k < BS; ++k) grow[k] = 0.f;
+    return;
+  }
+  const float* row = box + i * BS;
+  double d[4], t[4], df[4], dd[4], ds[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    d[b] = (double)fmaxf(row[b], 0.f);
+    t[b] = (double)reg_targets[i * 4 + b];
+    df[b] = t[b] - d[b];
+  }
+  float gout[CT_COLS];
+  gout[CT_CTR] = loc_row_bwd(d, t, df, row + CT_STD, row[CT_CTR], bvars ? bvars + i * 4 : nullptr, cf.bce, cf.giou, cf.nll, cf.l1, ts_better,
+                             ts_cert, flags, dd, ds);
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    gout[b] = row[b] > 0.f ? (float)dd[b] : 0.f;   // ReLU: no gradient at or below 0
+    gout[CT_STD + b] = (float)ds[b];
+  }
+  if (accumulate) {
+#pragma unroll
+    for (int k = 0; k < CT_COLS; ++k) grow[k] += gout[k];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < CT_COLS; ++k) grow[k] = gout[k];
+  for (int k = CT_COLS; k < BS; ++k) grow[k] = 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -604,6 +675,55 @@ __global__ __launch_bounds__(256) void fcos_rank_keys_kernel(const float* __rest
 // in : topkeys [N][K] (from the keys above, sorted or not; -1 = empty slot)
 // out (slot s = level_slot0 + k of image n, MAXC slots per image):
 //   boxes[4] scores cls(int) loc[2] ctr cls_conf std[4] level valid
+struct DecodeOut {
+  float *boxes, *scores;
+  int* cls;
+  float *loc, *ctr, *conf, *std;
+  int* level;
+  unsigned char* valid;
+};
+
+__device__ __forceinline__ void decode_empty_slot(const DecodeOut& o, size_t s, int level) {
+  o.valid[s] = 0;
+  o.scores[s] = -1.f;
+  o.cls[s] = 0;
+  o.level[s] = level;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { o.boxes[s * 4 + e] = 0.f; o.std[s * 4 + e] = 0.f; }
+  o.loc[s * 2] = 0.f; o.loc[s * 2 + 1] = 0.f; o.ctr[s] = 0.f; o.conf[s] = 0.f;
+}
+
+// The flat index into this level's [HW][C] that a key carries, and the empty-slot test: -1, or a flat index outside HW * C (such a key cannot
+// come from utv2_fcos_rank_keys; it is never followed).  The test is kept in this form: as `key >= 0 && flat < HW * C` on the live side hipcc
+// (ROCm 7.2) held 122 VGPRs in fcos_decode_kernel<17> instead of 84.
+__device__ __forceinline__ unsigned key_flat(long long key) { return 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFll); }
+__device__ __forceinline__ bool key_empty(long long key, int HW, int C) {
+  return key < 0 || (unsigned long long)key_flat(key) >= (unsigned long long)HW * (unsigned long long)C;
+}
+
+// a live slot: d = the head's four distances of location hw, sp / ctr_logit = its std and centerness logits, cls_logit -> logit of class c
+__device__ __forceinline__ void decode_live_slot(const DecodeOut& o, size_t s, const float (&d)[4], const float* sp, float ctr_logit,
+                                                 const float* cls_logit, float rank, int hw, int c, int Wl, int stride, int level, int method) {
+  const int y = hw / Wl, x = hw - y * Wl;
+  const float lx = (float)(x * stride) + (float)(stride / 2), ly = (float)(y * stride) + (float)(stride / 2);
+  const float fs = (float)stride;
+  o.boxes[s * 4 + 0] = lx - d[0] * fs;
+  o.boxes[s * 4 + 1] = ly - d[1] * fs;
+  o.boxes[s * 4 + 2] = lx + d[2] * fs;
+  o.boxes[s * 4 + 3] = ly + d[3] * fs;
+  const int crit = method & 3;
+  o.scores[s] = (crit == 1 || crit == 3) ? sqrtf(rank) : rank;
+  o.cls[s] = c;
+  o.loc[s * 2] = lx; o.loc[s * 2 + 1] = ly;
+  o.ctr[s] = 1.f / (1.f + expf(-ctr_logit));
+  // THRESH_WITH_CTR: cls_confs is taken after the centerness product (:1175-1179) - the ranking score the key carries
+  o.conf[s] = (method & FCOS_THRESH_WITH_CTR) ? rank : 1.f / (1.f + expf(-cls_logit[0]));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o.std[s * 4 + e] = sp[e];
+  o.level[s] = level;
+  o.valid[s] = 1;
+}
+
 template <int R1>
 __global__ __launch_bounds__(128) void fcos_decode_kernel(const long long* __restrict__ topkeys, int K, const float* __restrict__ logits,
                                                         const float* __restrict__ box, int BS, int HW, int Wl, int C, int stride,
@@ -614,188 +734,23 @@ __global__ __launch_bounds__(128) void fcos_decode_kernel(const long long* __res
   const int n = blockIdx.y;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
+  const DecodeOut o = {oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel, ovalid};
   const size_t s = (size_t)n * MAXC + slot0 + k;
   const long long key = topkeys[(size_t)n * K + k];
-  if (key < 0) {
-    ovalid[s] = 0;
-    oscores[s] = -1.f;
-    ocls[s] = 0;
-    olevel[s] = level;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { oboxes[s * 4 + e] = 0.f; ostd[s * 4 + e] = 0.f; }
-    oloc[s * 2] = 0.f; oloc[s * 2 + 1] = 0.f; octr[s] = 0.f; oconf[s] = 0.f;
+  if (key_empty(key, HW, C)) {
+    decode_empty_slot(o, s, level);
     return;
   }
-  const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFll);
   const float rank = __uint_as_float((unsigned)(key >> 32));
-  const int hw = flat / C, c = flat - hw * C;
+  const int hw = key_flat(key) / C, c = key_flat(key) - hw * C;
   const size_t row = (size_t)n * HW + hw;
   const float* br = box + row * BS;
   float d[4];
-  integral4<R1>(br, d, (float(*)[R1]) nullptr);
-  const int y = hw / Wl, x = hw - y * Wl;
-  const float lx = (float)(x * stride) + (float)(stride / 2), ly = (float)(y * stride) + (float)(stride / 2);
-  const float fs = (float)stride;
-  oboxes[s * 4 + 0] = lx - d[0] * fs;
-  oboxes[s * 4 + 1] = ly - d[1] * fs;
-  oboxes[s * 4 + 2] = lx + d[2] * fs;
-  oboxes[s * 4 + 3] = ly + d[3] * fs;
-  const int crit = method & 3;
-  oscores[s] = (crit == 1 || crit == 3) ? sqrtf(rank) : rank;
-  ocls[s] = c;
-  oloc[s * 2] = lx; oloc[s * 2 + 1] = ly;
-  octr[s] = 1.f / (1.f + expf(-br[4 * R1 + 4]));
-  // THRESH_WITH_CTR: cls_confs is taken after the centerness product (:1175-1179) - the ranking score the key carries
-  oconf[s] = (method & FCOS_THRESH_WITH_CTR) ? rank : 1.f / (1.f + expf(-logits[row * C + c]));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ostd[s * 4 + e] = br[4 * R1 + e];
-  olevel[s] = level;
-  ovalid[s] = 1;
+  integral4<R1>(br, d);
+  decode_live_slot(o, s, d, br + 4 * R1, br[4 * R1 + 4], logits + row * C + c, rank, hw, c, Wl, stride, level, method);
 }
 
-// ---------------------------------------------------------------------------------------------
-// The same positive-location terms and decode for the CONTINUOUS regression head (MODEL.FCOS.REG_DISCRETE False: the plain FCOS head,
-// fcos/fcos.py:294-297,363-364; the scalar distances go straight into the losses, fcos_outputs.py:349-350,545-546, and into the
-// decode, :1107-1108).  box rows: [ltrb 4 | std 4 | ctr 1 | pad], row stride BS floats.  The buffer holds the Scale layer's output
-// BEFORE the ReLU: d_b = max(row[b], 0) is taken on read here, and the backward writes 0 where the stored value is <= 0 (torch's
-// convention at exactly 0, and at -0.0) - the conv epilogue and the Scale kernels are the discrete head's, unchanged.
-#define CT_STD 4
-#define CT_CTR 8
-#define CT_COLS 9
-
-__global__ __launch_bounds__(128) void fcos_loc_cont_fwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
-                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
-                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
-                                                              float* __restrict__ partial) {
-  __shared__ float red[2];
-  float acc[LT_NSUM];
-#pragma unroll
-  for (int k = 0; k < LT_NSUM; ++k) acc[k] = 0.f;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < P; i += stride) {
-    const int lab = labels[i];
-    if (lab < 0 || lab == num_classes) continue;
-    const float* row = box + i * BS;
-    float d[4], t[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { d[b] = fmaxf(row[b], 0.f); t[b] = reg_targets[i * 4 + b]; }
-    float ctr_t = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
-    float iou;
-    const float gl = giou_ltrb(d, t, &iou, nullptr, (flags >> LT_LOC_SHIFT) & 3);
-    if (flags & LT_QUALITY_IOU) ctr_t = iou;
-    float nll = 0.f;
-    const float* sp = row + CT_STD;
-    if (flags & LT_KLLOSS) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float n = fabsf(d[b] - t[b]);
-        nll += expf(-sp[b]) * (n < 1.f ? 0.5f * n * n : n - 0.5f) + 0.5f * sp[b];
-      }
-      iou = (flags & LT_KL_WCTR) ? ctr_t : 1.f;
-    } else {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float sg = 1.f / (1.f + expf(-sp[b]));
-        const float sq = sg * sg;
-        const float df = t[b] - d[b];
-        nll += (df * df) / (2.f * sq) + 0.5f * logf(sq);
-      }
-      nll += 2.f * logf(2.f * 3.14159265358979323846f);
-    }
-    const float c = row[CT_CTR];
-    const float bce = fmaxf(c, 0.f) - c * ctr_t + log1pf(expf(-fabsf(c)));
-    acc[0] += 1.f;
-    acc[1] += ctr_t;
-    acc[2] += bce;
-    acc[3] += gl * ctr_t;
-    acc[4] += nll * iou;
-    if (bvars) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
-        const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
-        if (ct > ts_cert && ct > cs + ts_better) {
-          acc[5] += 1.f;
-          acc[6] += fabsf(d[b] - t[b]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < LT_NSUM; ++k) {
-    const float s = block_reduce_sum(acc[k], red);
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * LT_NSUM + k] = s;
-  }
-}
-
-// coef / coef8 / gscale / accumulate: as fcos_loc_bwd_kernel.  One thread per row, the row's arithmetic in double and rounded once per
-// output element like the discrete kernel's (positive rows only: the fp64 rate does not show); the teacher-better selection in fp32,
-// bit for bit the forward's.
-__global__ __launch_bounds__(128) void fcos_loc_cont_bwd_kernel(const int* __restrict__ labels, const float* __restrict__ box, int BS,
-                                                              const float* __restrict__ reg_targets, const float* __restrict__ bvars,
-                                                              size_t P, int num_classes, float ts_better, float ts_cert, int flags,
-                                                              const float* __restrict__ coef, float* __restrict__ dbox,
-                                                              const float* __restrict__ gscale, int coef8, int accumulate) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const float gs = gscale ? gscale[0] : 1.f;
-  const float c_bce = coef[coef8 ? 2 : 0] * gs, c_giou = coef[coef8 ? 3 : 1] * gs, c_nll = coef[coef8 ? 4 : 2] * gs,
-              c_l1 = coef[coef8 ? 6 : 3] * gs;
-  const int lab = labels[i];
-  float* grow = dbox + i * BS;
-  if (lab < 0 || lab == num_classes) {
-    if (!accumulate)
-      for (int k = 0; k < BS; ++k) grow[k] = 0.f;
-    return;
-  }
-  const float* row = box + i * BS;
-  double d[4], t[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) { d[b] = (double)fmaxf(row[b], 0.f); t[b] = (double)reg_targets[i * 4 + b]; }
-  double ctr_t = sqrt((fmin(t[0], t[2]) / fmax(t[0], t[2])) * (fmin(t[1], t[3]) / fmax(t[1], t[3])));
-  double iou, gg[4];
-  giou_ltrb_f64(d, t, &iou, gg, (flags >> LT_LOC_SHIFT) & 3);
-  if (flags & LT_QUALITY_IOU) ctr_t = iou;  // detached target
-  const float* sp = row + CT_STD;
-  float gout[CT_COLS];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const double sg = 1.0 / (1.0 + exp(-(double)sp[b]));
-    const double df = t[b] - d[b];
-    double dd, ds;
-    if (flags & LT_KLLOSS) {
-      const double n = fabs(df), es = exp(-(double)sp[b]);
-      const double sgn = df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0);
-      const double wk = (flags & LT_KL_WCTR) ? ctr_t : 1.0;   // a detached target
-      dd = (double)c_giou * ctr_t * gg[b] + (double)c_nll * wk * es * fmin(n, 1.0) * sgn;
-      ds = (double)c_nll * wk * (0.5 - es * (n < 1.0 ? 0.5 * n * n : n - 0.5));
-    } else {
-      dd = (double)c_giou * ctr_t * gg[b] + (double)c_nll * iou * (-df / (sg * sg));
-      ds = (double)c_nll * iou * (1.0 - sg) * (1.0 - (df * df) / (sg * sg));
-    }
-    if (bvars) {
-      const float cs = 1.f - 1.f / (1.f + expf(-sp[b]));
-      const float ct = 1.f - 1.f / (1.f + expf(-bvars[i * 4 + b]));
-      if (ct > ts_cert && ct > cs + ts_better) dd += (double)c_l1 * (df < 0.0 ? 1.0 : (df > 0.0 ? -1.0 : 0.0));
-    }
-    gout[b] = row[b] > 0.f ? (float)dd : 0.f;   // ReLU: no gradient at or below 0
-    gout[CT_STD + b] = (float)ds;
-  }
-  const double c = (double)row[CT_CTR];
-  gout[CT_CTR] = (float)((double)c_bce * (1.0 / (1.0 + exp(-c)) - ctr_t));
-  if (accumulate) {
-#pragma unroll
-    for (int k = 0; k < CT_COLS; ++k) grow[k] += gout[k];
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < CT_COLS; ++k) grow[k] = gout[k];
-  for (int k = CT_COLS; k < BS; ++k) grow[k] = 0.f;
-}
-
-// fcos_decode_kernel for the continuous rows: ltrb = max(r, 0) * stride (fcos_outputs.py:1107-1108).  A key whose flat index lies outside
-// this level's HW * C (it cannot come from utv2_fcos_rank_keys) is written as an empty slot, never followed.
+// the continuous rows: ltrb = max(r, 0) * stride (fcos_outputs.py:1107-1108)
 __global__ __launch_bounds__(128) void fcos_decode_cont_kernel(const long long* __restrict__ topkeys, int K, const float* __restrict__ logits,
                                                              const float* __restrict__ box, int BS, int HW, int Wl, int C, int stride,
                                                              int level, int method, int MAXC, int slot0, float* __restrict__ oboxes,
@@ -805,74 +760,19 @@ __global__ __launch_bounds__(128) void fcos_decode_cont_kernel(const long long* 
   const int n = blockIdx.y;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
+  const DecodeOut o = {oboxes, oscores, ocls, oloc, octr, oconf, ostd, olevel, ovalid};
   const size_t s = (size_t)n * MAXC + slot0 + k;
   const long long key = topkeys[(size_t)n * K + k];
-  const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFll);
-  if (key < 0 || (unsigned long long)flat >= (unsigned long long)HW * (unsigned long long)C) {
-    ovalid[s] = 0;
-    oscores[s] = -1.f;
-    ocls[s] = 0;
-    olevel[s] = level;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { oboxes[s * 4 + e] = 0.f; ostd[s * 4 + e] = 0.f; }
-    oloc[s * 2] = 0.f; oloc[s * 2 + 1] = 0.f; octr[s] = 0.f; oconf[s] = 0.f;
+  if (key_empty(key, HW, C)) {
+    decode_empty_slot(o, s, level);
     return;
   }
   const float rank = __uint_as_float((unsigned)(key >> 32));
-  const int hw = flat / C, c = flat - hw * C;
+  const int hw = key_flat(key) / C, c = key_flat(key) - hw * C;
   const size_t row = (size_t)n * HW + hw;
   const float* br = box + row * BS;
-  const int y = hw / Wl, x = hw - y * Wl;
-  const float lx = (float)(x * stride) + (float)(stride / 2), ly = (float)(y * stride) + (float)(stride / 2);
-  const float fs = (float)stride;
-  oboxes[s * 4 + 0] = lx - fmaxf(br[0], 0.f) * fs;
-  oboxes[s * 4 + 1] = ly - fmaxf(br[1], 0.f) * fs;
-  oboxes[s * 4 + 2] = lx + fmaxf(br[2], 0.f) * fs;
-  oboxes[s * 4 + 3] = ly + fmaxf(br[3], 0.f) * fs;
-  const int crit = method & 3;
-  oscores[s] = (crit == 1 || crit == 3) ? sqrtf(rank) : rank;
-  ocls[s] = c;
-  oloc[s * 2] = lx; oloc[s * 2 + 1] = ly;
-  octr[s] = 1.f / (1.f + expf(-br[CT_CTR]));
-  // THRESH_WITH_CTR: cls_confs is taken after the centerness product (:1175-1179) - the ranking score the key carries
-  oconf[s] = (method & FCOS_THRESH_WITH_CTR) ? rank : 1.f / (1.f + expf(-logits[row * C + c]));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ostd[s * 4 + e] = br[CT_STD + e];
-  olevel[s] = level;
-  ovalid[s] = 1;
-}
-
-// in-place y[:, 0:ncols] *= s[0] on rows of stride BS (Scale layer, fcos/fcos.py:22-28,356-357)
-__global__ __launch_bounds__(256) void scale_cols_kernel(float* __restrict__ y, size_t rows, int BS, int ncols, const float* __restrict__ s) {
-  const size_t total = rows * (size_t)ncols;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const float k = s[0];
-  for (; i < total; i += stride) {
-    const size_t r = i / ncols;
-    const int c = (int)(i - r * ncols);
-    y[r * BS + c] *= k;
-  }
-}
-
-// backward of the above: g[:, 0:ncols] *= s ; partial[b] = sum g_in * y_post   (ds = sum / s)
-__global__ __launch_bounds__(256) void scale_cols_bwd_kernel(float* __restrict__ g, const float* __restrict__ ypost, size_t rows, int BS,
-                                                           int ncols, const float* __restrict__ s, float* __restrict__ partial) {
-  __shared__ float red[4];
-  const size_t total = rows * (size_t)ncols;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const float k = s[0];
-  float acc = 0.f;
-  for (; i < total; i += stride) {
-    const size_t r = i / ncols;
-    const int c = (int)(i - r * ncols);
-    const float gv = g[r * BS + c];
-    acc += gv * ypost[r * BS + c];
-    g[r * BS + c] = gv * k;
-  }
-  const float t = block_reduce_sum(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  const float d[4] = {fmaxf(br[0], 0.f), fmaxf(br[1], 0.f), fmaxf(br[2], 0.f), fmaxf(br[3], 0.f)};
+  decode_live_slot(o, s, d, br + CT_STD, br[CT_CTR], logits + row * C + c, rank, hw, c, Wl, stride, level, method);
 }
 
 // The Scale layers of ALL FPN levels of a level-first matrix in one launch (fcos/fcos.py:22-28,306-340: one learnable scalar per level):
@@ -1253,33 +1153,18 @@ int utv2_fcos_decode_cont(const long long* topkeys, int K, const float* logits, 
                                  ocls, oloc, octr, oconf, ostd, olevel, ovalid, stream);
 }
 
-int utv2_scale_cols(float* y, int64_t rows, int row_stride, int ncols, const float* s, hipStream_t stream) {
-  if (!y || !s) return UTV2_EARG;
-  int g = cdiv(rows * ncols, 256);
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(scale_cols_kernel, dim3(g), dim3(256), 0, stream, y, (size_t)rows, row_stride, ncols, s);
-  return utv2_launch_status();
-}
-
-// g[:, :ncols] *= s in place; dsum[0] = sum(g_in * ypost) (caller divides by s).  ws >= 1024 floats.
-int utv2_scale_cols_bwd(float* g, const float* ypost, int64_t rows, int row_stride, int ncols, const float* s, float* dsum,
-                        float* ws, hipStream_t stream) {
-  if (!g || !ypost || !s || !dsum || !ws) return UTV2_EARG;
-  int nb = cdiv(rows * ncols, 256);
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(scale_cols_bwd_kernel, dim3(nb), dim3(256), 0, stream, g, ypost, (size_t)rows, row_stride, ncols, s, ws);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws, nb, 1, dsum);
-  return utv2_launch_status();
-}
-
-static int fill_scale_levels(ScaleLevels& L, int nlev, const int64_t* row0_host, const float* const* s_host, float* const* sgrad_host) {
-  if (nlev < 1 || nlev > SC_MAXL || !row0_host || !s_host) return UTV2_EARG;
+// ScaleLevels from the host arrays of an entry point; need_grad: every level must have an sgrad pointer.  *rows_max: the longest level.
+static int fill_scale_levels(ScaleLevels& L, int nlev, const int64_t* row0_host, const float* const* s_host, float* const* sgrad_host,
+                             bool need_grad, int64_t* rows_max) {
+  if (nlev < 1 || nlev > SC_MAXL || !row0_host || !s_host || (need_grad && !sgrad_host)) return UTV2_EARG;
   L.nlev = nlev;
+  *rows_max = 0;
   for (int l = 0; l <= SC_MAXL; ++l) L.row0[l] = row0_host[l <= nlev ? l : nlev];
   for (int l = 0; l < SC_MAXL; ++l) {
     L.s[l] = l < nlev ? s_host[l] : nullptr;
     L.sgrad[l] = (l < nlev && sgrad_host) ? sgrad_host[l] : nullptr;
-    if (l < nlev && (!L.s[l] || L.row0[l + 1] < L.row0[l])) return UTV2_EARG;
+    if (l < nlev && (!L.s[l] || L.row0[l + 1] < L.row0[l] || (need_grad && !L.sgrad[l]))) return UTV2_EARG;
+    if (l < nlev && L.row0[l + 1] - L.row0[l] > *rows_max) *rows_max = L.row0[l + 1] - L.row0[l];
   }
   return UTV2_OK;
 }
@@ -1289,9 +1174,8 @@ static int fill_scale_levels(ScaleLevels& L, int nlev, const int64_t* row0_host,
 int utv2_scale_cols_ml(float* y, int nlev, const int64_t* row0_host, int row_stride, int ncols, const float* const* s_host,
                        hipStream_t stream) {
   ScaleLevels L;
-  if (!y || fill_scale_levels(L, nlev, row0_host, s_host, nullptr) != UTV2_OK) return UTV2_EARG;
-  int64_t most = 0;
-  for (int l = 0; l < nlev; ++l) most = L.row0[l + 1] - L.row0[l] > most ? L.row0[l + 1] - L.row0[l] : most;
+  int64_t most;
+  if (!y || fill_scale_levels(L, nlev, row0_host, s_host, nullptr, false, &most) != UTV2_OK) return UTV2_EARG;
   int gx = cdiv(most * ncols, 256 * 4);
   if (gx > 1024) gx = 1024;
   if (gx < 1) gx = 1;
@@ -1300,16 +1184,13 @@ int utv2_scale_cols_ml(float* y, int nlev, const int64_t* row0_host, int row_str
 }
 
 // backward of all levels in two launches: g[rows of level l, 0:ncols] *= s_l in place and sgrad_l[0] += sum(g_in * ypost) / s_l
-// (sgrad_host: host array of nlev device pointers into the gradient arena).  ws >= nlev * 256 floats.
+// (sgrad_host: host array of nlev device pointers into the gradient arena).  ws >= nlev * 1024 floats.
 int utv2_scale_cols_bwd_ml(float* g, const float* ypost, int nlev, const int64_t* row0_host, int row_stride, int ncols,
                            const float* const* s_host, float* const* sgrad_host, float* ws, hipStream_t stream) {
   ScaleLevels L;
-  if (!g || !ypost || !ws || !sgrad_host || fill_scale_levels(L, nlev, row0_host, s_host, sgrad_host) != UTV2_OK) return UTV2_EARG;
-  for (int l = 0; l < nlev; ++l)
-    if (!L.sgrad[l]) return UTV2_EARG;
+  int64_t rows_max;
+  if (!g || !ypost || !ws || fill_scale_levels(L, nlev, row0_host, s_host, sgrad_host, true, &rows_max) != UTV2_OK) return UTV2_EARG;
   const int nb = 1024;
-  int64_t rows_max = 0;
-  for (int l = 0; l < nlev; ++l) rows_max = rows_max > row0_host[l + 1] - row0_host[l] ? rows_max : row0_host[l + 1] - row0_host[l];
   const bool vec4 = (row_stride & 3) == 0 && (ncols & 3) == 0 && (((uintptr_t)g | (uintptr_t)ypost) & 15) == 0 &&
                     rows_max * (row_stride >> 2) < (int64_t)1 << 31;
   if (vec4) hipLaunchKernelGGL(scale_cols_bwd_ml_kernel<true>, dim3(nb, nlev), dim3(256), 0, stream, g, ypost, L, row_stride, ncols, ws);
@@ -1321,11 +1202,8 @@ int utv2_scale_cols_bwd_ml(float* g, const float* ypost, int nlev, const int64_t
 int utv2_scale_cols_bwd_ml_pad16(const float* g, const float* ypost, int nlev, const int64_t* row0_host, int row_stride, int ncols,
                                  const float* const* s_host, float* const* sgrad_host, float* ws, void* out16, int cpad, hipStream_t stream) {
   ScaleLevels L;
-  if (!g || !ypost || !ws || !sgrad_host || !out16 || fill_scale_levels(L, nlev, row0_host, s_host, sgrad_host) != UTV2_OK) return UTV2_EARG;
-  for (int l = 0; l < nlev; ++l)
-    if (!L.sgrad[l]) return UTV2_EARG;
-  int64_t rows_max = 0;
-  for (int l = 0; l < nlev; ++l) rows_max = rows_max > row0_host[l + 1] - row0_host[l] ? rows_max : row0_host[l + 1] - row0_host[l];
+  int64_t rows_max;
+  if (!g || !ypost || !ws || !out16 || fill_scale_levels(L, nlev, row0_host, s_host, sgrad_host, true, &rows_max) != UTV2_OK) return UTV2_EARG;
   if ((row_stride & 3) || (ncols & 3) || (cpad & 3) || cpad < row_stride || ncols > row_stride || ((((uintptr_t)g | (uintptr_t)ypost) & 15) != 0) ||
       (((uintptr_t)out16) & 7) != 0 || rows_max * (cpad >> 2) >= (int64_t)1 << 31)
     return UTV2_EARG;

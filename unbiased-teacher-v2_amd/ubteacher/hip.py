@@ -664,11 +664,6 @@ def fcos_decode_cont(topkeys, logits, box, N, HW, Wl, stride, level, method, slo
          _p(outs["cls_confid"]), _p(outs["reg_pred_std"]), _p(outs["fpn_levels"]), _p(outs["valid"]), _stream())
 
 
-def scale_cols(y2d, ncols, s):
-    rows, BS = y2d.shape
-    call("utv2_scale_cols", _p(y2d), rows, BS, ncols, _p(s), _stream())
-
-
 def _i64arr(vals):
     return (ctypes.c_int64 * len(vals))(*[int(v) for v in vals])
 
@@ -702,14 +697,6 @@ def scale_cols_bwd_ml_pad16(g2d, ypost2d, rows, ncols, scales, sgrads, cpad):
     call("utv2_scale_cols_bwd_ml_pad16", _p(g2d), _p(ypost2d), len(rows), ctypes.cast(r0, c_p), g2d.shape[1], ncols, ctypes.cast(sp, c_p),
          ctypes.cast(gp, c_p), _p(ws), _p(out), int(cpad), _stream())
     return out
-
-
-def scale_cols_bwd(g2d, ypost2d, ncols, s):
-    rows, BS = g2d.shape
-    dsum = torch.empty(1, dtype=torch.float32, device=g2d.device)
-    ws = workspace(4096, g2d.device, "loss")
-    call("utv2_scale_cols_bwd", _p(g2d), _p(ypost2d), rows, BS, ncols, _p(s), _p(dsum), _p(ws), _stream())
-    return dsum
 
 
 # --------------------------------------------------------------------------------------------

@@ -185,7 +185,7 @@ def _sync_handles(layer, cs=None):
     from .utils.grad_sync import param_handles
     hs = param_handles(layer)
     if cs is not None:
-        hs = hs + (list(cs) if isinstance(cs, (list, tuple)) else [cs])
+        hs = hs + list(cs)
     return hs
 
 
@@ -229,10 +229,6 @@ class LevelMeta:
         C = t2d.shape[1]
         return torch.empty((0,), dtype=t2d.dtype, device=t2d.device).set_(
             t2d.untyped_storage(), t2d.storage_offset() + r0 * C, (self.N, h, w, C), (h * w * C, w * C, C, 1))
-
-
-def _scale_ml_on():
-    return os.environ.get("UTV2_SCALE_ML", "1") != "0"
 
 
 class FlipBank:
@@ -372,7 +368,7 @@ class Conv:
         self.relu = relu
         self.trainable = trainable
         self.kred = kred if kred is not None else k * k * cin
-        self.colscale = colscale  # (Handle scalar, ncols): Scale layer on the first ncols output channels
+        self.colscale = colscale  # ncols: the per-level Scale layers (colscale_handle of a call) act on the first ncols output channels
         self.out_fp32 = out_fp32  # AMP: keep this layer's output fp32 (loss-side head outputs, RoIAlign inputs)
         self.dgrad_pad_small = False  # set by the model builder: a layer of at most 32 output channels pads its 16-bit dgrad operand too (the
         #                               16-channel box head of the continuous FCOS head: its dgrad writes into a column half of the paired
@@ -440,7 +436,10 @@ class Conv:
 
     def __call__(self, x, residual=None, out=None, colscale_handle=None, meta=None):
         """x: NHWC tensor, or a level-first [P, C] matrix with `meta` (one launch for all levels; k x k
-        'same' convs only).  colscale_handle: a Handle, or one Handle per level when `meta` is given."""
+        'same' convs only).  colscale_handle: one Handle per level (the Scale layers of a level-first matrix; `meta` required)."""
+        if colscale_handle is not None:
+            assert meta is not None and isinstance(colscale_handle, (list, tuple)) and len(colscale_handle) == len(meta.rows), \
+                "colscale_handle: one Handle per level of `meta`"
         if torch.is_grad_enabled() and self.trainable:
             return _ConvFn.apply(x, residual, hook(x.device), self, (out, getattr(x, "_utv2_fanin", None), getattr(x, "_utv2_pair", None)),
                                  colscale_handle, meta)
@@ -499,15 +498,8 @@ class Conv:
             y = fn(x, w, scale=sc, bias=sh, residual=residual, stride=self.stride, pad=self.pad, relu=self.relu, kh=self.k,
                    kw=self.k, out=out, **kw)
         if cs is not None:
-            assert y.dtype == torch.float32
-            if meta is not None and _scale_ml_on() and y.is_contiguous():
-                hip.scale_cols_ml(y, meta.rows, self.colscale, [h.t for h in cs])      # all levels in one launch
-            elif meta is not None:
-                for l, h in enumerate(cs):
-                    r0, r1 = meta.rows[l]
-                    hip.scale_cols(y[r0:r1], self.colscale, h.t)
-            else:
-                hip.scale_cols(y.view(-1, self.cout), self.colscale, cs.t)
+            assert y.dtype == torch.float32 and y.is_contiguous()
+            hip.scale_cols_ml(y, meta.rows, self.colscale, [h.t for h in cs])      # all levels in one launch
         return y
 
 
@@ -537,6 +529,22 @@ class _ConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    def _scale_backward(ctx, dy, y, sc):
+        """Backward of the Scale layers (one per level) on the conv's output y: adds each level's d s_l and returns (the scaled gradient
+        the conv's own backward starts from, gp_ready = that gradient as the zero-padded 16-bit matrix the dgrad reads, or None)."""
+        layer, meta = ctx.layer, ctx.meta
+        s, sg = [h.t for h in ctx.cs], [h.g for h in ctx.cs]
+        if (dy.dtype == torch.float32 and layer.k > 1 and ctx.needs_input_grad[0] and layer.use_bf16_dgrad() and layer.use_bf16_wgrad()
+                and layer.dgrad_cout() != layer.cout and not layer.relu and sc is None and not ctx.has_res
+                and os.environ.get("UTV2_SCALE_BWD_PAD16", "1") != "0"):
+            # the bbox prediction conv (fcos.py:338-364): Scale backward, conversion and zero padding of the gradient in ONE pass, out of
+            # place - no clone of the incoming gradient, no in-place scale, no separate pad pass (568 -> 224 MB on the student batch)
+            return dy, hip.scale_cols_bwd_ml_pad16(dy, y, meta.rows, layer.colscale, s, sg, layer.dgrad_cout())
+        g = dy.clone()
+        hip.scale_cols_bwd_ml(g, y, meta.rows, layer.colscale, s, sg)   # all levels in two launches, in place
+        return g, None
+
+    @staticmethod
     def backward(ctx, dy):
         layer = ctx.layer
         if layer.gconv:
@@ -548,28 +556,8 @@ class _ConvFn(torch.autograd.Function):
         sc, _ = layer.scale_shift()
         meta = ctx.meta
         gp_ready = None
-        if (ctx.cs is not None and meta is not None and _scale_ml_on() and y.is_contiguous() and dy.dtype == torch.float32
-                and layer.k > 1 and ctx.needs_input_grad[0] and layer.use_bf16_dgrad() and layer.use_bf16_wgrad()
-                and layer.dgrad_cout() != layer.cout and not layer.relu and sc is None and not ctx.has_res
-                and os.environ.get("UTV2_SCALE_BWD_PAD16", "1") != "0"):
-            # the bbox prediction conv (fcos.py:338-364): Scale backward, conversion and zero padding of the gradient in ONE pass, out of
-            # place - no clone of the incoming gradient, no in-place scale, no separate pad pass (568 -> 224 MB on the student batch)
-            gp_ready = hip.scale_cols_bwd_ml_pad16(dy, y, meta.rows, layer.colscale, [h.t for h in ctx.cs], [h.g for h in ctx.cs],
-                                                   layer.dgrad_cout())
-        elif ctx.cs is not None:
-            g = dy.clone()
-            if meta is not None and _scale_ml_on() and y.is_contiguous():
-                # all levels in two launches (it was four per level, each waiting for the one before at the forward / backward seam)
-                hip.scale_cols_bwd_ml(g, y, meta.rows, layer.colscale, [h.t for h in ctx.cs], [h.g for h in ctx.cs])
-            elif meta is not None:
-                for l, h in enumerate(ctx.cs):
-                    r0, r1 = meta.rows[l]
-                    dsum = hip.scale_cols_bwd(g[r0:r1], y[r0:r1], layer.colscale, h.t)
-                    h.g.add_(dsum / h.t.view(-1))
-            else:
-                dsum = hip.scale_cols_bwd(g.view(-1, layer.cout), y.view(-1, layer.cout), layer.colscale, ctx.cs.t)
-                ctx.cs.g.add_(dsum / ctx.cs.t.view(-1))
-            dy = g
+        if ctx.cs is not None:
+            dy, gp_ready = _ConvFn._scale_backward(ctx, dy, y, sc)
         gres = None
         d16 = layer.use_bf16_dgrad()
         # AMP + FrozenBN: the BN multiplier is folded into the dgrad weight image and the wgrad slab reduction, so the
