@@ -1,7 +1,43 @@
-// Faster-RCNN specific kernels of the UTv2 step (gfx950): batched box<->gt matching (IoU max /
-// argmax + low-quality pass), multi-level RoIAlign (aligned, adaptive sampling) NHWC fwd/bwd,
-// softmax focal loss fwd/bwd.
+// Faster-RCNN specific kernels of the UTv2 step (gfx950), in file order: box<->gt matching (IoU max / argmax + low-quality pass); the
+// multi-level ROI pooler (RoIAlign V2 / V1, RoIPool; NHWC; forward, atomic and tiled backward); softmax focal loss; RPN ranking keys and
+// proposal decoding; the RPN losses (BCE + smooth-L1 / "giou"); anchor / proposal labelling and subsampling; the ROI box-regression
+// losses (modes 0..4); the predictor's inference chain and the NMS pack; the C-ABI entry points and the scalar loss tail.
+// A formula that several of these kernels need is written once ("Faster-RCNN loss and decode kernels").
 #include "common.h"
+
+// Sortable 64-bit keys: a float image in the high bits, an index in the low W bits stored as 2^W - 1 - index, so that DESCENDING key
+// order is (high part descending, index ascending).  utv2_topk_rows_i64 and rcnn.float_order_key (Python) read these layouts.
+// Signed-float monotone: mono_i32 of a float's bits is an int32 ordered like the float, any sign (its own inverse); positive-float:
+// f32_pos_bits, the bits as they are.
+__device__ __forceinline__ int mono_i32(int i) { return i ^ ((i >> 31) & 0x7FFFFFFF); }
+__device__ __forceinline__ int f32_pos_bits(float v) { return __float_as_int(v) & 0x7fffffff; }
+template <int W> __device__ __forceinline__ long long key_pack(long long hi, long long index) { return hi * (1ll << W) + (((1ll << W) - 1) - index); }
+template <int W> __device__ __forceinline__ long long key_index(long long key) { return ((1ll << W) - 1) - (key & ((1ll << W) - 1)); }
+
+// the 256-thread LDS tree sum in its fixed pairing order (s = 128 .. 1, thread t adds t + s); every thread calls it, all get the sum
+__device__ __forceinline__ float block_tree_sum_256(float* red, float v) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// fvcore smooth_l1_loss of one element d: returns the term, grad = its derivative.  l1 = beta < 1e-5f (the caller's): plain L1 - beta 0
+// adds |d| and writes sign(d), nothing divides by it.  |d| == beta is on the linear side (fvcore: where(n < beta, ...)); sign(0) = 0.
+// Masking is the caller's: a select for the sum, a 0 / 1 product for the derivative.
+__device__ __forceinline__ float smooth_l1(float d, float beta, bool l1, float& grad) {
+  const float ad = fabsf(d);
+  const bool quad = !l1 && ad < beta;
+  grad = quad ? d / beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
+  return quad ? 0.5f * d * d / beta : l1 ? ad : ad - 0.5f * beta;
+}
+
+// the box at q for a row / slot that carries weight, the neutral (0, 0, 1, 1) - and no load - for one that does not: what it names may
+// hold anything, and a non-finite operand must not reach a masked sum
+__device__ __forceinline__ float4 box_or_unit(const float* q, bool on) { return on ? *(const float4*)q : make_float4(0.f, 0.f, 1.f, 1.f); }
 
 // ---------------------------------------------------------------------------------------------
 // Matching (D2 pairwise_iou + Matcher [D2-recall]; called from proposal_generator/rpn.py:112-148 and
@@ -11,8 +47,10 @@
 //   gt_max[n][g]   = max_p IoU (as float bits, via atomicMax; IoU >= 0 so bit order == value order)
 #define MB_MAXG 256
 
-// valid gts of image n, compacted in their original order (256 threads, G <= MB_MAXG): sidx[k] = k-th valid slot; returns their number
-__device__ __forceinline__ int compact_valid_gts(const unsigned char* __restrict__ gt_valid, int n, int G, int* sidx, int* wcnt) {
+// both matcher kernels' prologue: the valid gts of image n, compacted in their original order (256 threads, G <= MB_MAXG): sidx[k] = k-th
+// valid slot, sg[k] = its box; returns their number.  The caller fills its own smax[], then holds the barrier that publishes both.
+__device__ __forceinline__ int load_valid_gts(const float* __restrict__ gt_boxes, const unsigned char* __restrict__ gt_valid, int n, int G,
+                                              float4* sg, int* sidx, int* wcnt) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const bool v = t < G && gt_valid[n * G + t];
   const unsigned long long b = __ballot(v);
@@ -23,6 +61,7 @@ __device__ __forceinline__ int compact_valid_gts(const unsigned char* __restrict
   if (v) sidx[base + __popcll(b & ((1ull << lane) - 1ull))] = t;
   const int total = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
   __syncthreads();
+  for (int k = threadIdx.x; k < total; k += blockDim.x) sg[k] = ((const float4*)gt_boxes)[(size_t)n * G + sidx[k]];
   return total;
 }
 
@@ -35,11 +74,8 @@ __global__ __launch_bounds__(256) void match_boxes_kernel(const float* __restric
   __shared__ unsigned smax[MB_MAXG];
   __shared__ int wcnt[4];
   const int n = blockIdx.y;
-  const int Gv = compact_valid_gts(gt_valid, n, G, sidx, wcnt);
-  for (int k = threadIdx.x; k < Gv; k += blockDim.x) {
-    sg[k] = ((const float4*)gt_boxes)[(size_t)n * G + sidx[k]];
-    smax[k] = 0u;
-  }
+  const int Gv = load_valid_gts(gt_boxes, gt_valid, n, G, sg, sidx, wcnt);
+  for (int k = threadIdx.x; k < Gv; k += blockDim.x) smax[k] = 0u;
   __syncthreads();
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < P) {
@@ -70,11 +106,8 @@ __global__ __launch_bounds__(256) void match_lowq_kernel(const float* __restrict
   __shared__ int sidx[MB_MAXG];
   __shared__ int wcnt[4];
   const int n = blockIdx.y;
-  const int scount = compact_valid_gts(gt_valid, n, G, sidx, wcnt);
-  for (int k = threadIdx.x; k < scount; k += blockDim.x) {
-    sg[k] = ((const float4*)gt_boxes)[(size_t)n * G + sidx[k]];
-    smax[k] = __uint_as_float(gt_max_bits[(size_t)n * G + sidx[k]]);
-  }
+  const int scount = load_valid_gts(gt_boxes, gt_valid, n, G, sg, sidx, wcnt);
+  for (int k = threadIdx.x; k < scount; k += blockDim.x) smax[k] = __uint_as_float(gt_max_bits[(size_t)n * G + sidx[k]]);
   __syncthreads();
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
@@ -778,6 +811,26 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_tiled(RoiBwdArgs a, const fl
 // Softmax focal loss of the ROI head (roi_heads/fast_rcnn.py:925-936 + FocalLoss :1405-1429):
 //   CE = logsumexp(x) - x[t];  p = exp(-CE);  loss = (1-p)^gamma * CE      (gamma 1.5), summed.
 // Rows with target < 0 are skipped.  One wave per row.
+// softmax_row: the statistics of row x (C logits, target t) both kernels need - m = max, s = sum exp(x - m), ce, p.  m is valid on every
+// lane; s, ce and p on every lane when ALL_LANES (the backward, which broadcasts s), on lane 0 only otherwise (the forward).
+struct SoftmaxRow { float m, s, ce, p; };
+
+template <bool ALL_LANES>
+__device__ __forceinline__ SoftmaxRow softmax_row(const float* __restrict__ x, int C, int t, int lane) {
+  SoftmaxRow o = {-INFINITY, 0.f, 0.f, 0.f};
+  for (int c = lane; c < C; c += 64) o.m = fmaxf(o.m, x[c]);
+  o.m = wave_reduce_max(o.m);
+  o.m = __shfl(o.m, 0, 64);
+  for (int c = lane; c < C; c += 64) o.s += expf(x[c] - o.m);
+  o.s = wave_reduce_sum(o.s);
+  if (ALL_LANES) o.s = __shfl(o.s, 0, 64);
+  if (ALL_LANES || lane == 0) {
+    o.ce = logf(o.s) + (o.m - x[t]);   // not (logf(s) + m) - x[t]: with logits of order 1e4 the sum m + log s rounds at 1e-3
+    o.p = expf(-o.ce);
+  }
+  return o;
+}
+
 __global__ __launch_bounds__(256) void softmax_focal_fwd_kernel(const float* __restrict__ logits, const int* __restrict__ target, int R, int C,
                                                               float gamma, float* __restrict__ partial) {
   __shared__ float red[4];
@@ -786,19 +839,8 @@ __global__ __launch_bounds__(256) void softmax_focal_fwd_kernel(const float* __r
   for (int r = blockIdx.x * 4 + wid; r < R; r += gridDim.x * 4) {
     const int t = target[r];
     if (t < 0) continue;
-    const float* x = logits + (size_t)r * C;
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-    m = wave_reduce_max(m);
-    m = __shfl(m, 0, 64);
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
-    s = wave_reduce_sum(s);
-    if (lane == 0) {
-      const float ce = logf(s) + (m - x[t]);   // not (logf(s) + m) - x[t]: with logits of order 1e4 the sum m + log s rounds at 1e-3
-      const float p = expf(-ce);
-      acc += powf(1.f - p, gamma) * ce;
-    }
+    const SoftmaxRow q = softmax_row<false>(logits + (size_t)r * C, C, t, lane);
+    if (lane == 0) acc += powf(1.f - q.p, gamma) * q.ce;
   }
   if (lane == 0) red[wid] = acc;
   __syncthreads();
@@ -818,20 +860,11 @@ __global__ __launch_bounds__(256) void softmax_focal_bwd_kernel(const float* __r
       for (int c = lane; c < C; c += 64) d[c] = 0.f;
       continue;
     }
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-    m = wave_reduce_max(m);
-    m = __shfl(m, 0, 64);
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
-    s = wave_reduce_sum(s);
-    s = __shfl(s, 0, 64);
-    const float ce = logf(s) + (m - x[t]);
-    const float p = expf(-ce);
-    const float om = 1.f - p;
-    const float dce = powf(om, gamma) + (om > 0.f ? gamma * powf(om, gamma - 1.f) * p * ce : 0.f);
+    const SoftmaxRow q = softmax_row<true>(x, C, t, lane);
+    const float om = 1.f - q.p;
+    const float dce = powf(om, gamma) + (om > 0.f ? gamma * powf(om, gamma - 1.f) * q.p * q.ce : 0.f);
     for (int c = lane; c < C; c += 64) {
-      const float sm = expf(x[c] - m) / s;
+      const float sm = expf(x[c] - q.m) / q.s;
       d[c] = k * dce * (sm - (c == t ? 1.f : 0.f));
     }
   }
@@ -858,6 +891,16 @@ struct RpnLevels {
   int out0[RPN_MAX_LEVELS + 1]; // first candidate slot of the level in the per-image output (k_l = out0[l+1] - out0[l])
 };
 
+// the level that head row / candidate slot / anchor v belongs to: the last of the n levels whose entry of `starts` (row0 / out0 /
+// anchor0) is <= v
+__device__ __forceinline__ int rpn_level_of(const int* starts, int n, int v) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < RPN_MAX_LEVELS; ++i)
+    if (i < n && v >= starts[i]) l = i;
+  return l;
+}
+
 // sortable keys of every objectness logit, in memory order: descending key order == (logit desc, anchor index asc) inside the
 // (level, image) row the logit belongs to; 63-bit non-negative (the select kernel's negative = empty)
 __global__ __launch_bounds__(256) void rpn_rank_keys_kernel(RpnLevels L, const float* __restrict__ head, int N, int A, int ch,
@@ -865,18 +908,41 @@ __global__ __launch_bounds__(256) void rpn_rank_keys_kernel(RpnLevels L, const f
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
   const int r = (int)(t / A), a = (int)(t - (long long)r * A);
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < RPN_MAX_LEVELS; ++i)
-    if (i < L.n && r >= L.row0[i]) l = i;
+  const int l = rpn_level_of(L.row0, L.n, r);
   const int p = (r - L.row0[l]) % L.hw[l];
-  const int bits = __float_as_int(head[(size_t)r * ch + a]);
-  const long long mono = (long long)(bits ^ ((bits >> 31) & 0x7FFFFFFF)) + 2147483648ll;
-  keys[t] = mono * 2147483648ll + (2147483647ll - ((long long)p * A + a));
+  keys[t] = key_pack<31>((long long)mono_i32(__float_as_int(head[(size_t)r * ch + a])) + 2147483648ll, (long long)p * A + a);
 }
 
-// one thread per (image, candidate): anchor index from the selected key, Box2BoxTransform.apply_deltas (separately rounded mul / add
-// as the elementwise reference chain), clip to the image, the finite / min-size keep mask
+// Centre-size Box2BoxTransform (D2 [D2-recall]), separately rounded mul / add as the elementwise reference chain: the one copy for
+// rpn_decode_kernel and the RPN loss.  apply_deltas: d / weights, dw and dh cut at scale_clamp by torch.clamp(max=) (a NaN stays a NaN;
+// cutw / cuth: the cut happened - the bound itself is not cut), no clip to an image; corners and the decoded width / height.
+struct CtrBox { float x1, y1, x2, y2, pw, ph; bool cutw, cuth; };
+
+__device__ __forceinline__ CtrBox ctr_apply_deltas(const float4& an, const float (&d)[4], const float4& wt, float scale_clamp) {
+  const float w = an.z - an.x, h = an.w - an.y;
+  const float cx = an.x + 0.5f * w, cy = an.y + 0.5f * h;
+  const float dx = d[0] / wt.x, dy = d[1] / wt.y;
+  float dw = d[2] / wt.z, dh = d[3] / wt.w;
+  CtrBox o;
+  o.cutw = dw > scale_clamp; o.cuth = dh > scale_clamp;
+  dw = o.cutw ? scale_clamp : dw;
+  dh = o.cuth ? scale_clamp : dh;
+  const float pcx = dx * w + cx, pcy = dy * h + cy;
+  o.pw = expf(dw) * w; o.ph = expf(dh) * h;
+  o.x1 = pcx - 0.5f * o.pw; o.y1 = pcy - 0.5f * o.ph; o.x2 = pcx + 0.5f * o.pw; o.y2 = pcy + 0.5f * o.ph;
+  return o;
+}
+
+// get_deltas: the regression target t[4] that takes anchor an to box b
+__device__ __forceinline__ void ctr_get_deltas(const float4& an, const float4& b, const float4& wt, float (&t)[4]) {
+  const float sw = an.z - an.x, sh = an.w - an.y, sx = an.x + 0.5f * sw, sy = an.y + 0.5f * sh;
+  const float tw = b.z - b.x, th = b.w - b.y, tx = b.x + 0.5f * tw, ty = b.y + 0.5f * th;
+  t[0] = wt.x * (tx - sx) / sw; t[1] = wt.y * (ty - sy) / sh;
+  t[2] = wt.z * logf(tw / sw); t[3] = wt.w * logf(th / sh);
+}
+
+// one thread per (image, candidate): anchor index from the selected key, ctr_apply_deltas, clip to the image, the finite / min-size
+// keep mask
 __global__ __launch_bounds__(256) void rpn_decode_kernel(RpnLevels L, const long long* __restrict__ top, int maxk, const float* __restrict__ head,
                                                        const float* __restrict__ anchors, const float* __restrict__ image_hw, int N, int A,
                                                        int ch, float wx, float wy, float ww, float wh, float scale_clamp, float min_size,
@@ -885,10 +951,7 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(RpnLevels L, const long
   const int K = L.out0[L.n];
   const int j = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
   if (j >= K) return;
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < RPN_MAX_LEVELS; ++i)
-    if (i < L.n && j >= L.out0[i]) l = i;
+  const int l = rpn_level_of(L.out0, L.n, j);
   const size_t o = (size_t)n * K + j;
   const long long key = top[((size_t)l * N + n) * maxk + (j - L.out0[l])];
   lvls[o] = l;
@@ -898,21 +961,14 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(RpnLevels L, const long
     keep[o] = 0;
     return;
   }
-  const int idx = (int)(2147483647ll - (key & 2147483647ll));
+  const int idx = (int)key_index<31>(key);
   const int p = idx / A, a = idx - p * A;
   const float* hrow = head + ((size_t)L.row0[l] + (size_t)n * L.hw[l] + p) * ch;
   const float sc = hrow[a];
   const float4 an = *(const float4*)(anchors + ((size_t)L.anchor0[l] + idx) * 4);
-  const float d0 = hrow[A + a * 4], d1 = hrow[A + a * 4 + 1], d2 = hrow[A + a * 4 + 2], d3 = hrow[A + a * 4 + 3];
-  const float w = an.z - an.x, h = an.w - an.y;
-  const float cx = an.x + 0.5f * w, cy = an.y + 0.5f * h;
-  const float dx = d0 / wx, dy = d1 / wy;
-  float dw = d2 / ww, dh = d3 / wh;
-  dw = dw > scale_clamp ? scale_clamp : dw;   // torch.clamp(max=): NaN stays NaN
-  dh = dh > scale_clamp ? scale_clamp : dh;
-  const float pcx = dx * w + cx, pcy = dy * h + cy;
-  const float pw = expf(dw) * w, ph = expf(dh) * h;
-  float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
+  const float d[4] = {hrow[A + a * 4], hrow[A + a * 4 + 1], hrow[A + a * 4 + 2], hrow[A + a * 4 + 3]};
+  const CtrBox q = ctr_apply_deltas(an, d, make_float4(wx, wy, ww, wh), scale_clamp);
+  float x1 = q.x1, y1 = q.y1, x2 = q.x2, y2 = q.y2;
   const bool finite = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(sc);
   const float H = image_hw[n * 2], W = image_hw[n * 2 + 1];
   x1 = x1 < 0.f ? 0.f : x1; y1 = y1 < 0.f ? 0.f : y1; x2 = x2 < 0.f ? 0.f : x2; y2 = y2 < 0.f ? 0.f : y2;
@@ -950,31 +1006,40 @@ struct RpnLossArgs {
   float beta, scale_clamp;
 };
 
-// fvcore giou_loss (eps 1e-7) of the box (px1, py1, px2, py2) against gb: 1 - (I / (U + eps) - (C - U) / (C + eps)), I = fvcore's
-// intersection (non-zero where both sides are > 0), C = the area of the smallest enclosing box; dL = its derivative w.r.t. px1, px2,
-// py1, py2 (in this order).  torch.max / torch.min send the gradient to the selected operand (half on a tie).  The one copy for
-// roi_box_loss_kernel (mode 4) and rpn_loss_fwd_kernel (loc_mode 1).
-__device__ __forceinline__ float giou_loss_grad(float px1, float py1, float px2, float py2, const float4& gb, float (&dL)[4]) {
+// Intersection I and union U of the box (px1, py1, px2, py2) with gb, and the derivatives dI / dA of I and of the box's own area
+// w.r.t. px1, px2, py1, py2 (in this order).  torch.max / torch.min send the gradient to the selected operand (half on a tie).
+// fvcore_open: fvcore's giou_loss has I = w * h only where BOTH sides are > 0 (an open interval, else 0 and no gradient); without it,
+// D2's pairwise IoU: each side clamped at 0, and clamp(min=0) passes the gradient where its input is >= 0.  The same I for finite
+// boxes; the derivatives differ on a side that is exactly 0.
+struct BoxOverlap { float I, U, dI[4], dA[4]; };
+__device__ __forceinline__ float max_share(float a, float b) { return a > b ? 1.f : a == b ? 0.5f : 0.f; }   // d max(a, b) / d a, tie halved
+
+__device__ __forceinline__ BoxOverlap box_overlap_grad(float px1, float py1, float px2, float py2, const float4& gb, bool fvcore_open) {
   const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
   const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
   const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
   const bool open = rbx > ltx && rby > lty;
-  const float I = !open ? 0.f : whx * why, U = a1 + a2 - I;
-  const float cx = open ? 1.f : 0.f, cy = cx;
-  const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-  const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-  const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
-  const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
-  const float Ue = U + 1e-7f;
+  const float I = (fvcore_open && !open) ? 0.f : whx * why;
+  const float cx = (fvcore_open ? open : (rbx - ltx) >= 0.f) ? 1.f : 0.f, cy = (fvcore_open ? open : (rby - lty) >= 0.f) ? 1.f : 0.f;
+  const float mx1 = max_share(px1, gb.x), mx2 = max_share(gb.z, px2), my1 = max_share(py1, gb.y), my2 = max_share(gb.w, py2);
+  return {I, a1 + a2 - I, {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2},
+          {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)}};
+}
+
+// fvcore giou_loss (eps 1e-7) of the box (px1, py1, px2, py2) against gb: 1 - (I / (U + eps) - (C - U) / (C + eps)), I = fvcore's
+// intersection, C = the area of the smallest enclosing box; dL = its derivative w.r.t. px1, px2, py1, py2 (in this order).  The one
+// copy for roi_box_loss_kernel (mode 4) and rpn_loss_fwd_kernel (loc_mode 1).
+__device__ __forceinline__ float giou_loss_grad(float px1, float py1, float px2, float py2, const float4& gb, float (&dL)[4]) {
+  const BoxOverlap ov = box_overlap_grad(px1, py1, px2, py2, gb, true);
+  const float I = ov.I, U = ov.U, Ue = U + 1e-7f;
   const float ew = fmaxf(px2, gb.z) - fminf(px1, gb.x), eh = fmaxf(py2, gb.w) - fminf(py1, gb.y);
   const float C = ew * eh, Ce = C + 1e-7f;
-  const float nx1 = px1 < gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, nx2 = px2 > gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-  const float ny1 = py1 < gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, ny2 = py2 > gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
+  const float nx1 = max_share(gb.x, px1), nx2 = max_share(px2, gb.z), ny1 = max_share(gb.y, py1), ny2 = max_share(py2, gb.w);
   const float dC[4] = {-eh * nx1, eh * nx2, -ew * ny1, ew * ny2};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const float dU = dA[k] - dI[k];
-    const float diou = (dI[k] * Ue - I * dU) / (Ue * Ue);
+    const float dU = ov.dA[k] - ov.dI[k];
+    const float diou = (ov.dI[k] * Ue - I * dU) / (Ue * Ue);
     const float dpen = ((dC[k] - dU) * Ce - (C - U) * dC[k]) / (Ce * Ce);
     dL[k] = dpen - diou;
   }
@@ -988,10 +1053,7 @@ __device__ __forceinline__ void rpn_locate(const RpnLevels& L, int head, int n, 
     o_dl = ((size_t)n * R + r) * 4;
     return;
   }
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < RPN_MAX_LEVELS; ++i)
-    if (i < L.n && r >= L.anchor0[i]) l = i;
+  const int l = rpn_level_of(L.anchor0, L.n, r);
   const int q = r - L.anchor0[l], p = q / A, a = q - p * A;
   const size_t row = (size_t)L.row0[l] + (size_t)n * L.hw[l] + p;
   o_obj = row * ch + a;
@@ -1002,7 +1064,7 @@ __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs p, float*
                                                          float* __restrict__ gdl) {
   __shared__ float red[2][256];
   const int S = p.npos + p.nneg;
-  const bool l1 = p.beta < 1e-5f;   // fvcore smooth_l1_loss: plain L1 below 1e-5 - beta 0 adds |d| and writes sign(d), nothing divides by it
+  const bool l1 = p.beta < 1e-5f;   // smooth_l1's plain-L1 switch
   float cls = 0.f, loc = 0.f;
   for (int slot = threadIdx.x; slot < p.N * S; slot += blockDim.x) {
     const int n = slot / S, j = slot - n * S;
@@ -1023,57 +1085,40 @@ __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnLossArgs p, float*
     gobj[slot] = w != 0.f ? (1.f / (1.f + expf(-x)) - t) * w : 0.f;
     if (pos) {
       const bool pv = valid && hg;
-      float4 a = make_float4(0.f, 0.f, 1.f, 1.f), b = a;
-      if (pv) {
-        a = *(const float4*)(p.anchors + (size_t)idx * 4);
-        b = *(const float4*)(p.gt_boxes + ((size_t)n * p.G + g) * 4);
-      }
-      const float sw = a.z - a.x, sh = a.w - a.y, sx = a.x + 0.5f * sw, sy = a.y + 0.5f * sh;
+      const float4 a = box_or_unit(p.anchors + (size_t)idx * 4, pv), b = box_or_unit(p.gt_boxes + ((size_t)n * p.G + g) * 4, pv);
+      const float4 wt = make_float4(p.wx, p.wy, p.ww, p.wh);
+      const float d[4] = {p.deltas[od], p.deltas[od + 1], p.deltas[od + 2], p.deltas[od + 3]};
       float* gout = gdl + ((size_t)n * p.npos + j) * 4;
       if (p.loc_mode == 0) {
-        const float tw = b.z - b.x, th = b.w - b.y, tx = b.x + 0.5f * tw, ty = b.y + 0.5f * th;
-        const float tgt[4] = {p.wx * (tx - sx) / sw, p.wy * (ty - sy) / sh, p.ww * logf(tw / sw), p.wh * logf(th / sh)};
+        float tgt[4];
+        ctr_get_deltas(a, b, wt, tgt);
         const float m = pv ? 1.f : 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float d = p.deltas[od + c] - tgt[c], ad = fabsf(d);
-          const bool quad = !l1 && ad < p.beta;   // |d| == beta is on the linear side (fvcore: where(n < beta, ...))
-          if (pv) loc += quad ? 0.5f * d * d / p.beta : l1 ? ad : ad - 0.5f * p.beta;
-          gout[c] = (quad ? d / p.beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f) * m;
+          float g;
+          const float term = smooth_l1(d[c] - tgt[c], p.beta, l1, g);
+          if (pv) loc += term;
+          gout[c] = g * m;
         }
       } else {
-        // "giou": Box2BoxTransform.apply_deltas on the anchor (rpn_decode_kernel's arithmetic, no clip to the image), then fvcore's GIoU
-        // loss against the matched gt box; x1 / x2 = pcx -+ pw / 2: the derivative w.r.t. dx is the sum of the two corner derivatives times
-        // w / wx, w.r.t. dw their difference times pw / (2 ww) - 0 where torch.clamp(max=) cut (its bound itself passes the gradient)
-        const float dx = p.deltas[od] / p.wx, dy = p.deltas[od + 1] / p.wy;
-        float dw = p.deltas[od + 2] / p.ww, dh = p.deltas[od + 3] / p.wh;
-        const bool cutw = dw > p.scale_clamp, cuth = dh > p.scale_clamp;
-        dw = cutw ? p.scale_clamp : dw;
-        dh = cuth ? p.scale_clamp : dh;
-        const float pcx = dx * sw + sx, pcy = dy * sh + sy;
-        const float pw = expf(dw) * sw, ph = expf(dh) * sh;
+        // "giou": the box rpn_decode_kernel decodes (before its clip to the image), then fvcore's GIoU loss against the matched gt box;
+        // x1 / x2 = pcx -+ pw / 2: the derivative w.r.t. dx is the sum of the two corner derivatives times w / wx, w.r.t. dw their
+        // difference times pw / (2 ww) - 0 where torch.clamp(max=) cut (its bound itself passes the gradient)
+        const CtrBox q = ctr_apply_deltas(a, d, wt, p.scale_clamp);
         float dL[4];
-        const float gl = giou_loss_grad(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph, b, dL);
+        const float gl = giou_loss_grad(q.x1, q.y1, q.x2, q.y2, b, dL);
         if (pv) loc += gl;
         // (selects: the deltas an empty slot's index names may be non-finite)
-        gout[0] = pv ? (dL[0] + dL[1]) * (sw / p.wx) : 0.f;
-        gout[1] = pv ? (dL[2] + dL[3]) * (sh / p.wy) : 0.f;
-        gout[2] = (pv && !cutw) ? (dL[1] - dL[0]) * (0.5f * pw / p.ww) : 0.f;
-        gout[3] = (pv && !cuth) ? (dL[3] - dL[2]) * (0.5f * ph / p.wh) : 0.f;
+        gout[0] = pv ? (dL[0] + dL[1]) * ((a.z - a.x) / p.wx) : 0.f;
+        gout[1] = pv ? (dL[2] + dL[3]) * ((a.w - a.y) / p.wy) : 0.f;
+        gout[2] = (pv && !q.cutw) ? (dL[1] - dL[0]) * (0.5f * q.pw / p.ww) : 0.f;
+        gout[3] = (pv && !q.cuth) ? (dL[3] - dL[2]) * (0.5f * q.ph / p.wh) : 0.f;
       }
     }
   }
-  red[0][threadIdx.x] = cls;
-  red[1][threadIdx.x] = loc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + s];
-      red[1][threadIdx.x] += red[1][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { sums[0] = red[0][0]; sums[1] = red[1][0]; }
+  cls = block_tree_sum_256(red[0], cls);
+  loc = block_tree_sum_256(red[1], loc);
+  if (threadIdx.x == 0) { sums[0] = cls; sums[1] = loc; }
 }
 
 // gradient of (gout[0] * cls_sum + gout[1] * loc_sum) scattered to the sampled anchors' logits / deltas (the caller zero-fills the
@@ -1130,7 +1175,7 @@ __global__ __launch_bounds__(256) void rpn_sample_keys_kernel(const float* __res
     const float H = image_hw[n * 2], W = image_hw[n * 2 + 1], t = boundary_thresh;
     if (!(a.x >= -t && a.y >= -t && a.z < W + t && a.w < H + t)) label = -1;
   }
-  const long long k = ((long long)(0x7fffffff - (__float_as_int(keys[o]) & 0x7fffffff)) << 32) | (long long)(0xffffffffu - (unsigned)r);
+  const long long k = key_pack<32>(0x7fffffff - f32_pos_bits(keys[o]), r);
   out[o] = label == 1 ? k : -1;
   out[(size_t)N * R + o] = label == 0 ? k : -1;
 }
@@ -1146,7 +1191,7 @@ __global__ __launch_bounds__(256) void rpn_sample_unpack_kernel(const long long*
   for (int j = threadIdx.x; j < npos_max; j += blockDim.x) {
     const long long key = j < k ? top[(size_t)n * k + j] : -1;
     const bool ok = key >= 0;
-    pos_idx[(size_t)n * npos_max + j] = ok ? (long long)(0xffffffffu - (unsigned)(key & 0xffffffffll)) : 0;
+    pos_idx[(size_t)n * npos_max + j] = ok ? key_index<32>(key) : 0;
     pos_valid[(size_t)n * npos_max + j] = ok;
     cnt += ok;
   }
@@ -1160,7 +1205,7 @@ __global__ __launch_bounds__(256) void rpn_sample_unpack_kernel(const long long*
   for (int j = threadIdx.x; j < nneg_max; j += blockDim.x) {
     const long long key = j < k ? top[(size_t)(N + n) * k + j] : -1;
     const bool ok = key >= 0 && j < room;
-    neg_idx[(size_t)n * nneg_max + j] = key >= 0 ? (long long)(0xffffffffu - (unsigned)(key & 0xffffffffll)) : 0;
+    neg_idx[(size_t)n * nneg_max + j] = key >= 0 ? key_index<32>(key) : 0;
     neg_valid[(size_t)n * nneg_max + j] = ok;
   }
 }
@@ -1191,7 +1236,7 @@ __global__ __launch_bounds__(512) void roi_sample_kernel(const float* __restrict
       const bool fgm = has_gt && mx[(size_t)n * P + i] >= iou_thr;
       const int cls = fgm ? gt_classes[(size_t)n * G + arg[(size_t)n * P + i]] : num_classes;
       grp = cls != num_classes ? 0 : 1;
-      kb = (unsigned)__float_as_int(keys[(size_t)n * P + i]) & 0x7fffffffu;
+      kb = f32_pos_bits(keys[(size_t)n * P + i]);
       atomicAdd(&cnt[grp], 1);
     }
     sk[i] = (grp << 60) | (kb << 20) | (unsigned long long)i;
@@ -1269,15 +1314,11 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
   }
   __shared__ float red[256];
   float acc = 0.f;
-  const bool l1 = beta < 1e-5f;   // fvcore smooth_l1_loss: plain L1 below 1e-5 - beta 0 adds |d| and writes sign(d), nothing divides by it
+  const bool l1 = beta < 1e-5f;   // smooth_l1's plain-L1 switch
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     const long long c = cls[r];
     const bool fg = c >= 0 && c < num_classes;
-    float4 pb = make_float4(0.f, 0.f, 1.f, 1.f), gb = pb;
-    if (fg) {
-      pb = *(const float4*)(prop + (size_t)r * 4);
-      gb = *(const float4*)(gtb + (size_t)r * 4);
-    }
+    const float4 pb = box_or_unit(prop + (size_t)r * 4, fg), gb = box_or_unit(gtb + (size_t)r * 4, fg);
     const size_t co = (fg && PER_CLASS) ? (size_t)c * 4 : 0;   // a background / empty row reads columns 0..3: its terms are all masked
     const float* dr = deltas + (size_t)r * ld + co;
     const float* sr = stdl + (size_t)r * ld + co;
@@ -1286,82 +1327,65 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
     const float sw = pb.z - pb.x + 1.f, sh = pb.w - pb.y + 1.f;
     const float t[4] = {wx * (gb.x - pb.x) / sw, wx * (gb.z - pb.z) / sw, wy * (gb.y - pb.y) / sh, wy * (gb.w - pb.w) / sh};
     float g_d[4] = {0.f, 0.f, 0.f, 0.f}, g_s[4] = {0.f, 0.f, 0.f, 0.f};
-    const float fgf = fg ? 1.f : 0.f;
-    if (!PER_CLASS && mode == 2) {   // (the entry point refuses the per-class form)
+    const bool ts = !PER_CLASS && mode == 2;   // (the entry point refuses the per-class form of mode 2)
+    if (mode != 4) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float ct = 1.f - sigmoidf_(gstd ? gstd[(size_t)r * 4 + k] : 0.f), cs = 1.f - sigmoidf_(sl[k]);
-        const float m = (ct > cs + ts_better && ct > t_cert && fg) ? 1.f : 0.f;
-        const float df = d[k] - t[k];
-        if (m != 0.f) acc += fabsf(df);     // (selected rows only: a non-finite delta on an unselected row must not reach the sum as inf * 0)
-        g_d[k] = (df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * m;
+        float m = fg ? 1.f : 0.f, g;
+        if (ts) {   // only the boundaries where the teacher is more certain, and at beta 0 whatever the config says, as the reference
+          const float ct = 1.f - sigmoidf_(gstd ? gstd[(size_t)r * 4 + k] : 0.f), cs = 1.f - sigmoidf_(sl[k]);
+          m = (ct > cs + ts_better && ct > t_cert && fg) ? 1.f : 0.f;
+        }
+        const float term = smooth_l1(d[k] - t[k], ts ? 0.f : beta, ts || l1, g);
+        if (m != 0.f) acc += term;     // (selected rows only: a non-finite delta on an unselected row must not reach the sum as inf * 0)
+        g_d[k] = g * m;
       }
-    } else {
-      if (mode != 4) {
+    }
+    if (mode == 0 || mode == 4) {
+      const float w = pb.z - pb.x, h = pb.w - pb.y;
+      const float wd[4] = {wx, wx, wy, wy};
+      const float side[4] = {w, w, h, h};
+      float q[4], dq[4];   // clamped delta / weight and its derivative w.r.t. the delta
+      // (a true division, as the fp64 reference: NOT shared with roi_infer_keys_kernel's decode, which multiplies by the reciprocal)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float v = d[k] / wd[k];
+        q[k] = v > clampv ? clampv : v < -clampv ? -clampv : v;   // NaN stays NaN like torch.clamp
+        dq[k] = (v >= -clampv && v <= clampv) ? side[k] / wd[k] : 0.f;
+      }
+      const float px1 = q[0] * w + pb.x, px2 = q[1] * w + pb.z, py1 = q[2] * h + pb.y, py2 = q[3] * h + pb.w;
+      if (mode == 0) {
+        // D2 pairwise IoU (both sides clamped at 0) of the decoded box; order of the deltas: x1, x2, y1, y2, as box_overlap_grad's
+        const BoxOverlap ov = box_overlap_grad(px1, py1, px2, py2, gb, false);
+        const float I = ov.I, U = ov.U;
+        const float iou = fg ? I / U : 0.f;
+        float nll = 0.f, sig[4], sq[4];   // (nl_loss takes the smooth-L1 beta and never reads it, fast_rcnn.py:1228-1292: no beta here)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float df = d[k] - t[k], a = fabsf(df);
-          const bool quad = !l1 && a < beta;   // |d| == beta is on the linear side (fvcore: where(n < beta, ...))
-          if (fg) acc += quad ? 0.5f * df * df / beta : l1 ? a : a - 0.5f * beta;
-          g_d[k] = (quad ? df / beta : df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f) * fgf;
+          sig[k] = sigmoidf_(sl[k]);
+          sq[k] = sig[k] * sig[k];
+          const float df = t[k] - d[k];
+          nll += df * df / (2.f * sq[k]) + 0.5f * logf(sq[k]);
         }
-      }
-      if (mode == 0 || mode == 4) {
-        const bool giou = mode == 4;
-        const float w = pb.z - pb.x, h = pb.w - pb.y;
-        const float wd[4] = {wx, wx, wy, wy};
-        const float side[4] = {w, w, h, h};
-        float q[4], dq[4];   // clamped delta / weight and its derivative w.r.t. the delta
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float v = d[k] / wd[k];
-          q[k] = v > clampv ? clampv : v < -clampv ? -clampv : v;   // NaN stays NaN like torch.clamp
-          dq[k] = (v >= -clampv && v <= clampv) ? side[k] / wd[k] : 0.f;
-        }
-        const float px1 = q[0] * w + pb.x, px2 = q[1] * w + pb.z, py1 = q[2] * h + pb.y, py2 = q[3] * h + pb.w;
-        if (!giou) {
-          const float a1 = (gb.z - gb.x) * (gb.w - gb.y), a2 = (px2 - px1) * (py2 - py1);
-          const float ltx = fmaxf(gb.x, px1), lty = fmaxf(gb.y, py1), rbx = fminf(gb.z, px2), rby = fminf(gb.w, py2);
-          const float whx = fmaxf(rbx - ltx, 0.f), why = fmaxf(rby - lty, 0.f);
-          // D2 pairwise IoU, both sides clamped at 0 (giou_loss_grad has fvcore's intersection, non-zero where both sides are > 0: the same
-          // value for finite boxes; the derivatives differ on a side that is exactly 0)
-          const float I = whx * why, U = a1 + a2 - I;
-          // torch.max / torch.min send the gradient to the selected operand (half on a tie), clamp(min=0) passes it where its input >= 0
-          const float cx = (rbx - ltx) >= 0.f ? 1.f : 0.f, cy = (rby - lty) >= 0.f ? 1.f : 0.f;
-          const float mx1 = px1 > gb.x ? 1.f : px1 == gb.x ? 0.5f : 0.f, mx2 = px2 < gb.z ? 1.f : px2 == gb.z ? 0.5f : 0.f;
-          const float my1 = py1 > gb.y ? 1.f : py1 == gb.y ? 0.5f : 0.f, my2 = py2 < gb.w ? 1.f : py2 == gb.w ? 0.5f : 0.f;
-          // order of the deltas: x1, x2, y1, y2
-          const float dI[4] = {-why * cx * mx1, why * cx * mx2, -whx * cy * my1, whx * cy * my2};
-          const float dA[4] = {-(py2 - py1), (py2 - py1), -(px2 - px1), (px2 - px1)};
-          const float iou = fg ? I / U : 0.f;
-          float nll = 0.f, sig[4], sq[4];   // (nl_loss takes the smooth-L1 beta and never reads it, fast_rcnn.py:1228-1292: no beta here)
+        nll += 2.f * 1.8378770664093453f;  // 2 log(2 pi)
+        // (foreground rows only, as the reference indexes them: on a background row a std logit below -88 makes nll = inf - inf, and
+        // NaN * 0 would put a NaN into the loss VALUE - the gradients below were always guarded)
+        if (fg) {
+          acc += 0.05f * (nll * iou);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            sig[k] = sigmoidf_(sl[k]);
-            sq[k] = sig[k] * sig[k];
-            const float df = t[k] - d[k];
-            nll += df * df / (2.f * sq[k]) + 0.5f * logf(sq[k]);
+            const float diou = (ov.dI[k] * (U + I) - I * ov.dA[k]) / (U * U) * dq[k];
+            const float df = d[k] - t[k];
+            g_d[k] += 0.05f * (iou * df / sq[k] + nll * diou);
+            g_s[k] = 0.05f * iou * (1.f - sig[k]) * (1.f - df * df / sq[k]);
           }
-          nll += 2.f * 1.8378770664093453f;  // 2 log(2 pi)
-          // (foreground rows only, as the reference indexes them: on a background row a std logit below -88 makes nll = inf - inf, and
-          // NaN * 0 would put a NaN into the loss VALUE - the gradients below were always guarded)
-          if (fg) acc += 0.05f * (nll * iou);
-          if (fg) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float diou = (dI[k] * (U + I) - I * dA[k]) / (U * U) * dq[k];
-              const float df = d[k] - t[k];
-              g_d[k] += 0.05f * (iou * df / sq[k] + nll * diou);
-              g_s[k] = 0.05f * iou * (1.f - sig[k]) * (1.f - df * df / sq[k]);
-            }
-          }
-        } else if (fg) {
-          // fvcore giou_loss of the decoded box (giou_loss_grad, shared with the RPN loss); the std head gets no gradient (g_s stays 0)
-          float dL[4];
-          acc += giou_loss_grad(px1, py1, px2, py2, gb, dL);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) g_d[k] = dL[k] * dq[k];
         }
+      } else if (fg) {
+        // fvcore giou_loss of the decoded box (giou_loss_grad, shared with the RPN loss); the std head gets no gradient (g_s stays 0)
+        float dL[4];
+        acc += giou_loss_grad(px1, py1, px2, py2, gb, dL);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g_d[k] = dL[k] * dq[k];
       }
     }
     if (fg || !PER_CLASS) {
@@ -1369,13 +1393,8 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
       *(float4*)(gs + (size_t)r * 4 * nbox + co) = make_float4(g_s[0], g_s[1], g_s[2], g_s[3]);
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sum[0] = red[0];
+  acc = block_tree_sum_256(red, acc);
+  if (threadIdx.x == 0) sum[0] = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1393,12 +1412,6 @@ __global__ __launch_bounds__(256) void roi_box_loss_kernel(const float* __restri
 //   gather: the k best keys of an image -> probability (recovered from the key), proposal row, class, the decoded box of (row, class) -
 //           nbox == 1: of the row -, candidate flag
 //   pack:   the NMS survivors -> padded detections (+ the 4 * nbox raw std logits of their proposal rows, fast_rcnn.py:1118-1123)
-__device__ __forceinline__ long long order_key_f32(float v, unsigned flat) {
-  const int i = __float_as_int(v);
-  const long long mono = (long long)(i ^ ((i >> 31) & 0x7FFFFFFF));
-  return mono * 4294967296ll + (long long)(4294967295u - flat);
-}
-
 __global__ __launch_bounds__(256) void roi_infer_keys_kernel(const float* __restrict__ probs, const float* __restrict__ deltas,
                                                            const float* __restrict__ prop, const unsigned char* __restrict__ valid,
                                                            const float* __restrict__ whwh, int N, int P, int K, int nbox, float wx, float wy,
@@ -1412,7 +1425,8 @@ __global__ __launch_bounds__(256) void roi_infer_keys_kernel(const float* __rest
   const float w = b.z - b.x, h = b.w - b.y;
   auto cl = [clampv](float v) { return v < -clampv ? -clampv : (v > clampv ? clampv : v); };   // a NaN stays a NaN (torch.clamp)
   // ATen divides a tensor by a host scalar as a multiplication by its fp32 reciprocal: the same here, so that the boxes are bit-identical
-  // to the op chain this replaces (a true division differs in the last bit for weights like 10)
+  // to the op chain this replaces (a true division differs in the last bit for weights like 10; NOT shared with roi_box_loss_kernel's
+  // decode, which divides as its fp64 reference does)
   const float iwx = 1.f / wx, iwy = 1.f / wy;
   const float* pr = probs + t * (K + 1);
   bool fin = true;
@@ -1430,7 +1444,7 @@ __global__ __launch_bounds__(256) void roi_infer_keys_kernel(const float* __rest
   long long* kr = keys + (long long)n * P * K + (long long)p * K;
   for (int c = lane; c < K; c += 64) {
     const float v = pr[c];
-    kr[c] = order_key_f32((ok && v > thr) ? v : -1.f, (unsigned)p * (unsigned)K + (unsigned)c);   // P*K < 2^32 (checked): no int overflow
+    kr[c] = key_pack<32>(mono_i32(__float_as_int((ok && v > thr) ? v : -1.f)), (unsigned)p * (unsigned)K + (unsigned)c);   // P*K < 2^32 (checked): no int overflow
   }
 }
 
@@ -1442,9 +1456,8 @@ __global__ __launch_bounds__(256) void roi_infer_gather_kernel(const long long* 
   if (t >= (long long)N * k) return;
   const int n = (int)(t / k);
   const long long key = top[t];
-  const unsigned flat = 4294967295u - (unsigned)(key & 0xFFFFFFFFll);   // < P*K for every key utv2_roi_infer_keys wrote
-  const int mono = (int)(key >> 32);
-  const float v = __int_as_float(mono ^ ((mono >> 31) & 0x7FFFFFFF));
+  const unsigned flat = (unsigned)key_index<32>(key);   // < P*K for every key utv2_roi_infer_keys wrote
+  const float v = __int_as_float(mono_i32((int)(key >> 32)));
   const unsigned r = flat / (unsigned)K, c = flat - r * (unsigned)K;
   sc[t] = v;
   rows[t] = (long long)r;
@@ -1503,7 +1516,6 @@ int utv2_nms_pack(const int* kidx, const int* cnt, const float* boxes, const flo
                      oscores, ovalid);
   return utv2_launch_status();
 }
-
 
 // boxes: [N][P][4] (box_img_stride = P*4) or shared anchors [P][4] (box_img_stride = 0).
 // gt_max_bits (optional, [N][G] uint32, must be zeroed by the caller) receives max-over-boxes IoU bits.
