@@ -625,12 +625,17 @@ def test_maxpool_backward_first_maximum_rule(dt):
         want = (xr.grad * (xr > 0)).permute(0, 2, 3, 1)
         got = hip.maxpool3x3s2_bwd(x, dy.permute(0, 2, 3, 1).contiguous(), relu=True)
         assert got.dtype == dt
+        # 16-bit: the kernel adds at most four 16-bit gradients in fp32 and rounds once (2^-9 relative); the fp32 sums of the two sides
+        # may differ in their order (a few 2^-24 of the largest gradient).  PER ELEMENT - a gradient that slips to a neighbouring pixel
+        # fails unless it is below 2^-20 of the largest (test_elementwise_edges_gpu.py compares the same kernel bit for bit on exact operands).
+        tol = lambda ref: 2.0 ** -8 * ref.abs() + 2.0 ** -20 * float(dy.float().abs().max())
         if dt == torch.float32:
             assert torch.equal(got, want)
         else:
-            assert float((got.float() - want).abs().max()) <= 2.0 ** -7 * float(want.abs().max())
+            assert bool(((got.float() - want).abs() <= tol(want)).all())
         raw = hip.maxpool3x3s2_bwd(x, dy.permute(0, 2, 3, 1).contiguous(), relu=False)
-        assert float((raw.float() - xr.grad.permute(0, 2, 3, 1)).abs().max()) <= (0 if dt == torch.float32 else 2.0 ** -7 * float(want.abs().max()))
+        full = xr.grad.permute(0, 2, 3, 1)
+        assert torch.equal(raw, full) if dt == torch.float32 else bool(((raw.float() - full).abs() <= tol(full)).all())
 
 
 @pytest.mark.parametrize("ydt", [BF, torch.float32])

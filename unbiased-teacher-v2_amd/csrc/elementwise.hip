@@ -314,6 +314,10 @@ __global__ __launch_bounds__(256) void add_f32(const float* __restrict__ a, cons
 
 // ---------------------------------------------------------------------------------------------
 // 3x3 stride-2 pad-1 max pool, NHWC (ResNet stem; frozen => forward only)
+// ATen's running maximum (`val > maxval || isnan(val)`): a NaN in the window is the window's maximum - fmaxf would drop it - so this
+// forward and the backward below name the same pixel.
+__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
+
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_k(const TI* __restrict__ x, TO* __restrict__ y, int N, int H,
                                                          int W, int C4, int OH, int OW) {
@@ -337,7 +341,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_k(const TI* __restrict_
         if ((unsigned)iw >= (unsigned)W) continue;
         const f32x4 v = ld4(x, ((size_t)(n * H + ih) * W + iw) * C4 + c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+        for (int e = 0; e < 4; ++e) m[e] = pool_max(m[e], v[e]);
       }
     }
     st4(y, i, m);
@@ -367,7 +371,9 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc_k(const TX* __restr
       for (int ow = w / 2; ow <= (w + 1) / 2; ++ow) {
         if (ow >= OW) continue;
         float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        int arg[4] = {-1, -1, -1, -1};
+        // ATen starts from the window's first existing tap: that is where the gradient of a window full of -inf goes
+        const int first = (oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0);
+        int arg[4] = {first, first, first, first};
 #pragma unroll
         for (int dh = 0; dh < 3; ++dh) {
           const int ih = oh * 2 - 1 + dh;
@@ -420,7 +426,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_bf16x8_k(const h16_t* _
         if ((unsigned)iw >= (unsigned)W) continue;
         const bf16x8_t v = ((const bf16x8_t*)x)[((size_t)(n * H + ih) * W + iw) * C8 + c];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], (float)v[e]);
+        for (int e = 0; e < 8; ++e) m[e] = pool_max(m[e], (float)v[e]);
       }
     }
     bf16x8_t o;

@@ -363,8 +363,12 @@ def upsample2x_add(lateral, top):
 
 def downsample2x_sum(g, out=None, accumulate=False):
     N, H, W, C = g.shape
+    # the kernel rebuilds g's row pitch as 2 * (W // 2): an odd size would read the wrong rows (upsample2x_add refuses it as well)
+    if H % 2 or W % 2:
+        raise ValueError("downsample2x_sum: H and W must be even, got %s" % (tuple(g.shape),))
     if out is None:
         out = torch.empty((N, H // 2, W // 2, C), dtype=g.dtype, device=g.device)
+    assert tuple(out.shape) == (N, H // 2, W // 2, C), (g.shape, out.shape)
     call("utv2_downsample2x_sum_nhwc", _p(g), _p(out), N, H // 2, W // 2, C, int(accumulate), _same_dt(g, out), _stream())
     return out
 
