@@ -1722,8 +1722,9 @@ int utv2_rcnn_loss_combine(const float* rpn_sup, const float* rpn_uns, const flo
                            const float* box_uns, const int* tgt_sup, int n_sup, const int* tgt_uns, int n_uns, float rpn_norm_sup,
                            float rpn_norm_uns, float w_rpn_cls, float w_rpn_loc, float w_box, const float* wt_host, float* rec, float* coef,
                            hipStream_t stream) {
-  if (!rpn_sup || !rpn_uns || !focal_sup || !focal_uns || !box_sup || !box_uns || !tgt_sup || !tgt_uns || !wt_host || !rec || !coef ||
-      n_sup < 0 || n_uns < 0 || !(rpn_norm_sup > 0.f) || !(rpn_norm_uns > 0.f))
+  // a target list of length 0 may come without storage (an empty tensor has no data pointer): the kernel never reads it, Rn clamps to 1
+  if (!rpn_sup || !rpn_uns || !focal_sup || !focal_uns || !box_sup || !box_uns || n_sup < 0 || n_uns < 0 || (!tgt_sup && n_sup > 0) ||
+      (!tgt_uns && n_uns > 0) || !wt_host || !rec || !coef || !(rpn_norm_sup > 0.f) || !(rpn_norm_uns > 0.f))
     return UTV2_EARG;
   RcnnCombineArgs a;
   a.rpn[0] = rpn_sup; a.rpn[1] = rpn_uns; a.focal[0] = focal_sup; a.focal[1] = focal_uns; a.box[0] = box_sup; a.box[1] = box_uns;

@@ -570,6 +570,11 @@ class FCOSOutputs:
         and 70 backward, the GPU idle in between) - is ONE utv2_fcos_loss_combine launch whose backward hands the kernels their
         coefficients.  loss_weights: key -> (mul, div), the loss enters the total as value * mul / div.  Returns (supervised dict,
         pseudo dict (keys without the suffix), weighted total); the dict entries are detached (metrics)."""
+        # the fused scalar tail has no switch for these: it would silently compute another loss than losses() / pseudo_losses()
+        if not self.kl_loss:
+            raise ValueError("pseudo regression loss needs MODEL.FCOS.KL_LOSS")  # as pseudo_losses (fcos_outputs.py:587-588)
+        if self.kl_loss_type == "klloss" and self.loc_fun_all != "mean":
+            raise ValueError("joint_losses knows the 'mean' reduction of KL_LOSS_TYPE 'klloss' only, not LOC_FUN_ALL %r" % (self.loc_fun_all,))
         logits_all, box_all = head_out["logits"], head_out["box"]
         nc, rm = self.num_classes, self.reg_max
         if os.environ.get("UTV2_JOINT_LOSS_NODE", "1") != "0":
