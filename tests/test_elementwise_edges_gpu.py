@@ -105,6 +105,28 @@ def test_maxpool_backward_nan_goes_where_aten_sends_it(h16, pair):
         assert agrees(hip.maxpool3x3s2_bwd(D(x, xdt), D(d, gdt), relu=relu), ref, "pool bwd nan %s relu=%s" % (pair, relu))
 
 
+def test_maxpool_backward_of_equal_taps_goes_to_the_first_tap(h16):
+    """a constant input: every existing tap of every window ties, so each window's whole gradient lands on its first existing tap,
+    pixel (max(2 oh - 1, 0), max(2 ow - 1, 0)) - the strict `>` of the rule the forward and the backward share; at H = W = 4 window
+    (1, 1) has all nine taps.  C = 4 and 8, every legal type pair."""
+    for pair in ("ff", "hh", "hf"):
+        xdt, gdt = _types(pair, h16)
+        for C in (4, 8):
+            for HW in (3, 4):
+                shape = (1, HW, HW, C)
+                x = torch.full(shape, 1.5)
+                d = R.pool_grad(shape, gdt, 7)
+                want = torch.zeros(shape, dtype=F64)
+                for oh in range(d.shape[1]):
+                    for ow in range(d.shape[2]):
+                        want[0, max(2 * oh - 1, 0), max(2 * ow - 1, 0)] += d[0, oh, ow].double()
+                ref = R.maxpool_bwd(x, d, False)
+                assert torch.equal(ref, want) and int((d != 0).sum()) > 2 * C
+                for relu in (False, True):
+                    dx = hip.maxpool3x3s2_bwd(D(x, xdt), D(d, gdt), relu=relu)
+                    assert agrees(dx, ref, "pool bwd ties %s %s relu=%s" % (pair, shape, relu))
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # FPN resampling
 @pytest.mark.parametrize("kind", ["f", "h"])
@@ -359,6 +381,47 @@ def test_amp_found_inf(h16):
         assert st.tolist() == [1024.0, 1.0, 7.0]
 
 
+EDGE_N = 64
+EDGE_SEGMENTS = [(0, 1), (1, 3), (3, 6), (6, 10), (12, 17), (17, 23), (23, 30)]    # lengths 1..7; the tail [30, 64) and [10, 12) are gaps
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_flat_sgd_equals_segmented_sgd_at_chunk_edges(h16, mirror):
+    """one arena of 64 floats cut into chunks of 1..7 elements that start at 0, 1, 2 and 3 mod 4 (heads of 0..3 elements, bodies of 0 or 1
+    quads, tails of 0..3): the segmented kernel's single-lane head / tail and its 16-byte body give the bytes of the flat kernel - both
+    call one update - and of the one-rounding-per-operation reference; plain, under AMP, and skipped under AMP with found_inf set"""
+    from ubteacher.params import SegmentTable
+    assert [e - s for s, e in EDGE_SEGMENTS] == list(range(1, 8)) and {s % 4 for s, _ in EDGE_SEGMENTS} == {0, 1, 2, 3}
+    lr, mo, wd, gs = 0.01, 0.9, 1e-4, 0.25
+    tb = SegmentTable(EDGE_N, EDGE_SEGMENTS, [(0, EDGE_N, wd)], DEV)
+    g0 = torch.Generator().manual_seed(11)
+    p, g, m = (R.grid((EDGE_N,), h16, g0, zero_frac=0.0) for _ in range(3))
+    bits16 = lambda t: None if t is None else t.view(torch.int16)
+    for state in (None, [1024.0, 0.0, 0.0], [1024.0, 1.0, 0.0]):
+        st = None if state is None else torch.tensor(state, device=DEV)
+        sp, sg, sm, smi = D(p), D(g), D(m), _mirror(EDGE_N, h16, mirror)
+        hip.sgd_segmented(sp, sg, sm, tb, lr, mo, gs, None, 1.0, False, st, mirror16=smi)
+        fp, fg, fm, fmi = D(p), D(g), D(m), _mirror(EDGE_N, h16, mirror)
+        if st is None:
+            hip.sgd_momentum(fp, fg, fm, lr, mo, wd, grad_scale=gs, zero_grad=False, mirror16=fmi)
+            pn, mn = R.sgd_momentum(p, g, m, lr, mo, wd, gs)
+        else:
+            hip.sgd_momentum_amp(fp, fg, fm, lr, mo, wd, gs, st, mirror16=fmi)
+            pn, mn = R.sgd_momentum_amp(p, g, m, lr, mo, wd, gs, torch.tensor(state))
+        for what, a, b in (("p", sp, fp), ("m", sm, fm)):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (what, state)
+        assert torch.equal(sg.cpu(), g) and torch.equal(fg.cpu(), g)
+        assert torch.equal(sp.cpu().view(torch.int32), pn.view(torch.int32)) and torch.equal(sm.cpu().view(torch.int32), mn.view(torch.int32)), state
+        if mirror:
+            assert torch.equal(bits16(smi), bits16(fmi)), state
+        if state is not None and state[1]:                             # found_inf: all three arrays stay untouched
+            assert torch.equal(sp.cpu(), p) and torch.equal(sm.cpu(), m) and torch.equal(fp.cpu(), p) and torch.equal(fm.cpu(), m)
+            assert not mirror or (bool((smi == SENTINEL).all()) and bool((fmi == SENTINEL).all()))
+        else:
+            assert not torch.equal(pn, p) and not torch.equal(mn, m)
+            assert not mirror or _mirror_ok(smi, pn)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # preprocess (all three C entries through hip.preprocess_images)
 def _pre_check(got, ref64, what):
@@ -429,6 +492,23 @@ def test_preprocess_rewrites_the_cached_stem_buffer(h16, kinds):
     assert float(g[0, 3 + 20:, :, :].abs().max()) == 0.0 and float(g[0, :, 3 + 30:, :].abs().max()) == 0.0
     assert float(g[1, 4:, :, :].abs().max()) == 0.0 and float(g[1, :, 4:, :].abs().max()) == 0.0
     assert float(g[:, :3].abs().max()) == 0.0 and float(g[:, :, :3].abs().max()) == 0.0
+
+
+def test_per_image_stem_path_equals_the_batched_path(h16):
+    """the first 32 of 33 tiny images in one batched launch, then all 33 one launch each (more than 32 images), through the same
+    kernel: slots 0..31 are byte-identical, the zero border (3 rows above, 3 below, 3 columns left, 5 right) included"""
+    sizes, kinds, div = PRE_BATCHES["tiny33_u8"]
+    dims = [D(i) for i in R.images_of(sizes, kinds, 5)]
+    batched, _ = hip.preprocess_images(dims[:32], R.PRE_MEAN, R.PRE_STD, div, bf16_stem=True)
+    each, _ = hip.preprocess_images(dims, R.PRE_MEAN, R.PRE_STD, div, bf16_stem=True)
+    assert batched.canvas == each.canvas == (4, 8) and batched.data_ptr() != each.data_ptr()
+    assert tuple(batched.shape) == (32, 10, 16, 4) and tuple(each.shape) == (33, 10, 16, 4)
+    assert torch.equal(batched.view(torch.int16), each[:32].view(torch.int16))
+    inner = each[:, 3:7, 3:11]
+    assert int((inner != 0).sum()) == 3 * sum(h * w for h, w in sizes)      # every pixel of every image, nothing beyond it
+    border = each.clone()
+    border[:, 3:7, 3:11] = 0
+    assert not bool(border.view(torch.int16).any())
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -23,12 +23,7 @@ __global__ __launch_bounds__(256) void ema_axpby_f32(float* __restrict__ teacher
 #pragma unroll
     for (int e = 0; e < 4; ++e) r[e] = __fadd_rn(__fmul_rn(s[e], a), __fmul_rn(t[e], b));
     t4[j] = r;
-    if (mirror16) {
-      bf16x4_t o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (h16_t)r[e];
-      ((bf16x4_t*)mirror16)[j] = o;
-    }
+    if (mirror16) st4(mirror16, j, r);
   }
   // tail
   for (size_t j = n4 * 4 + i; j < n; j += stride) {
@@ -39,67 +34,26 @@ __global__ __launch_bounds__(256) void ema_axpby_f32(float* __restrict__ teacher
 }
 
 // ---------------------------------------------------------------------------------------------
-// SGD with momentum + weight decay on a flat arena (D2 build_optimizer: torch.optim.SGD,
-// momentum 0.9, nesterov off).  g = grad*gscale + wd*p ; buf = mom*buf + g ; p -= lr*buf.
-// `gscale_ptr` (optional, device) multiplies the gradient (1/world for DDP mean, loss-scale
-// inverse); grad is zeroed afterwards if zero_grad != 0 (saves the separate memset pass).
-__global__ __launch_bounds__(256) void sgd_momentum_f32(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                      size_t n, float lr, float mom, float wd, float gscale,
-                                                      int zero_grad, h16_t* __restrict__ mirror16) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const float pv = p[i];
-    float gv = __fmul_rn(g[i], gscale);
-    gv = __fadd_rn(gv, __fmul_rn(wd, pv));
-    const float mv = __fadd_rn(__fmul_rn(mom, m[i]), gv);
-    m[i] = mv;
-    const float pn = __fsub_rn(pv, __fmul_rn(lr, mv));
-    p[i] = pn;
-    if (mirror16) mirror16[i] = (h16_t)pn;
-    if (zero_grad) g[i] = 0.f;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Dynamic loss scaling for the fp16 AMP mode, with torch.cuda.amp.GradScaler's semantics (the reference: engine/trainer.py:207,
 // 424-426 `scaler.scale(losses).backward(); scaler.step(optimizer); scaler.update()`), entirely on the device - no host read of
 // the inf flag.  state = fp32 {scale, found_inf, growth_tracker}:
-//   backward runs on scale * loss;  amp_found_inf marks non-finite gradients;  sgd_momentum_amp unscales (g / scale) and applies
-//   the update unless found_inf (GradScaler.step skips optimizer.step());  amp_update_scale: found_inf ? scale *= backoff, tracker = 0
-//   : (++tracker == interval ? scale *= growth, tracker = 0), then clears found_inf.
+//   backward runs on scale * loss;  amp_found_inf marks non-finite gradients;  the AMP forms of the SGD kernels unscale (g / scale) and
+//   apply the update unless found_inf (GradScaler.step skips optimizer.step());  amp_update_scale: found_inf ? scale *= backoff,
+//   tracker = 0 : (++tracker == interval ? scale *= growth, tracker = 0), then clears found_inf.
+// x - x is 0 for finite x, NaN for +-inf and NaN
+__device__ __forceinline__ bool is_finite_f(float x) { return x - x == 0.f; }
+
 __global__ __launch_bounds__(256) void amp_found_inf_f32(const float* __restrict__ g, size_t n4, size_t n, float* __restrict__ state) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   bool bad = false;
   for (; i < n4; i += stride) {
     const f32x4 v = ((const f32x4*)g)[i];
-    // x - x is 0 for finite x, NaN for +-inf and NaN
-    const float t = (v[0] - v[0]) + (v[1] - v[1]) + (v[2] - v[2]) + (v[3] - v[3]);
-    bad |= !(t == 0.f);
+    bad |= !(is_finite_f(v[0]) & is_finite_f(v[1]) & is_finite_f(v[2]) & is_finite_f(v[3]));
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (size_t k = n4 * 4; k < n; ++k) bad |= !((g[k] - g[k]) == 0.f);
+    for (size_t k = n4 * 4; k < n; ++k) bad |= !is_finite_f(g[k]);
   if (__any(bad) && (threadIdx.x & 63) == 0) state[1] = 1.0f;   // every writer stores the same value: order-free
-}
-
-__global__ __launch_bounds__(256) void sgd_momentum_amp_f32(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          size_t n, float lr, float mom, float wd, float gscale,
-                                                          const float* __restrict__ state, h16_t* __restrict__ mirror16) {
-  if (state[1] != 0.f) return;                       // non-finite gradients: the step is skipped (a fresh mirror16 stays fresh)
-  const float inv = 1.0f / state[0];                 // the scale is a power of two: exact
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const float pv = p[i];
-    float gv = __fmul_rn(__fmul_rn(g[i], inv), gscale);
-    gv = __fadd_rn(gv, __fmul_rn(wd, pv));
-    const float mv = __fadd_rn(__fmul_rn(mom, m[i]), gv);
-    m[i] = mv;
-    const float pn = __fsub_rn(pv, __fmul_rn(lr, mv));
-    p[i] = pn;
-    if (mirror16) mirror16[i] = (h16_t)pn;
-  }
 }
 
 __global__ void amp_update_scale_f32(float* __restrict__ state, float growth, float backoff, int interval) {
@@ -112,13 +66,55 @@ __global__ void amp_update_scale_f32(float* __restrict__ state, float growth, fl
     tracker += 1.f;
     if (tracker >= (float)interval) {
       const float grown = scale * growth;
-      if (grown - grown == 0.f) scale = grown;     // only while the grown scale is finite
+      if (is_finite_f(grown)) scale = grown;       // only while the grown scale is finite
       tracker = 0.f;
     }
   }
   state[0] = scale;
   state[1] = 0.f;
   state[2] = tracker;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SGD with momentum + weight decay on a flat arena (D2 build_optimizer: torch.optim.SGD, momentum 0.9).
+//   g = grad * gscale (AMP: grad * (1 / loss scale) * gscale) ; clip ; g += wd*p ; buf = mom*buf + g ; p -= lr*(nesterov ? g + mom*buf : buf)
+// sgd_elem is the ONE place the update is written: the flat kernel below calls it with no clip and no Nesterov as literals (those
+// branches fold away), the segmented kernel (next section) with its runtime clip between the gradient multiplier and the weight decay.
+enum { SEG_CLIP_NONE = 0, SEG_CLIP_VALUE = 1, SEG_CLIP_NORM = 2 };
+
+template <bool AMP>
+__device__ __forceinline__ float sgd_elem(float pv, float gr, float& mv, float inv, float gscale, int clip_mode, float cf, float cv,
+                                          float wd, float mom, float lr, int nesterov) {
+  float gv = AMP ? __fmul_rn(__fmul_rn(gr, inv), gscale) : __fmul_rn(gr, gscale);
+  if (clip_mode == SEG_CLIP_NORM) gv = __fmul_rn(gv, cf);
+  else if (clip_mode == SEG_CLIP_VALUE) gv = gv < -cv ? -cv : (gv > cv ? cv : gv);   // a NaN stays a NaN (clamp_)
+  gv = __fadd_rn(gv, __fmul_rn(wd, pv));
+  mv = __fadd_rn(__fmul_rn(mom, mv), gv);
+  const float step = nesterov ? __fadd_rn(gv, __fmul_rn(mom, mv)) : mv;
+  return __fsub_rn(pv, __fmul_rn(lr, step));
+}
+
+// The flat form: one element per lane.  `gscale` multiplies the gradient (1/world for DDP mean); AMP: `state` as above; otherwise grad is
+// zeroed afterwards if zero_grad != 0 (saves the separate memset pass).
+template <bool AMP>
+__global__ __launch_bounds__(256) void sgd_momentum_f32(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, size_t n,
+                                                      float lr, float mom, float wd, float gscale, int zero_grad,
+                                                      const float* __restrict__ state, h16_t* __restrict__ mirror16) {
+  float inv = 1.f;
+  if (AMP) {
+    if (state[1] != 0.f) return;                     // non-finite gradients: the step is skipped (a fresh mirror16 stays fresh)
+    inv = 1.0f / state[0];                           // the scale is a power of two: exact
+  }
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    float mv = m[i];
+    const float pn = sgd_elem<AMP>(p[i], g[i], mv, inv, gscale, SEG_CLIP_NONE, 1.f, 0.f, wd, mom, lr, 0);
+    m[i] = mv;
+    p[i] = pn;
+    if (mirror16) mirror16[i] = (h16_t)pn;
+    if (!AMP && zero_grad) g[i] = 0.f;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -157,6 +153,24 @@ __device__ __forceinline__ double seg_norm_wave(double v) {
   return v;
 }
 
+// How a workgroup of 256 lanes walks chunk [s, e): the body is n4 quads from a, the first 16-byte boundary (the arena's base is 16-byte
+// aligned); lanes 0..2 take the head elements in front of it, lanes 4..6 the tail elements behind the body; i = lane t's head or tail
+// element, or -1
+struct ChunkSplit {
+  int64_t a, n4, tail, i;
+};
+__device__ __forceinline__ ChunkSplit chunk_split(int64_t s, int64_t e, int t) {
+  ChunkSplit k;
+  k.a = (s + 3) & ~(int64_t)3;
+  if (k.a > e) k.a = e;
+  k.n4 = (e - k.a) >> 2;
+  k.tail = k.a + 4 * k.n4;
+  k.i = -1;
+  if (t < k.a - s) k.i = s + t;
+  else if (t >= 4 && t - 4 < e - k.tail) k.i = k.tail + t - 4;
+  return k;
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void seg_norm_partial(const float* __restrict__ g, const int64_t* __restrict__ chunk_start,
                                                       const int32_t* __restrict__ chunk_seg, int nchunks,
@@ -165,19 +179,14 @@ __global__ __launch_bounds__(256) void seg_norm_partial(const float* __restrict_
   const int t = threadIdx.x;
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
     if (chunk_seg[c] < 0) continue;                  // the same for the whole workgroup; nobody reads a gap's partial
-    const int64_t s = chunk_start[c], e = chunk_start[c + 1];
-    int64_t a = (s + 3) & ~(int64_t)3;               // first 16-byte boundary (the arena's base is 16-byte aligned)
-    if (a > e) a = e;
-    const int64_t n4 = (e - a) >> 2, tail = a + 4 * n4;
-    double acc = 0.0;
-    if (t < a - s) acc = seg_norm_term<KIND>(g[s + t]);                              // head: lanes 0..2
-    else if (t >= 4 && t - 4 < e - tail) acc = seg_norm_term<KIND>(g[tail + t - 4]);   // tail: lanes 4..6
-    for (int64_t j = t; j < n4; j += 4 * 256) {
+    const ChunkSplit k = chunk_split(chunk_start[c], chunk_start[c + 1], t);
+    double acc = k.i >= 0 ? seg_norm_term<KIND>(g[k.i]) : 0.0;
+    for (int64_t j = t; j < k.n4; j += 4 * 256) {
       f32x4 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {                  // four independent 16-byte loads in flight per lane
         const int64_t jj = j + 256 * u;
-        v[u] = jj < n4 ? *(const f32x4*)(g + a + 4 * jj) : f32x4{0.f, 0.f, 0.f, 0.f};
+        v[u] = jj < k.n4 ? *(const f32x4*)(g + k.a + 4 * jj) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -212,22 +221,6 @@ __global__ __launch_bounds__(64) void seg_clip_coef(const double* __restrict__ p
   }
 }
 
-enum { SEG_CLIP_NONE = 0, SEG_CLIP_VALUE = 1, SEG_CLIP_NORM = 2 };
-
-// one element of the update; the roundings are those of sgd_momentum_f32 / sgd_momentum_amp_f32, with the clip between the gradient
-// multiplier and the weight decay (cf == 1 and no Nesterov: the same bits as those kernels)
-template <bool AMP>
-__device__ __forceinline__ float sgd_seg_elem(float pv, float gr, float& mv, float inv, float gscale, int clip_mode, float cf, float cv,
-                                              float wd, float mom, float lr, int nesterov) {
-  float gv = AMP ? __fmul_rn(__fmul_rn(gr, inv), gscale) : __fmul_rn(gr, gscale);
-  if (clip_mode == SEG_CLIP_NORM) gv = __fmul_rn(gv, cf);
-  else if (clip_mode == SEG_CLIP_VALUE) gv = gv < -cv ? -cv : (gv > cv ? cv : gv);   // a NaN stays a NaN (clamp_)
-  gv = __fadd_rn(gv, __fmul_rn(wd, pv));
-  mv = __fadd_rn(__fmul_rn(mom, mv), gv);
-  const float step = nesterov ? __fadd_rn(gv, __fmul_rn(mom, mv)) : mv;
-  return __fsub_rn(pv, __fmul_rn(lr, step));
-}
-
 template <bool AMP>
 __global__ __launch_bounds__(256) void sgd_seg_f32(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                  h16_t* __restrict__ mirror16, const int64_t* __restrict__ chunk_start,
@@ -241,41 +234,30 @@ __global__ __launch_bounds__(256) void sgd_seg_f32(float* __restrict__ p, const 
   }
   const int t = threadIdx.x;
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const int64_t s = chunk_start[c], e = chunk_start[c + 1];
+    const ChunkSplit k = chunk_split(chunk_start[c], chunk_start[c + 1], t);
     const int seg = chunk_seg[c];
     const float cf = (clip_mode == SEG_CLIP_NORM && seg >= 0) ? coef[seg] : 1.f;
     const float wd = chunk_wd[c];
-    int64_t a = (s + 3) & ~(int64_t)3;
-    if (a > e) a = e;
-    const int64_t n4 = (e - a) >> 2, tail = a + 4 * n4;
-    int64_t i = -1;                                  // the head / tail element of this lane, if it has one
-    if (t < a - s) i = s + t;
-    else if (t >= 4 && t - 4 < e - tail) i = tail + t - 4;
-    if (i >= 0) {
-      float mv = m[i];
-      const float pn = sgd_seg_elem<AMP>(p[i], g[i], mv, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
-      m[i] = mv;
-      p[i] = pn;
-      if (mirror16) mirror16[i] = (h16_t)pn;
+    if (k.i >= 0) {
+      float mv = m[k.i];
+      const float pn = sgd_elem<AMP>(p[k.i], g[k.i], mv, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
+      m[k.i] = mv;
+      p[k.i] = pn;
+      if (mirror16) mirror16[k.i] = (h16_t)pn;
     }
-    for (int64_t j = t; j < n4; j += 256) {
-      const int64_t o = a + 4 * j;
+    for (int64_t j = t; j < k.n4; j += 256) {
+      const int64_t o = k.a + 4 * j;
       const f32x4 pv = *(const f32x4*)(p + o), gv = *(const f32x4*)(g + o);
       f32x4 mv = *(const f32x4*)(m + o), pn;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float mq = mv[q];
-        pn[q] = sgd_seg_elem<AMP>(pv[q], gv[q], mq, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
+        pn[q] = sgd_elem<AMP>(pv[q], gv[q], mq, inv, gscale, clip_mode, cf, cv, wd, mom, lr, nesterov);
         mv[q] = mq;
       }
       *(f32x4*)(m + o) = mv;
       *(f32x4*)(p + o) = pn;
-      if (mirror16) {
-        bf16x4_t h;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) h[q] = (h16_t)pn[q];
-        *(bf16x4_t*)(mirror16 + o) = h;
-      }
+      if (mirror16) st4(mirror16 + o, 0, pn);
     }
   }
 }
@@ -313,10 +295,43 @@ __global__ __launch_bounds__(256) void add_f32(const float* __restrict__ a, cons
 }
 
 // ---------------------------------------------------------------------------------------------
+// Element i of an [N][H][W][C] tensor as (n, h, w, c); C counts whatever one lane moves (quads or octets of channels).  I: the index type
+// the caller's loop runs in (size_t; unsigned for the kernel whose host check keeps it below 2^31).
+struct Nhwc {
+  int c, w, h, n;
+};
+template <typename I>
+__device__ __forceinline__ Nhwc nhwc_split(I i, int C, int W, int H) {
+  Nhwc s;
+  s.c = (int)(i % C); i /= C;
+  s.w = (int)(i % W); i /= W;
+  s.h = (int)(i % H); i /= H;
+  s.n = (int)i;
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3x3 stride-2 pad-1 max pool, NHWC (ResNet stem; frozen => forward only)
-// ATen's running maximum (`val > maxval || isnan(val)`): a NaN in the window is the window's maximum - fmaxf would drop it - so this
-// forward and the backward below name the same pixel.
-__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
+// ATen's running maximum (`val > maxval || isnan(val)`): a NaN in the window is the window's maximum - fmaxf would drop it - so the
+// forwards and the backward below name the same pixel.  pool_beats is that condition, pool_max the maximum it gives.
+__device__ __forceinline__ bool pool_beats(float m, float v) { return v > m || v != v; }
+__device__ __forceinline__ float pool_max(float m, float v) { return pool_beats(m, v) ? v : m; }
+
+// the window of output pixel (n, oh, ow) in (kh, kw) scan order: f(dh * 3 + dw, pixel index of (n, ih, iw)) for each tap that exists
+template <typename F>
+__device__ __forceinline__ void pool_window(int n, int oh, int ow, int H, int W, F&& f) {
+#pragma unroll
+  for (int dh = 0; dh < 3; ++dh) {
+    const int ih = oh * 2 - 1 + dh;
+    if ((unsigned)ih >= (unsigned)H) continue;
+#pragma unroll
+    for (int dw = 0; dw < 3; ++dw) {
+      const int iw = ow * 2 - 1 + dw;
+      if ((unsigned)iw >= (unsigned)W) continue;
+      f(dh * 3 + dw, (size_t)(n * H + ih) * W + iw);
+    }
+  }
+}
 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_k(const TI* __restrict__ x, TO* __restrict__ y, int N, int H,
@@ -325,25 +340,13 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_k(const TI* __restrict_
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C4); t /= C4;
-    const int ow = (int)(t % OW); t /= OW;
-    const int oh = (int)(t % OH); t /= OH;
-    const int n = (int)t;
+    const Nhwc o = nhwc_split(i, C4, OW, OH);
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    pool_window(o.n, o.h, o.w, H, W, [&](int, size_t px) {
+      const f32x4 v = ld4(x, px * C4 + o.c);
 #pragma unroll
-    for (int dh = 0; dh < 3; ++dh) {
-      const int ih = oh * 2 - 1 + dh;
-      if ((unsigned)ih >= (unsigned)H) continue;
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        const int iw = ow * 2 - 1 + dw;
-        if ((unsigned)iw >= (unsigned)W) continue;
-        const f32x4 v = ld4(x, ((size_t)(n * H + ih) * W + iw) * C4 + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = pool_max(m[e], v[e]);
-      }
-    }
+      for (int e = 0; e < 4; ++e) m[e] = pool_max(m[e], v[e]);
+    });
     st4(y, i, m);
   }
 }
@@ -358,11 +361,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc_k(const TX* __restr
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C4); t /= C4;
-    const int w = (int)(t % W); t /= W;
-    const int h = (int)(t % H); t /= H;
-    const int n = (int)t;
+    const Nhwc s = nhwc_split(i, C4, W, H);
+    const int c = s.c, w = s.w, h = s.h, n = s.n;
     const f32x4 mine = ld4(x, i);
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
     // windows that contain (h, w): 2 oh - 1 <= h <= 2 oh + 1, i.e. oh = h / 2 (and h / 2 + 1 for odd h)
@@ -374,20 +374,12 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_nhwc_k(const TX* __restr
         // ATen starts from the window's first existing tap: that is where the gradient of a window full of -inf goes
         const int first = (oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0);
         int arg[4] = {first, first, first, first};
+        pool_window(n, oh, ow, H, W, [&](int tap, size_t px) {
+          const f32x4 v = ld4(x, px * C4 + c);
 #pragma unroll
-        for (int dh = 0; dh < 3; ++dh) {
-          const int ih = oh * 2 - 1 + dh;
-          if ((unsigned)ih >= (unsigned)H) continue;
-#pragma unroll
-          for (int dw = 0; dw < 3; ++dw) {
-            const int iw = ow * 2 - 1 + dw;
-            if ((unsigned)iw >= (unsigned)W) continue;
-            const f32x4 v = ld4(x, ((size_t)(n * H + ih) * W + iw) * C4 + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; arg[e] = dh * 3 + dw; }
-          }
-        }
+          for (int e = 0; e < 4; ++e)
+            if (pool_beats(best[e], v[e])) { best[e] = v[e]; arg[e] = tap; }
+        });
         const int me = (h - (oh * 2 - 1)) * 3 + (w - (ow * 2 - 1));
         const f32x4 d = ld4(dpool, ((size_t)(n * OH + oh) * OW + ow) * C4 + c);
 #pragma unroll
@@ -408,27 +400,15 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_bf16x8_k(const h16_t* _
                                                                 int C8, int OH, int OW) {
   const unsigned total = (unsigned)N * OH * OW * C8;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    unsigned t = i;
-    const int c = (int)(t % C8); t /= C8;
-    const int ow = (int)(t % OW); t /= OW;
-    const int oh = (int)(t % OH); t /= OH;
-    const int n = (int)t;
+    const Nhwc s = nhwc_split(i, C8, OW, OH);
     float m[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+    pool_window(s.n, s.h, s.w, H, W, [&](int, size_t px) {
+      const bf16x8_t v = ((const bf16x8_t*)x)[px * C8 + s.c];
 #pragma unroll
-    for (int dh = 0; dh < 3; ++dh) {
-      const int ih = oh * 2 - 1 + dh;
-      if ((unsigned)ih >= (unsigned)H) continue;
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        const int iw = ow * 2 - 1 + dw;
-        if ((unsigned)iw >= (unsigned)W) continue;
-        const bf16x8_t v = ((const bf16x8_t*)x)[((size_t)(n * H + ih) * W + iw) * C8 + c];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = pool_max(m[e], (float)v[e]);
-      }
-    }
+      for (int e = 0; e < 8; ++e) m[e] = pool_max(m[e], (float)v[e]);
+    });
     bf16x8_t o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (h16_t)m[e];
@@ -445,13 +425,9 @@ __global__ __launch_bounds__(256) void upsample2x_add_nhwc_k(const T* __restrict
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const int TH = H >> 1, TW = W >> 1;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C4); t /= C4;
-    const int w = (int)(t % W); t /= W;
-    const int h = (int)(t % H); t /= H;
-    const int n = (int)t;
+    const Nhwc s = nhwc_split(i, C4, W, H);
     const f32x4 a = ld4(lat, i);
-    const f32x4 b = ld4(top, ((size_t)(n * TH + (h >> 1)) * TW + (w >> 1)) * C4 + c);
+    const f32x4 b = ld4(top, ((size_t)(s.n * TH + (s.h >> 1)) * TW + (s.w >> 1)) * C4 + s.c);
     st4(out, i, a + b);
   }
 }
@@ -465,12 +441,8 @@ __global__ __launch_bounds__(256) void downsample2x_sum_nhwc_k(const T* __restri
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const int H = TH * 2, W = TW * 2;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C4); t /= C4;
-    const int w = (int)(t % TW); t /= TW;
-    const int h = (int)(t % TH); t /= TH;
-    const int n = (int)t;
-    const size_t b = ((size_t)(n * H + 2 * h) * W + 2 * w) * C4 + c;
+    const Nhwc o = nhwc_split(i, C4, TW, TH);
+    const size_t b = ((size_t)(o.n * H + 2 * o.h) * W + 2 * o.w) * C4 + o.c;
     f32x4 s = ld4(g, b) + ld4(g, b + C4) + ld4(g, b + (size_t)W * C4) + ld4(g, b + (size_t)W * C4 + C4);
     if (accumulate) s += ld4(dtop, i);
     st4(dtop, i, s);
@@ -478,6 +450,22 @@ __global__ __launch_bounds__(256) void downsample2x_sum_nhwc_k(const T* __restri
 }
 
 // dgrad of a stride-2 1x1 conv: the compact gradient [N][TH][TW][C] lands on the even pixels of [N][H][W][C], zeros elsewhere
+// is s an even pixel?  off = where its value sits in the compact tensor (in the caller's units of C)
+__device__ __forceinline__ bool interleave_src(const Nhwc& s, int TH, int TW, int C, size_t& off) {
+  if ((s.h | s.w) & 1) return false;
+  off = ((size_t)(s.n * TH + (s.h >> 1)) * TW + (s.w >> 1)) * C + s.c;
+  return true;
+}
+
+// the ReLU mask of NV values as a lane mask (the layout of a mask_bits byte): bit q set = mk[q] > 0 = value q passes
+template <int NV, typename V>
+__device__ __forceinline__ unsigned keep_bits(const V& mk) {
+  unsigned mb = 0;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) mb |= ((float)mk[q] > 0.f ? 1u : 0u) << q;
+  return mb;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void zero_interleave2x_nhwc_k(const T* __restrict__ src, const T* __restrict__ mask, T* __restrict__ dst,
                                                               int N, int H, int W, int TH, int TW, int C4) {
@@ -485,18 +473,14 @@ __global__ __launch_bounds__(256) void zero_interleave2x_nhwc_k(const T* __restr
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C4); t /= C4;
-    const int w = (int)(t % W); t /= W;
-    const int h = (int)(t % H); t /= H;
-    const int n = (int)t;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!((h | w) & 1)) {
-      v = ld4(src, ((size_t)(n * TH + (h >> 1)) * TW + (w >> 1)) * C4 + c);
+    size_t off;
+    if (interleave_src(nhwc_split(i, C4, W, H), TH, TW, C4, off)) {
+      v = ld4(src, off);
       if (mask) {  // optional [N][H][W][C]: the gradient flows into a ReLU output, masked where it is made
-        const f32x4 mk = ld4(mask, i);
+        const unsigned mb = keep_bits<4>(ld4(mask, i));
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = mk[q] > 0.f ? v[q] : 0.f;
+        for (int q = 0; q < 4; ++q) v[q] = ((mb >> q) & 1u) ? v[q] : 0.f;
       }
     }
     st4(dst, i, v);
@@ -514,24 +498,15 @@ __global__ __launch_bounds__(256) void zero_interleave2x_add_h16_k(const h16_t* 
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
-    size_t t = i;
-    const int c = (int)(t % C8); t /= C8;
-    const int w = (int)(t % W); t /= W;
-    const int h = (int)(t % H); t /= H;
-    const int n = (int)t;
     float v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] = 0.f;
-    if (!((h | w) & 1)) {
-      const bf16x8_t sv = *(const bf16x8_t*)(src + (((size_t)(n * TH + (h >> 1)) * TW + (w >> 1)) * C8 + c) * 8);
+    size_t off;
+    if (interleave_src(nhwc_split(i, C8, W, H), TH, TW, C8, off)) {
+      const bf16x8_t sv = *(const bf16x8_t*)(src + off * 8);
       unsigned mb = 0xffu;
       if (mask_bits) mb = mask_bits[i];
-      else if (mask) {
-        const bf16x8_t mk = *(const bf16x8_t*)(mask + i * 8);
-        mb = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) mb |= ((float)mk[q] > 0.f ? 1u : 0u) << q;
-      }
+      else if (mask) mb = keep_bits<8>(*(const bf16x8_t*)(mask + i * 8));
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = ((mb >> q) & 1u) ? (float)sv[q] : 0.f;
     }
@@ -551,58 +526,41 @@ __global__ __launch_bounds__(256) void zero_interleave2x_add_h16_k(const h16_t* 
 // ---------------------------------------------------------------------------------------------
 // Image normalisation + CHW -> padded NHWC4 (one_stage_detector.py:88-90 / D2 preprocess_image +
 // ImageList.from_tensors): dst[n,h,w,c] = (src[c,h,w] - mean[c]) / std[c] for h<H,w<W, else 0.
+struct PreNorm {
+  float m[3], s[3];   // pixel mean and std per channel
+};
+
+// pixel (h, w) of the canvas from a [3][H][W] image: the normalised channels (a division, as the reference divides), zero beyond the image
+template <typename T>
+__device__ __forceinline__ f32x4 pre_pixel(const T* __restrict__ src, int H, int W, int h, int w, const PreNorm& nm) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (h < H && w < W) {
+    const size_t o = (size_t)h * W + w, hw = (size_t)H * W;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = ((float)src[c * hw + o] - nm.m[c]) / nm.s[c];
+  }
+  return v;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void preprocess_chw_to_nhwc4(const T* __restrict__ src, float* __restrict__ dst, int H, int W,
-                                                             int Hp, int Wp, float m0, float m1, float m2, float s0,
-                                                             float s1, float s2) {
+                                                             int Hp, int Wp, PreNorm nm) {
   const size_t total = (size_t)Hp * Wp;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    const int h = (int)(i / Wp), w = (int)(i % Wp);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (h < H && w < W) {
-      const size_t o = (size_t)h * W + w, hw = (size_t)H * W;
-      v[0] = ((float)src[o] - m0) / s0;
-      v[1] = ((float)src[hw + o] - m1) / s1;
-      v[2] = ((float)src[2 * hw + o] - m2) / s2;
-    }
-    ((f32x4*)dst)[i] = v;
-  }
+  for (; i < total; i += stride) ((f32x4*)dst)[i] = pre_pixel(src, H, W, (int)(i / Wp), (int)(i % Wp), nm);
 }
 
-// bf16 form for the MFMA stem: the image lands at pixel offset (3, 3) of a [Hp+6][Wp+8][4] bf16 buffer whose border the
-// caller zeroed once (rows pitch Wp+8); the padded canvas beyond the image is written as zeros here.
-template <typename T>
-__global__ __launch_bounds__(256) void preprocess_chw_to_nhwc4_bf16pad(const T* __restrict__ src, h16_t* __restrict__ dst, int H, int W,
-                                                                     int Hp, int Wp, float m0, float m1, float m2, float s0,
-                                                                     float s1, float s2) {
-  const size_t total = (size_t)Hp * Wp;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    const int h = (int)(i / Wp), w = (int)(i % Wp);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (h < H && w < W) {
-      const size_t o = (size_t)h * W + w, hw = (size_t)H * W;
-      v[0] = ((float)src[o] - m0) / s0;
-      v[1] = ((float)src[hw + o] - m1) / s1;
-      v[2] = ((float)src[2 * hw + o] - m2) / s2;
-    }
-    st4(dst, (size_t)(h + 3) * (Wp + 8) + (w + 3), v);
-  }
-}
-
-// the same for a whole batch in ONE launch (blockIdx.y = image): a training step preprocesses 12 + 4 images and each launch, with its
-// gap, sat at the very start of the step's critical path
+// bf16 form for the MFMA stem, a batch in ONE launch (blockIdx.y = image): image n lands at pixel offset (3, 3) of slot n of a
+// [N][Hp+6][Wp+8][4] bf16 buffer whose border the caller zeroed once (rows pitch Wp+8); the padded canvas beyond the image is written as
+// zeros here.  A training step preprocesses 12 + 4 images and each launch, with its gap, sat at the very start of the step's critical path.
 #define PRE_MAX_IMGS 32
 struct PreBatch {
   const void* src[PRE_MAX_IMGS];
   int H[PRE_MAX_IMGS], W[PRE_MAX_IMGS];
 };
 template <typename T>
-__global__ __launch_bounds__(256) void preprocess_batch_bf16pad(PreBatch b, h16_t* __restrict__ dst, int Hp, int Wp, float m0, float m1,
-                                                              float m2, float s0, float s1, float s2) {
+__global__ __launch_bounds__(256) void preprocess_batch_bf16pad(PreBatch b, h16_t* __restrict__ dst, int Hp, int Wp, PreNorm nm) {
   const int n = blockIdx.y, H = b.H[n], W = b.W[n];
   const T* __restrict__ src = (const T*)b.src[n];
   h16_t* out = dst + (size_t)n * (Hp + 6) * (Wp + 8) * 4;
@@ -611,14 +569,7 @@ __global__ __launch_bounds__(256) void preprocess_batch_bf16pad(PreBatch b, h16_
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     const int h = (int)(i / Wp), w = (int)(i % Wp);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (h < H && w < W) {
-      const size_t o = (size_t)h * W + w, hw = (size_t)H * W;
-      v[0] = ((float)src[o] - m0) / s0;
-      v[1] = ((float)src[hw + o] - m1) / s1;
-      v[2] = ((float)src[2 * hw + o] - m2) / s2;
-    }
-    st4(out, (size_t)(h + 3) * (Wp + 8) + (w + 3), v);
+    st4(out, (size_t)(h + 3) * (Wp + 8) + (w + 3), pre_pixel(src, H, W, h, w, nm));
   }
 }
 
@@ -1175,6 +1126,21 @@ static inline int grid_for(size_t n, int block = 256, int cap = 256 * 16) {
 
 static inline bool is_act_dtype(int dtype) { return dtype == UTV2_F32 || dtype == UTV2_BF16; }
 
+// the mean3_host / std3_host arguments of the three preprocess entries; false: one of them is missing
+static bool pre_norm(const float* mean3_host, const float* std3_host, PreNorm& nm) {
+  if (!mean3_host || !std3_host) return false;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3_host[c];
+    nm.s[c] = std3_host[c];
+  }
+  return true;
+}
+
+static void pre_batch_launch(int is_u8, dim3 grid, const PreBatch& b, void* dst16, int Hp, int Wp, const PreNorm& nm, hipStream_t stream) {
+  if (is_u8) hipLaunchKernelGGL((preprocess_batch_bf16pad<unsigned char>), grid, dim3(256), 0, stream, b, (h16_t*)dst16, Hp, Wp, nm);
+  else hipLaunchKernelGGL((preprocess_batch_bf16pad<float>), grid, dim3(256), 0, stream, b, (h16_t*)dst16, Hp, Wp, nm);
+}
+
 // stage 3 of both backward entries: dx, and dgamma / dbeta in the first cdiv(C, 64) workgroups (a workgroup past the last chunk finds no rows)
 template <typename T>
 static void gn_bwd_apply_launch(const GnSegs& sg, int chunks, const void* dy, const void* y, const void* x, const float* mean,
@@ -1203,8 +1169,8 @@ int utv2_sgd_momentum(float* param, float* grad, float* mom_buf, void* mirror16,
                       float grad_scale, int zero_grad, hipStream_t stream) {
   if (!param || !grad || !mom_buf || n < 0) return UTV2_EARG;
   if (n == 0) return UTV2_OK;
-  hipLaunchKernelGGL(sgd_momentum_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr,
-                     momentum, weight_decay, grad_scale, zero_grad, (h16_t*)mirror16);
+  hipLaunchKernelGGL(sgd_momentum_f32<false>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr,
+                     momentum, weight_decay, grad_scale, zero_grad, (const float*)nullptr, (h16_t*)mirror16);
   return utv2_launch_status();
 }
 
@@ -1220,8 +1186,9 @@ int utv2_sgd_momentum_amp(float* param, const float* grad, float* mom_buf, void*
                           float weight_decay, float grad_scale, const float* state, hipStream_t stream) {
   if (!param || !grad || !mom_buf || !state || n < 0) return UTV2_EARG;
   if (n == 0) return UTV2_OK;
-  hipLaunchKernelGGL(sgd_momentum_amp_f32, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, grad, mom_buf, (size_t)n, lr, momentum,
-                     weight_decay, grad_scale, state, (h16_t*)mirror16);
+  // (the AMP instantiation never writes grad: zero_grad belongs to the other one)
+  hipLaunchKernelGGL(sgd_momentum_f32<true>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, param, const_cast<float*>(grad), mom_buf,
+                     (size_t)n, lr, momentum, weight_decay, grad_scale, 0, state, (h16_t*)mirror16);
   return utv2_launch_status();
 }
 
@@ -1374,39 +1341,35 @@ int utv2_zero_interleave2x_add_nhwc(const void* src, const void* mask, const voi
 // src: one image [3][H][W], uint8 (is_u8) or fp32; dst: one padded NHWC4 image [Hp][Wp][4]
 int utv2_preprocess_image(const void* src, int is_u8, float* dst, int H, int W, int Hp, int Wp, const float* mean3_host,
                           const float* std3_host, hipStream_t stream) {
-  if (!src || !dst || H > Hp || W > Wp) return UTV2_EARG;
-  const float m0 = mean3_host[0], m1 = mean3_host[1], m2 = mean3_host[2];
-  const float s0 = std3_host[0], s1 = std3_host[1], s2 = std3_host[2];
+  PreNorm nm;
+  if (!src || !dst || H > Hp || W > Wp || !pre_norm(mean3_host, std3_host, nm)) return UTV2_EARG;
   const int g = grid_for((size_t)Hp * Wp, 256, 1 << 16);
   if (is_u8)
     hipLaunchKernelGGL((preprocess_chw_to_nhwc4<unsigned char>), dim3(g), dim3(256), 0, stream, (const unsigned char*)src,
-                       dst, H, W, Hp, Wp, m0, m1, m2, s0, s1, s2);
+                       dst, H, W, Hp, Wp, nm);
   else
-    hipLaunchKernelGGL((preprocess_chw_to_nhwc4<float>), dim3(g), dim3(256), 0, stream, (const float*)src, dst, H, W, Hp,
-                       Wp, m0, m1, m2, s0, s1, s2);
+    hipLaunchKernelGGL((preprocess_chw_to_nhwc4<float>), dim3(g), dim3(256), 0, stream, (const float*)src, dst, H, W, Hp, Wp, nm);
   return utv2_launch_status();
 }
 
-// dst16: one image slot [Hp+6][Wp+8][4] bf16 of the zero-bordered stem input (see utv2_conv2d_stem_fwd_bf16)
+// dst16: one image slot [Hp+6][Wp+8][4] bf16 of the zero-bordered stem input (see utv2_conv2d_stem_fwd_bf16): a batch of one
 int utv2_preprocess_image_bf16pad(const void* src, int is_u8, void* dst16, int H, int W, int Hp, int Wp, const float* mean3_host,
                                   const float* std3_host, hipStream_t stream) {
-  if (!src || !dst16 || H > Hp || W > Wp) return UTV2_EARG;
-  const float m0 = mean3_host[0], m1 = mean3_host[1], m2 = mean3_host[2];
-  const float s0 = std3_host[0], s1 = std3_host[1], s2 = std3_host[2];
-  const int g = grid_for((size_t)Hp * Wp, 256, 1 << 16);
-  if (is_u8)
-    hipLaunchKernelGGL((preprocess_chw_to_nhwc4_bf16pad<unsigned char>), dim3(g), dim3(256), 0, stream, (const unsigned char*)src,
-                       (h16_t*)dst16, H, W, Hp, Wp, m0, m1, m2, s0, s1, s2);
-  else
-    hipLaunchKernelGGL((preprocess_chw_to_nhwc4_bf16pad<float>), dim3(g), dim3(256), 0, stream, (const float*)src, (h16_t*)dst16,
-                       H, W, Hp, Wp, m0, m1, m2, s0, s1, s2);
+  PreNorm nm;
+  if (!src || !dst16 || H > Hp || W > Wp || !pre_norm(mean3_host, std3_host, nm)) return UTV2_EARG;
+  PreBatch b = {};
+  b.src[0] = src;
+  b.H[0] = H;
+  b.W[0] = W;
+  pre_batch_launch(is_u8, dim3(grid_for((size_t)Hp * Wp, 256, 1 << 16), 1), b, dst16, Hp, Wp, nm, stream);
   return utv2_launch_status();
 }
 
 // N <= 32 images (device pointers in src_host, sizes in H_host / W_host) into the N slots of dst16 = bf16 [N][Hp+6][Wp+8][4]
 int utv2_preprocess_images_bf16pad(const void* const* src_host, int is_u8, void* dst16, const int* H_host, const int* W_host, int N,
                                    int Hp, int Wp, const float* mean3_host, const float* std3_host, hipStream_t stream) {
-  if (!src_host || !dst16 || !H_host || !W_host || !mean3_host || !std3_host || N < 1 || N > PRE_MAX_IMGS) return UTV2_EARG;
+  PreNorm nm;
+  if (!src_host || !dst16 || !H_host || !W_host || !pre_norm(mean3_host, std3_host, nm) || N < 1 || N > PRE_MAX_IMGS) return UTV2_EARG;
   PreBatch b;
   for (int i = 0; i < PRE_MAX_IMGS; ++i) {
     b.src[i] = i < N ? src_host[i] : nullptr;
@@ -1414,14 +1377,7 @@ int utv2_preprocess_images_bf16pad(const void* const* src_host, int is_u8, void*
     b.W[i] = i < N ? W_host[i] : 0;
     if (i < N && (!src_host[i] || H_host[i] > Hp || W_host[i] > Wp || H_host[i] < 0 || W_host[i] < 0)) return UTV2_EARG;
   }
-  const float m0 = mean3_host[0], m1 = mean3_host[1], m2 = mean3_host[2];
-  const float s0 = std3_host[0], s1 = std3_host[1], s2 = std3_host[2];
-  const int g = grid_for((size_t)Hp * Wp, 256, 1 << 12);
-  if (is_u8)
-    hipLaunchKernelGGL((preprocess_batch_bf16pad<unsigned char>), dim3(g, N), dim3(256), 0, stream, b, (h16_t*)dst16, Hp, Wp, m0, m1, m2, s0,
-                       s1, s2);
-  else
-    hipLaunchKernelGGL((preprocess_batch_bf16pad<float>), dim3(g, N), dim3(256), 0, stream, b, (h16_t*)dst16, Hp, Wp, m0, m1, m2, s0, s1, s2);
+  pre_batch_launch(is_u8, dim3(grid_for((size_t)Hp * Wp, 256, 1 << 12), N), b, dst16, Hp, Wp, nm, stream);
   return utv2_launch_status();
 }
 
