@@ -153,6 +153,71 @@ def test_multi_level_routes_are_exact(name, h16):
             assert _eq(wide[:, :K], ref0, dt) and bool((wide[:, K:] == 7.0).all()), (name, dt, "padded columns")
 
 
+def _decode_and_table_outputs(name):
+    """(y without table, y with table) of one NHWC_CASES / ML_CASES entry on the selected build: the C entry point called directly, once
+    with rowinfo null - the tile prologue decodes its rows (conv_geom.h) - and once with the geometry table of the same conv"""
+    import ctypes
+    from ubteacher import hip
+    h16 = hip.h16_dtype()
+    ys = []
+    if name in R.NHWC_CASES:
+        N, H, W, C, K, k, s, p = R.NHWC_CASES[name][:8]
+        x, w2, _ = R.nhwc_operands(name)
+        OH, OW = _out_hw(H, W, k, s, p)
+        xd, w16 = x.cuda().to(h16), w2.cuda().to(h16)
+        for ri in (None, hip.rowinfo_nhwc(N, H, W, OH, OW, s, p, k, k, xd.device)):
+            y = torch.full((N, OH, OW, K), float("nan"), dtype=h16, device="cuda")
+            hip.call("utv2_conv2d_nhwc_fwd_bf16_bits", hip._p(xd), 1, hip._p(w16), hip._p(y), 1, None, None, None, None, None, N, H, W, C, K,
+                     k, k, s, p, 1, OH, OW, 0, 0, hip._p(ri), None, None, None, hip._stream())
+            ys.append(y)
+    else:
+        level_hw, N, C, K, bx, bw = R.ML_CASES[name]
+        g = torch.Generator().manual_seed(5)
+        P = N * sum(h * w for h, w in level_hw)
+        xd, w16 = R.dyadic((P, C), bx, -3, g).cuda().to(h16), R.dyadic((K, 9 * C), bw, -5, g).cuda().to(h16)
+        Hs, Ws = hip._iarr([h for h, _ in level_hw]), hip._iarr([w for _, w in level_hw])
+        for ri in (None, hip.rowinfo_ml(N, level_hw, 1, 3, xd.device)):
+            y = torch.full((P, K), float("nan"), dtype=h16, device="cuda")
+            hip.call("utv2_conv2d_ml_fwd_bf16_g", hip._p(xd), 1, C, hip._p(w16), hip._p(y), 1, K, None, None, None, len(level_hw),
+                     ctypes.cast(Hs, hip.c_p), ctypes.cast(Ws, hip.c_p), N, C, K, 3, 3, 1, 0, 0, 1, None, hip._p(ri), hip._stream())
+            ys.append(y)
+    torch.cuda.synchronize()
+    return ys
+
+
+# name -> the kernel whose prologue decodes; the environment of a fresh child process when a switch (read once per process) must differ
+_PROLOGUE_CASES = {
+    "v2_64_bk32": None,        # 3x3 stride 1 pad 1 on the 128 x 64 v2 tile: M = 81, one partial row tile
+    "strided_bk64": None,      # 3x3 stride 2 pad 1 (v2<128, ., 64>), 130 row tiles, the last one partial
+    "n96_72_ragged": None,     # two levels, 3x3: level 1 starts at row 10368 = 40.5 tiles of 256 rows (v2<96, true, 32>)
+    "pp_one_tile": {"UTV2_PP_RS": "0"},   # the smallest ping-pong case, kept off the row-span kernel
+}
+
+
+@pytest.mark.parametrize("name", list(_PROLOGUE_CASES))
+def test_tile_prologue_decode_equals_geometry_table(name, h16):
+    """The Python wrappers pass the geometry table wherever they can, so the in-kernel row decode of the v2 and ping-pong prologues runs only
+    for the image stem and under UTV2_CONV_ROWINFO=0.  It shares its formulas with the table builder (csrc/conv_geom.h): with and without
+    the table the same conv must give the same bits."""
+    env = _PROLOGUE_CASES[name]
+    if env is None:
+        y_decode, y_table = _decode_and_table_outputs(name)
+        assert not bool(torch.isnan(y_table.float()).any())
+        assert torch.equal(y_decode, y_table), name
+        return
+    import os
+    import subprocess
+    import sys
+    from ubteacher import hip
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r]; import torch; from ubteacher import hip; hip.set_h16(%r); "
+            "from tests.test_conv_exact_gpu import _decode_and_table_outputs as f; a, b = f(%r); "
+            "assert not bool(torch.isnan(b.float()).any()); assert torch.equal(a, b); print('same bits')"
+            % (root, os.path.dirname(os.path.dirname(os.path.abspath(hip.__file__))), hip.H16[0], name))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "same bits" in out.stdout, out.stderr[-2000:]
+
+
 @pytest.mark.parametrize("canvases", [R.STEM_CANVASES])
 def test_image_stem_is_exact(canvases, h16):
     from ubteacher import hip

@@ -24,9 +24,10 @@
 //            written in full 128-byte row pieces.
 // LDS: 43-45 KB (regions reused phase by phase, see the map in the kernel) -> three workgroups per CU, which overlap each other's load and
 // MFMA phases.  All LDS rows are XOR-swizzled on their 16-byte slots (64-byte rows: slot ^ (row >> 2 & 3); 128-byte rows: slot ^ (row & 7))
-// so the 32-row fragment reads are conflict-free.  blockIdx -> tile is XCD-aware (contiguous tile ranges per XCD: neighbouring tiles
-// share their halo through that XCD's L2).
+// so the 32-row fragment reads are conflict-free.  blockIdx -> tile is XCD-aware (xcd_tile of conv_geom.h: contiguous tile ranges per
+// XCD, so neighbouring tiles share their halo through that XCD's L2).
 #include "common.h"
+#include "conv_geom.h"
 
 #define BT_TH 8
 #define BT_TW 16
@@ -66,12 +67,7 @@ __global__ __launch_bounds__(256, 3) void bottleneck_fused(BtArgs a) {
   float* prm = (float*)(smem + BT_STAGE + BT_C1);           // s1 b1 s2 b2 (64 each) s3 b3 ssc bsc (256 each)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, fh = lane >> 5;
 
-  // XCD-aware bijective remap (blockIdx round-robins over the 8 XCDs): every XCD walks a contiguous range of tiles
-  int t;
-  {
-    const int bid = blockIdx.x, q = a.ntiles >> 3, r = a.ntiles & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int t = xcd_tile(blockIdx.x, a.ntiles);
   const int per = a.tiles_x * a.tiles_y;
   const int n = t / per, rem = t - n * per, ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
   const int y0 = ty * BT_TH, x0 = tx * BT_TW;
@@ -119,10 +115,7 @@ __global__ __launch_bounds__(256, 3) void bottleneck_fused(BtArgs a) {
   __syncthreads();
 
   f32x16 acc1[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc1[i][e] = 0.f;
+  zero_acc(acc1);
   const int pbA = wave, pbB = 4 + (wave >> 1), cbB = wave & 1;   // blocks (pbA, 0), (pbA, 1), (pbB, cbB)
   const int rowA = pbA * 32 + l31, rowB = pbB * 32 + l31;
   const int w0row = l31, w1row = 32 + l31;
@@ -195,10 +188,7 @@ __global__ __launch_bounds__(256, 3) void bottleneck_fused(BtArgs a) {
 
   // ---------------- phase 2: c2 = relu(conv2(c1) * s2 + b2) ----------------
   f32x16 acc2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc2[i][e] = 0.f;
+  zero_acc(acc2);
   const int p = wave * 32 + l31, pr = p >> 4, pc = p & 15;   // this lane's output pixel of the tile
   // a quarter of w3 = rows 64 g .. 64 g + 63 = [64][64] (128-byte rows): two pieces per thread; the same of the shortcut weight
   const int qco[2] = {tid >> 3, (tid + 256) >> 3}, qslot = tid & 7;
@@ -305,13 +295,8 @@ __global__ __launch_bounds__(256, 3) void bottleneck_fused(BtArgs a) {
       }
     }
     f32x16 acc3[2], accs[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc3[u][e] = 0.f;
-        if constexpr (SC) accs[u][e] = 0.f;
-      }
+    zero_acc(acc3);
+    if constexpr (SC) zero_acc(accs);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll

@@ -16,16 +16,9 @@
 // double-buffered so the next chunk's global loads are in flight during the MFMAs.
 // dgrad is the same kernel run on dY with the flipped/transposed weight image and
 // an input-dilation predicate (for strided forward convs).
+// The level table, tile order, output-row decode and accumulator fill are conv_geom.h's (shared with conv_bf16.hip).
 #include "common.h"
-
-#define CONV_MAX_LEVELS 8
-// Multi-level ("ragged") activations: rows [start[l], start[l+1]) hold N images of H[l] x W[l] pixels
-// (level-first layout of DESIGN.md section 2), so ONE launch covers every FPN level of a shared head.
-struct LevelTab {
-  int n;                         // 0 = single dense NHWC tensor
-  int start[CONV_MAX_LEVELS + 1];
-  int H[CONV_MAX_LEVELS], W[CONV_MAX_LEVELS];
-};
+#include "conv_geom.h"
 
 struct ConvArgs {
   LevelTab lt;
@@ -48,20 +41,6 @@ struct ConvArgs {
 // MODE 0: C % 16 == 0 (a 16-wide k chunk never straddles a filter tap)
 // MODE 1: C == 4 (stem on the NHWC4-padded image): each float4 is one tap
 // MODE 2: generic scalar gather (any C), weight rows unaligned
-__device__ __forceinline__ void ml_decode(const LevelTab& lt, int m, int& pixbase, int& H, int& W, int& oh, int& ow) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < CONV_MAX_LEVELS; ++i)
-    if (i < lt.n && m >= lt.start[i]) l = i;
-  H = lt.H[l];
-  W = lt.W[l];
-  const int r = m - lt.start[l], hw = H * W;
-  const int n = r / hw, rem = r - n * hw;
-  oh = rem / W;
-  ow = rem - oh * W;
-  pixbase = lt.start[l] + n * hw;
-}
-
 template <int BN, int MODE, bool ML = false>
 __global__ __launch_bounds__(256) void conv_igemm_f32(ConvArgs p) {
   constexpr int BM = 128, BK = 16, LDK = 20;
@@ -75,15 +54,8 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(ConvArgs p) {
   const int lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
-  // XCD-aware tile order: each XCD (bid % 8) walks a contiguous range of tiles so
-  // neighbouring M tiles (shared halo rows, same weights) hit one L2.
   const int tilesN = (p.K + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int tile;
-  {
-    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int mt = tile / tilesN, nt = tile - mt * tilesN;
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -106,12 +78,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(ConvArgs p) {
       iw0[r] = ow - p.pad;
       pixbase[r] = pb;
     } else {
-      const int hw = p.OH * p.OW;
-      const int n = mm / hw, rem = mm - n * hw;
-      const int oh = rem / p.OW, ow = rem - oh * p.OW;
-      ih0[r] = oh * p.stride - p.pad;
-      iw0[r] = ow * p.stride - p.pad;
-      pixbase[r] = (long long)n * p.H * p.W;
+      nhwc_row(mm, p.OH, p.OW, p.H, p.W, p.stride, p.pad, pixbase[r], ih0[r], iw0[r]);
       Hr[r] = p.H;
       Wr[r] = p.W;
     }
@@ -126,12 +93,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(ConvArgs p) {
   }
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const int nchunks = (p.Kred + BK - 1) / BK;
   int kh = 0, kw = 0, c0 = 0;  // MODE 0 chunk state
@@ -363,12 +325,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(WgradArgs p) {
   const int coidx = i0 + c4 * 4;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const int chunk_begin = split * p.chunks_per_split;
   const int total_chunks = (p.M + BK - 1) / BK;
@@ -376,7 +333,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(WgradArgs p) {
   if (chunk_end > total_chunks) chunk_end = total_chunks;
 
   f32x4 ra[2], rb[2];
-  const int hw = p.OH * p.OW;
 
   auto gload = [&](int chunk) {
 #pragma unroll
@@ -384,33 +340,30 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(WgradArgs p) {
       const int m = chunk * BK + lp + 8 * r;
       const bool mv = m < p.M;
       const int mm = mv ? m : 0;
-      int n, oh, ow, Hh = p.H, Ww = p.W;
+      int ih0, iw0, Hh = p.H, Ww = p.W;   // input row / column of tap (0, 0)
       long long pb;
       if constexpr (ML) {
-        int pbi;
+        int pbi, oh, ow;
         ml_decode(p.lt, mm, pbi, Hh, Ww, oh, ow);
         pb = pbi;
-        n = 0;
+        ih0 = oh * p.stride - p.pad;
+        iw0 = ow * p.stride - p.pad;
       } else {
-        n = mm / hw;
-        const int rem = mm - n * hw;
-        oh = rem / p.OW;
-        ow = rem - oh * p.OW;
-        pb = (long long)n * p.H * p.W;
+        nhwc_row(mm, p.OH, p.OW, p.H, p.W, p.stride, p.pad, pb, ih0, iw0);
       }
       f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
       if constexpr (VEC) {
         if (mv && coidx < p.K) va = *(const f32x4*)(p.dy + (size_t)mm * p.K + coidx);
-        const int ih = oh * p.stride - p.pad + tkh[0], iw = ow * p.stride - p.pad + tkw[0];
+        const int ih = ih0 + tkh[0], iw = iw0 + tkw[0];
         if (mv && kok[0] && (unsigned)ih < (unsigned)Hh && (unsigned)iw < (unsigned)Ww)
           vb = *(const f32x4*)(p.x + (size_t)(pb + (long long)ih * Ww + iw) * p.C + tci[0]);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (mv && coidx + e < p.K) va[e] = p.dy[(size_t)mm * p.K + coidx + e];
-          const int ih = oh * p.stride - p.pad + tkh[e], iw = ow * p.stride - p.pad + tkw[e];
+          const int ih = ih0 + tkh[e], iw = iw0 + tkw[e];
           if (mv && kok[e] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)
-            vb[e] = p.x[((size_t)((long long)n * p.H + ih) * p.W + iw) * p.C + tci[e]];
+            vb[e] = p.x[(size_t)(pb + (long long)ih * p.W + iw) * p.C + tci[e]];
         }
       }
       ra[r] = va;
@@ -537,23 +490,6 @@ __global__ void weight_flip_transpose_f32(const float* __restrict__ w, float* __
 }
 
 extern "C" int utv2_conv2d_wgrad_splits(int N, int OH, int OW, int K, int Kred);
-
-static int fill_levels(LevelTab& lt, int nlev, int N, const int* H, const int* W) {
-  lt.n = nlev;
-  int off = 0;
-  for (int l = 0; l < CONV_MAX_LEVELS; ++l) {
-    lt.start[l] = off;
-    if (l < nlev) {
-      lt.H[l] = H[l];
-      lt.W[l] = W[l];
-      off += N * H[l] * W[l];
-    } else {
-      lt.H[l] = lt.W[l] = 1;
-    }
-  }
-  lt.start[CONV_MAX_LEVELS] = off;
-  return off;
-}
 
 extern "C" {
 

@@ -14,22 +14,18 @@
 // BK = 32: a row of the LDS tile is 32 bf16 = 64 B (+16 B pad -> the same conflict-free 80-byte
 // stride); each thread stages 8 consecutive k of a row (two 16-byte global loads -> one
 // ds_write_b128); each MFMA reads one ds_read_b128 per operand fragment.
+// The level table, tile order, output-row decode, tap mask, geometry-table record and accumulator fill are conv_geom.h's
+// (shared with conv.hip).
 #include <mutex>
 #include <stdlib.h>
 #include "common.h"
+#include "conv_geom.h"
 #include <type_traits>
 
 // 64 zero bytes: out-of-image / out-of-range operand pieces are loaded from here, so every staging load is
 // unconditional (no exec-mask branches) and needs no masking of the loaded data (which would force the wave to wait for
 // its loads right after issuing them)
 __device__ uint4 g_zero64[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};  // never written (non-const keeps it in the global address space: global_load, not flat_load)
-
-#define CONV_MAX_LEVELS 8
-struct LevelTab {
-  int n;
-  int start[CONV_MAX_LEVELS + 1];
-  int H[CONV_MAX_LEVELS], W[CONV_MAX_LEVELS];
-};
 
 struct ConvArgs16 {
   LevelTab lt;
@@ -53,25 +49,11 @@ struct ConvArgs16 {
   int ntiles;                // conv_igemm_bf16_pp as a persistent grid: total tiles (0 = one tile per workgroup)
   EpiBits bits;              // optional ReLU bit planes (see epilogue_rows): written from / read in place of 16-bit sign tensors
   int mtot;                  // conv_igemm_bf16_rs: rows of x / rowinfo (>= M: a launch may cover a row range of the matrix)
-  const int2* rowinfo;       // optional: per OUTPUT row m {input pixel index of tap (0,0), (W << 16) | tap-validity mask} - the table the weight
+  const int2* rowinfo;       // optional: per OUTPUT row m the geometry record of conv_geom.h (rowinfo_pack) - the table the weight
                              // gradient kernels read (utv2_rowinfo_nhwc): the tile prologue then loads its rows' geometry instead of
                              // decoding it (level search, two integer divisions and a KH x KW bounds loop per staged row: 2.0-2.2 us of a
                              // 70 us tile on the 256-tile kernel, tools/probe/pp_trace)
 };
-
-__device__ __forceinline__ void ml_decode16(const LevelTab& lt, int m, int& pixbase, int& H, int& W, int& oh, int& ow) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < CONV_MAX_LEVELS; ++i)
-    if (i < lt.n && m >= lt.start[i]) l = i;
-  H = lt.H[l];
-  W = lt.W[l];
-  const int r = m - lt.start[l], hw = H * W;
-  const int n = r / hw, rem = r - n * hw;
-  oh = rem / W;
-  ow = rem - oh * W;
-  pixbase = lt.start[l] + n * hw;
-}
 
 // Matrix-pipe priority (round 5; measured, OFF by default).  Two waves of one SIMD that both have 32x32x16 MFMAs ready are served
 // alternately by the issue arbiter, and alternating costs the pipe a third of its rate: a register-only MFMA loop sustains 0.95 of the
@@ -108,12 +90,7 @@ __global__ __launch_bounds__(256) void conv_igemm_bf16(ConvArgs16 p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int tilesN = (p.K + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int tile;
-  {
-    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int mt = tile / tilesN, nt = tile - mt * tilesN;
   const int m0 = mt * BM, n0 = nt * BN;
   const int lrow = tid >> 2, kg = tid & 3;
@@ -128,17 +105,12 @@ __global__ __launch_bounds__(256) void conv_igemm_bf16(ConvArgs16 p) {
     const int mm = mvalid[r] ? m : 0;
     if constexpr (ML) {
       int pb, oh, ow;
-      ml_decode16(p.lt, mm, pb, Hr[r], Wr[r], oh, ow);
+      ml_decode(p.lt, mm, pb, Hr[r], Wr[r], oh, ow);
       ih0[r] = oh - p.pad;
       iw0[r] = ow - p.pad;
       pixbase[r] = pb;
     } else {
-      const int hw = p.OH * p.OW;
-      const int n = mm / hw, rem = mm - n * hw;
-      const int oh = rem / p.OW, ow = rem - oh * p.OW;
-      ih0[r] = oh * p.stride - p.pad;
-      iw0[r] = ow * p.stride - p.pad;
-      pixbase[r] = (long long)n * p.H * p.W;
+      nhwc_row(mm, p.OH, p.OW, p.H, p.W, p.stride, p.pad, pixbase[r], ih0[r], iw0[r]);
       Hr[r] = p.H;
       Wr[r] = p.W;
     }
@@ -153,12 +125,7 @@ __global__ __launch_bounds__(256) void conv_igemm_bf16(ConvArgs16 p) {
   }
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const int nchunks = p.KH * p.KW * ((p.C + BK - 1) / BK);  // a 32-channel slab per tap; the last slab may be partial (C % 8 == 0)
   int kh = 0, kw = 0, c0 = 0;
@@ -395,24 +362,6 @@ __global__ __launch_bounds__(256) void weight_flip_transpose_bf16_batched_kernel
   }
 }
 
-static int fill_levels16(LevelTab& lt, int nlev, int N, const int* H, const int* W) {
-  lt.n = nlev;
-  int off = 0;
-  for (int l = 0; l < CONV_MAX_LEVELS; ++l) {
-    lt.start[l] = off;
-    if (l < nlev) {
-      lt.H[l] = H[l];
-      lt.W[l] = W[l];
-      off += N * H[l] * W[l];
-    } else {
-      lt.H[l] = lt.W[l] = 1;
-    }
-  }
-  lt.start[CONV_MAX_LEVELS] = off;
-  return off;
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // Main kernel for bf16 activations (every backbone / FPN / tower layer): BK = 64 (C % 64 == 0; long, MFMA-bound K loops)
 // or BK = 32 (C % 32 == 0; short HBM-bound 1x1 layers, where 32 KB of LDS keeps 4 workgroups per CU in flight).
@@ -450,12 +399,7 @@ __global__ __launch_bounds__(256, TALL ? 3 : ((BK == 32 && BN != 96) ? 4 : 2)) v
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int tilesN = (p.K + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int tile;
-  {
-    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int mt = tile / tilesN, nt = tile - mt * tilesN;
   const int m0 = p.m_begin + mt * BM, n0 = nt * BN;
   const int lrow = tid / SLOTS, slot = tid % SLOTS;  // staged rows lrow + RPP*j, channels slot*8 .. +7 of the chunk
@@ -472,14 +416,15 @@ __global__ __launch_bounds__(256, TALL ? 3 : ((BK == 32 && BN != 96) ? 4 : 2)) v
     int pb, H, W, ih0, iw0;
     if (p.rowinfo) {
       const int2 ri = p.rowinfo[mm];
-      aoff[j] = ri.x * p.xs + slot * 8 + goff;
-      awc[j] = (ri.y >> 16) * p.xs;
-      amask[j] = mv ? (unsigned)(ri.y & 0xffff) : 0u;
+      const RowGeom g = rowinfo_unpack(ri);
+      aoff[j] = g.anchor * p.xs + slot * 8 + goff;
+      awc[j] = g.W * p.xs;
+      amask[j] = mv ? g.mask : 0u;
       continue;
     }
     if constexpr (ML) {
       int oh, ow;
-      ml_decode16(p.lt, mm, pb, H, W, oh, ow);
+      ml_decode(p.lt, mm, pb, H, W, oh, ow);
       ih0 = oh - p.pad;
       iw0 = ow - p.pad;
     } else {
@@ -489,22 +434,13 @@ __global__ __launch_bounds__(256, TALL ? 3 : ((BK == 32 && BN != 96) ? 4 : 2)) v
         amask[j] = mv ? 1u : 0u;
         continue;
       }
-      const int hw = p.OH * p.OW;
-      const int n = mm / hw, rem = mm - n * hw;
-      const int oh = rem / p.OW, ow = rem - oh * p.OW;
-      ih0 = oh * p.stride - p.pad;
-      iw0 = ow * p.stride - p.pad;
-      pb = n * p.H * p.W;
+      nhwc_row(mm, p.OH, p.OW, p.H, p.W, p.stride, p.pad, pb, ih0, iw0);
       H = p.H;
       W = p.W;
     }
     aoff[j] = (pb + ih0 * W + iw0) * p.xs + slot * 8 + goff;
     awc[j] = W * p.xs;
-    unsigned mk = 0;
-    for (int kh = 0; kh < p.KH; ++kh)
-      for (int kw = 0; kw < p.KW; ++kw)
-        if (mv && (unsigned)(ih0 + kh) < (unsigned)H && (unsigned)(iw0 + kw) < (unsigned)W) mk |= 1u << (kh * p.KW + kw);
-    amask[j] = mk;
+    amask[j] = tap_mask(ih0, iw0, H, W, p.KH, p.KW, mv);
   }
   int boff[BP];
   bool bvalid[BP];
@@ -516,12 +452,7 @@ __global__ __launch_bounds__(256, TALL ? 3 : ((BK == 32 && BN != 96) ? 4 : 2)) v
   }
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const h16_t* __restrict__ xb = (const h16_t*)p.x;
   const int nchunks = ntaps * (p.C / BK);
@@ -732,11 +663,7 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_pp(ConvArgs16 p) {
   // index a one-tile-per-workgroup launch would have had: same XCD-aware tile order); 0: one tile per workgroup
   const int nwg = p.ntiles > 0 ? p.ntiles : (int)gridDim.x;
   for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-  int tile;
-  {
-    const int bid = vb, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(vb, nwg);
   const int mt = tile / tilesN, nt = tile - mt * tilesN;
   const int m0 = p.m_begin + mt * BM, n0 = nt * BN;
   // DMA role of the lane: rows 32 * wid + 16 * j + (lane >> 2) of either operand, the k-slot that belongs in physical slot lane & 3
@@ -755,28 +682,26 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_pp(ConvArgs16 p) {
     int pb, H, W, ih0, iw0;
     if (p.rowinfo) {
       const int2 ri = p.rowinfo[mm];
-      aoff[j] = ri.x * p.xs + kslot * 8 + goff;
-      awc[j] = (ri.y >> 16) * p.xs;
-      amask[j] = mv ? (unsigned)(ri.y & 0xffff) : 0u;
+      const RowGeom g = rowinfo_unpack(ri);
+      aoff[j] = g.anchor * p.xs + kslot * 8 + goff;
+      awc[j] = g.W * p.xs;
+      amask[j] = mv ? g.mask : 0u;
       continue;
     }
     if constexpr (ML) {
       int oh, ow;
-      ml_decode16(p.lt, mm, pb, H, W, oh, ow);
+      ml_decode(p.lt, mm, pb, H, W, oh, ow);
       ih0 = oh - p.pad;
       iw0 = ow - p.pad;
     } else {
-      const int hw = p.OH * p.OW;
-      const int n = mm / hw, rem = mm - n * hw;
-      const int oh = rem / p.OW, ow = rem - oh * p.OW;
-      ih0 = oh * p.stride - p.pad;
-      iw0 = ow * p.stride - p.pad;
-      pb = n * p.H * p.W;
+      nhwc_row(mm, p.OH, p.OW, p.H, p.W, p.stride, p.pad, pb, ih0, iw0);
       H = p.H;
       W = p.W;
     }
     aoff[j] = (pb + ih0 * W + iw0) * p.xs + kslot * 8 + goff;
     awc[j] = W * p.xs;
+    // tap_mask(ih0, iw0, H, W, p.KH, p.KW, mv) of conv_geom.h, as literal text: through the helper the multi-level instantiations of THIS
+    // kernel (232 VGPRs, scalar registers spilled) come out with other register and spill counts
     unsigned mk = 0;
     for (int kh = 0; kh < p.KH; ++kh)
       for (int kw = 0; kw < p.KW; ++kw)
@@ -793,12 +718,7 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_pp(ConvArgs16 p) {
   }
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const h16_t* __restrict__ xb = (const h16_t*)p.x;
   const int nchunks = ntaps * (p.C / BK);
@@ -1088,11 +1008,7 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_rs(ConvArgs16 p) {
   const int tilesN = (p.K + BN - 1) / BN;
   const int nwg = p.ntiles > 0 ? p.ntiles : (int)gridDim.x;
   for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-  int tile;
-  {
-    const int bid = vb, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int tile = xcd_tile(vb, nwg);
   const int mt = tile / tilesN, nt = tile - mt * tilesN;
   const int m0 = p.m_begin + mt * BM, n0 = nt * BN;
   const int prow = lane >> 2;
@@ -1109,9 +1025,10 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_rs(ConvArgs16 p) {
     const int m = m0 - 1 + s;
     const bool mv = (unsigned)m < (unsigned)p.mtot && (j < 2 || prow < 2);
     const int2 ri = p.rowinfo[mv ? m : 0];
-    aoff[j] = (ri.x + 1) * p.xs + kslot * 8 + goff;
-    awc[j] = (ri.y >> 16) * p.xs;
-    amask[j] = mv ? (unsigned)(ri.y & 0xffff) : 0u;
+    const RowGeom g = rowinfo_unpack(ri);
+    aoff[j] = (g.anchor + 1) * p.xs + kslot * 8 + goff;
+    awc[j] = g.W * p.xs;
+    amask[j] = mv ? g.mask : 0u;
   }
   int boff[2];
   bool bvalid[2];
@@ -1123,12 +1040,7 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_rs(ConvArgs16 p) {
   }
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const h16_t* __restrict__ xb = (const h16_t*)p.x;
   const int ngroups = 3 * (p.C / 64);
@@ -1186,9 +1098,9 @@ __global__ __launch_bounds__(512) void conv_igemm_bf16_rs(ConvArgs16 p) {
   for (int i = 0; i < TM; ++i) {
     int m = m0 + wm * 128 + i * 32 + frow;
     m = m < p.mtot ? m : p.mtot - 1;
-    const int y = p.rowinfo[m].y;
-    okm |= (unsigned)((y >> 3) & 1) << i;
-    okm |= (unsigned)((y >> 5) & 1) << (8 + i);
+    const int2& ri = p.rowinfo[m];   // taps (1, 0) and (1, 2) of the 3 x 3
+    okm |= (unsigned)rowinfo_tap(ri, 3) << i;
+    okm |= (unsigned)rowinfo_tap(ri, 5) << (8 + i);
   }
 
   typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -1547,7 +1459,7 @@ static int ml_fwd_g(const void* x, int x_dtype, int x_pitch, const void* w16, vo
                  (groups > 1 && (K / groups) % 128)))
     return UTV2_EARG;
   LevelTab lt;
-  const int M = fill_levels16(lt, nlev, N, H_host, W_host);
+  const int M = fill_levels(lt, nlev, N, H_host, W_host);
   if (!plain && ((int64_t)M * x_pitch >= (1ll << 31) || (int64_t)K * KH * KW * C >= (1ll << 31))) return UTV2_EARG;
   ConvArgs16 a = make_args(x, w16, y, scale, bias, residual, N, C, K, KH, KW, 1, pad, relu, accumulate, M);
   a.lt = lt; a.xs = x_pitch; a.groups = groups; a.ldy = y_pitch; a.gn_part = gn_part; a.rowinfo = (const int2*)rowinfo; a.bits = bits;
@@ -1602,28 +1514,27 @@ int utv2_conv2d_stem_fwd_bf16(const void* xpad16, const void* w16s, void* y, int
 // The per-output-pixel geometry table of the 16-bit convs / weight gradients, built ON THE DEVICE (round 6): until then the host
 // built it with torch CPU ops and copied it over - 0.3-1 s of host time and a synchronising copy for every new canvas, which is every
 // step of the reference recipes (INPUT.MIN_SIZE_TRAIN (400, 1200) "range": a new padded canvas per batch).
-//   rowinfo[m] = {start + n*H*W + (oh*stride - pad)*W + (ow*stride - pad),  (W << 16) | mask of the taps (kh, kw) inside the image}
-// for output pixel m = (n, oh, ow) of an [N, OH, OW] output over an [N, H, W] input whose first pixel has index `start`.
+//   rowinfo[m] = rowinfo_pack(start + n*H*W + (oh*stride - pad)*W + (ow*stride - pad), W, mask of the taps (kh, kw) inside the image)
+// for output pixel m = (n, oh, ow) of an [N, OH, OW] output over an [N, H, W] input whose first pixel has index `start` (the record, the
+// row geometry and the mask rule are conv_geom.h's: what the tile prologues decode for themselves when they get no table).
 __global__ __launch_bounds__(256) void rowinfo_kernel(int2* __restrict__ out, int N, int H, int W, int OH, int OW, int stride, int pad,
                                                       int KH, int KW, long long start) {
   const long long total = (long long)N * OH * OW;
   for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < total; m += (long long)gridDim.x * 256) {
-    const int ow = (int)(m % OW);
+    const int ow = (int)(m % OW);   // (m may exceed 32 bits: split here, then the shared row geometry)
     const long long t = m / OW;
     const int oh = (int)(t % OH), n = (int)(t / OH);
-    const int ih0 = oh * stride - pad, iw0 = ow * stride - pad;
-    int mask = 0;
-    for (int a = 0; a < KH; ++a)
-      for (int b = 0; b < KW; ++b)
-        if (ih0 + a >= 0 && ih0 + a < H && iw0 + b >= 0 && iw0 + b < W) mask |= 1 << (a * KW + b);
-    out[m] = make_int2((int)(start + (long long)n * H * W + (long long)ih0 * W + iw0), (W << 16) | mask);
+    int ih0, iw0;
+    long long pb;
+    nhwc_row_at(n, oh, ow, H, W, stride, pad, pb, ih0, iw0);
+    out[m] = rowinfo_pack((int)(start + pb + (long long)ih0 * W + iw0), W, (int)tap_mask(ih0, iw0, H, W, KH, KW));
   }
 }
 
 int utv2_rowinfo_nhwc(int* out, int N, int H, int W, int OH, int OW, int stride, int pad, int KH, int KW, int64_t start,
                       hipStream_t stream) {
-  if (!out || N < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || stride < 1 || pad < 0 || KH < 1 || KW < 1 || KH * KW > 16 || W >= 32768 ||
-      start < 0 || start + (int64_t)N * H * W >= (1ll << 31))
+  if (!out || N < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || stride < 1 || pad < 0 || KH < 1 || KW < 1 || KH * KW > ROWINFO_MAX_TAPS ||
+      W >= ROWINFO_MAX_W || start < 0 || start + (int64_t)N * H * W >= (1ll << 31))
     return UTV2_EARG;
   int64_t nb = ((int64_t)N * OH * OW + 255) / 256;
   if (nb > 8192) nb = 8192;
@@ -1692,7 +1603,7 @@ int utv2_weight_flip_transpose_bf16_batched(const float* arena, const float* sca
 // LDS rows are 256 B + 64 B pad: the 4 rows x 64 B a 32-lane half reads land on 64 distinct banks.
 //
 // Pixel geometry comes from a per-output-pixel table (no divisions in the loop, any mix of FPN levels / strides):
-//   rowinfo[m] = { anchor = input pixel index of tap (0,0) (may lie outside the image), (W << 16) | tapmask }
+//   rowinfo[m] = rowinfo_pack(anchor = input pixel index of tap (0,0) (may lie outside the image), W, tapmask)   (conv_geom.h)
 // tap (kh,kw) of output pixel m reads input pixel anchor + kh*W + kw iff bit kh*KW+kw of tapmask is set.
 struct Wgrad16Args {
   const void* x;
@@ -1749,12 +1660,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16(Wgrad16Args p) {
   const int dh = tap / p.KW, dw = tap - dh * p.KW;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   const int chunk_begin = split * p.chunks_per_split;
   const int total_chunks = (p.M + BK - 1) / BK;
@@ -1803,9 +1709,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16(Wgrad16Args p) {
     if (q < 2) {
       ra[r] = load8(p.dy, (size_t)m * p.dys + co8, DY16, mok && aok);
     } else {
-      const int W = ri[r].y >> 16;
-      const bool ok = mok && bok && ((ri[r].y >> tap) & 1);
-      rb[r] = load8(p.x, (size_t)(ri[r].x + dh * W + dw) * p.xs + goff + ci, X16, ok);
+      const RowGeom g = rowinfo_unpack(ri[r]);
+      const bool ok = mok && bok && rowinfo_tap(ri[r], tap);
+      rb[r] = load8(p.x, (size_t)(g.anchor + dh * g.W + dw) * p.xs + goff + ci, X16, ok);
     }
   };
   auto store_piece = [&](int buf, int q) {
@@ -1944,12 +1850,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_bf16_pp(Wgrad16Args p) {
   const int dh = tap / p.KW, dw = tap - dh * p.KW;
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   // the split's pixel range in 32-pixel chunks (chunks_per_split counts the lock-step kernel's 64-pixel chunks)
   const int total_chunks = (p.M + BP - 1) / BP;
@@ -1998,9 +1899,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_bf16_pp(Wgrad16Args p) {
       const bool in = (m < p.M) & (chunk < chunk_end);                                                             \
       const h16_t* a0 = dyb + (unsigned)(m * p.K + i0 + choff[q]);                                                 \
       psrc[q] = in ? a0 : zero;                                                                                    \
-      const int W = ri[SET][q].y >> 16;                                                                            \
-      const h16_t* s0 = xb + (unsigned)((ri[SET][q].x + dh * W + dw) * p.xs + ci0 + choff[q]);                     \
-      psrc[2 + q] = (in & (bool)((ri[SET][q].y >> tap) & 1)) ? s0 : zero;                                          \
+      const RowGeom g = rowinfo_unpack(ri[SET][q]);                                                                \
+      const h16_t* s0 = xb + (unsigned)((g.anchor + dh * g.W + dw) * p.xs + ci0 + choff[q]);                       \
+      psrc[2 + q] = (in & (bool)rowinfo_tap(ri[SET][q], tap)) ? s0 : zero;                                         \
     }                                                                                                              \
   }
   auto prep0 = WGP_PREP(0);
@@ -2193,11 +2094,15 @@ __global__ __launch_bounds__(256) void colsum_bf16_partial(const h16_t* __restri
   }
 }
 
+// The three split-K tail reductions, each written ONCE as the work of workgroup `lb` of `nblk` (256 threads): the stand-alone kernels
+// below and the matching `kind` of reduce_slabs_table run these bodies, so a folded tail gives the bits of the launch it replaces
+// (same order of the partial sums) by construction.
+//
 // db[c] (+)= rowscale[c] * sum_b partial[b][c]: 32 channels x 8 row parts per block, four loads in flight, fixed combine order
-__global__ __launch_bounds__(256) void colsum_final_f32(const float* __restrict__ partial, float* __restrict__ db, int nb, int K,
-                                                        int accumulate, const float* __restrict__ rowscale) {
-  __shared__ float red[256];
-  const int c = blockIdx.x * 32 + (threadIdx.x & 31), part = threadIdx.x >> 5;
+// (red: 256 floats of LDS; one workgroup per 32 channels, nblk unused)
+__device__ __forceinline__ void colsum_final_body(float* red, const float* __restrict__ partial, float* __restrict__ db, int nb, int K,
+                                                  int accumulate, const float* __restrict__ rowscale, int lb) {
+  const int c = lb * 32 + (threadIdx.x & 31), part = threadIdx.x >> 5;
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   if (c < K) {
     int b = part;
@@ -2221,12 +2126,11 @@ __global__ __launch_bounds__(256) void colsum_final_f32(const float* __restrict_
 // dst[i] (+)= rowscale[i / rowlen] * sum_k ws[k][i]   (fixed order; rowscale optional: the folded FrozenBN multiplier of
 // the output channel, applied here instead of to the output gradient).  Four elements per thread (16-byte accesses),
 // four independent partial sums over k mod 4 combined in a fixed order: deterministic, and 4 loads in flight per thread.
-__global__ __launch_bounds__(256) void reduce_slabs16_f32(const float* __restrict__ ws, float* __restrict__ dst, size_t n, int splits,
-                                                          int accumulate, const float* __restrict__ rowscale, int rowlen) {
+__device__ __forceinline__ void reduce_slabs_body(const float* __restrict__ ws, float* __restrict__ dst, size_t n, int splits, int accumulate,
+                                                  const float* __restrict__ rowscale, int rowlen, int lb, int nblk) {
   const size_t n4 = n >> 2;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n4; i += stride) {
+  const size_t stride = (size_t)nblk * 256;
+  for (size_t i = (size_t)lb * 256 + threadIdx.x; i < n4; i += stride) {
     f32x4 s[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) s[u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -2248,14 +2152,29 @@ __global__ __launch_bounds__(256) void reduce_slabs16_f32(const float* __restric
 }
 
 // scalar form (bias slabs: n = K, one "row" per element)
+__device__ __forceinline__ void reduce_slabs_scalar_body(const float* __restrict__ ws, float* __restrict__ dst, size_t n, int splits,
+                                                         int accumulate, const float* __restrict__ rowscale, int lb, int nblk) {
+  for (size_t i = (size_t)lb * 256 + threadIdx.x; i < n; i += (size_t)nblk * 256) {
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += ws[(size_t)k * n + i];
+    if (rowscale) s *= rowscale[i];
+    dst[i] = accumulate ? dst[i] + s : s;
+  }
+}
+
+// the stand-alone launches (256 threads per workgroup)
+__global__ __launch_bounds__(256) void colsum_final_f32(const float* __restrict__ partial, float* __restrict__ db, int nb, int K,
+                                                        int accumulate, const float* __restrict__ rowscale) {
+  __shared__ float red[256];
+  colsum_final_body(red, partial, db, nb, K, accumulate, rowscale, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void reduce_slabs16_f32(const float* __restrict__ ws, float* __restrict__ dst, size_t n, int splits,
+                                                          int accumulate, const float* __restrict__ rowscale, int rowlen) {
+  reduce_slabs_body(ws, dst, n, splits, accumulate, rowscale, rowlen, blockIdx.x, gridDim.x);
+}
 __global__ void reduce_slabs16_scalar_f32(const float* __restrict__ ws, float* __restrict__ dst, size_t n, int splits, int accumulate,
                                           const float* __restrict__ rowscale) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < splits; ++k) s += ws[(size_t)k * n + i];
-  if (rowscale) s *= rowscale[i];
-  dst[i] = accumulate ? dst[i] + s : s;
+  reduce_slabs_scalar_body(ws, dst, n, splits, accumulate, rowscale, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2263,7 +2182,7 @@ __global__ void reduce_slabs16_scalar_f32(const float* __restrict__ ws, float* _
 // by its slab reduction (+ a bias reduction): 60-70 dispatches of 5-25 us that sit in their own launch gaps on the weight-gradient
 // lanes.  With a pending table (utv2_conv2d_wgrad_bf16_d) a launch only RECORDS its tail - {slabs, destination, splits, scale} - and
 // utv2_wgrad_fold_flush runs all recorded tails in one kernel: workgroups are dealt to the entries in proportion to their size, and every
-// entry is reduced with exactly the arithmetic (order of the partial sums included) of the kernel it replaces:
+// entry is reduced by the very body (order of the partial sums included) of the kernel it replaces:
 //   kind 0 = reduce_slabs16_f32, kind 1 = reduce_slabs16_scalar_f32, kind 2 = colsum_final_f32  ->  bit-identical gradients.
 #define SLAB_FOLD_MAX 24
 struct SlabFold {
@@ -2286,57 +2205,9 @@ __global__ __launch_bounds__(256) void reduce_slabs_table(SlabFoldTable t) {
     if ((int)blockIdx.x >= t.e[i].blk0) ei = i;
   const SlabFold f = t.e[ei];
   const int lb = (int)blockIdx.x - f.blk0;
-  if (f.kind == 0) {          // == reduce_slabs16_f32
-    const size_t n4 = f.n >> 2;
-    const size_t stride = (size_t)f.nblk * 256;
-    for (size_t i = (size_t)lb * 256 + threadIdx.x; i < n4; i += stride) {
-      f32x4 s[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      int k = 0;
-      for (; k + 4 <= f.splits; k += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s[u] += ((const f32x4*)(f.ws + (size_t)(k + u) * f.n))[i];
-      }
-      for (; k < f.splits; ++k) s[0] += ((const f32x4*)(f.ws + (size_t)k * f.n))[i];
-      f32x4 v = (s[0] + s[1]) + (s[2] + s[3]);
-      if (f.rowscale) {
-        const float r = f.rowscale[(i * 4) / f.rowlen];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= r;
-      }
-      if (f.accumulate) v += ((const f32x4*)f.dst)[i];
-      ((f32x4*)f.dst)[i] = v;
-    }
-  } else if (f.kind == 1) {   // == reduce_slabs16_scalar_f32
-    for (size_t i = (size_t)lb * 256 + threadIdx.x; i < f.n; i += (size_t)f.nblk * 256) {
-      float s = 0.f;
-      for (int k = 0; k < f.splits; ++k) s += f.ws[(size_t)k * f.n + i];
-      if (f.rowscale) s *= f.rowscale[i];
-      f.dst[i] = f.accumulate ? f.dst[i] + s : s;
-    }
-  } else {                    // == colsum_final_f32 (one workgroup per 32 channels; the branch is workgroup-uniform)
-    const int K = (int)f.n, nb = f.splits;
-    const int c = lb * 32 + (threadIdx.x & 31), part = threadIdx.x >> 5;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    if (c < K) {
-      int b = part;
-      for (; b + 24 < nb; b += 32) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s[u] += f.ws[(size_t)(b + 8 * u) * K + c];
-      }
-      for (; b < nb; b += 8) s[0] += f.ws[(size_t)b * K + c];
-    }
-    red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-    __syncthreads();
-    if (part == 0 && c < K) {
-      float v = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v += red[threadIdx.x + 32 * k];
-      if (f.rowscale) v *= f.rowscale[c];
-      f.dst[c] = f.accumulate ? f.dst[c] + v : v;
-    }
-  }
+  if (f.kind == 0) reduce_slabs_body(f.ws, f.dst, f.n, f.splits, f.accumulate, f.rowscale, f.rowlen, lb, f.nblk);
+  else if (f.kind == 1) reduce_slabs_scalar_body(f.ws, f.dst, f.n, f.splits, f.accumulate, f.rowscale, lb, f.nblk);
+  else colsum_final_body(red, f.ws, f.dst, f.splits, (int)f.n, f.accumulate, f.rowscale, lb);   // (the branch is workgroup-uniform)
 }
 
 static int slab_fold_add(SlabFoldTable* t, int kind, const float* ws, float* dst, const float* rowscale, size_t n, int splits, int accumulate,
