@@ -693,6 +693,41 @@ int64_t utv2_gconv3x3_wgrad_workspace_floats(int N, int OH, int OW, int C, int G
 int utv2_gconv3x3_wgrad(const void* x, const void* dy, int op_dtype, float* dw, float* ws, const float* scale, int N, int H, int W,
                         int C, int G, int stride, int OH, int OW, int accumulate, utv2_stream_t stream);
 
+/* ---- BatchNorm2d + ReLU of the FCOS towers (MODEL.FCOS.NORM "BN" / "SyncBN", fcos/fcos.py:262-281; csrc/batchnorm.hip) --------------
+ * x, y, dy, dx: level-first [P, C] matrices of one element type (`dtype`: UTV2_F32 or UTV2_BF16), C % 4 == 0.  Per-channel coefficients
+ * and the per-element arithmetic are fp64, every output is rounded once (16-bit outputs through fp32); a NaN in x is a NaN in y (torch's
+ * ReLU) and its gradient is masked like any y that is not > 0.
+ * A STATISTIC SET s = rows [set_row0[s], set_row0[s] + set_rows[s]) = the rows of FPN level set_level[s] that one forward call of the
+ * reference hands its BatchNorm2d; gamma / beta / running_* / dgamma / dbeta are [nlevels, C] fp32, mean / rstd / scale [nsets, C] fp64.  The set
+ * tables are HOST arrays (at most 16 sets, from the canvas geometry), passed on by value: nothing depends on device data.
+ * All sums are carried in fp64 and reduced in two stages of fixed order without atomics (bit-reproducible):
+ *   stats_partial  partial[chunk][0 | 1][C] = sum x | sum x^2 over chunks of 64 rows (utv2_bn_chunks of them)
+ *   reduce         out[s][0 | 1][C] = the set's chunks added up, divided by set_rows[s] when `divide` (-> [mean, mean of squares])
+ *   finalize       mode 0: mean, var = moments[s][1] - moments[s][0]^2 (in fp64), rstd = 1 / sqrt(var + eps), scale = gamma * rstd; then
+ *                  running_mean += momentum * (mean - running_mean), running_var likewise with var * n / (n - 1), n = set_rows[s] *
+ *                  count_mul (biased_running: with var itself), the sets in order (two sets of a level: two sequential updates);
+ *                  mode 1 (eval): mean / var = the level's running statistics, which are not written.  `moments` may be the mean of
+ *                  several ranks' reduce outputs (count_mul = their number, equal set sizes).  n < 2 in mode 0: UTV2_EARG.
+ *   apply_relu     y = relu(x * scale + shift), shift = beta - mean * scale, evaluated as (x - mean) * scale + beta; one rounding
+ *   bwd_partial    partial[chunk][0 | 1][C] = sum g | sum g * xhat; g = dy * [y > 0], xhat = (x - mean) * rstd; then `reduce`, divide 0
+ *   bwd_apply      dx = gamma * rstd * (g - sums[s][0] / n - xhat * sums[s][1] / n); dgamma[level] += sums[s][1] / count_mul,
+ *                  dbeta[level] += sums[s][0] / count_mul, the sets in order.  `sums` may be the SUM over count_mul ranks. */
+int utv2_bn_chunks(int nsets, const int* set_rows_host);
+int utv2_bn_stats_partial(const void* x, int dtype, double* partial, int64_t P, int C, int nsets, const int* set_row0_host,
+                          const int* set_rows_host, utv2_stream_t stream);
+int utv2_bn_reduce(const double* partial, double* out, int C, int nsets, const int* set_rows_host, int divide, utv2_stream_t stream);
+int utv2_bn_finalize(const double* moments, const float* gamma, float* running_mean, float* running_var, double* mean, double* rstd,
+                     double* scale, int C, int nlevels, int nsets, const int* set_rows_host, const int* set_level_host, double eps,
+                     double momentum, int mode, int count_mul, int biased_running, utv2_stream_t stream);
+int utv2_bn_apply_relu(const void* x, void* y, int dtype, const double* mean, const double* scale, const float* beta, int64_t P, int C,
+                       int nlevels, int nsets, const int* set_row0_host, const int* set_rows_host, const int* set_level_host,
+                       utv2_stream_t stream);
+int utv2_bn_bwd_partial(const void* dy, const void* y, const void* x, int dtype, const double* mean, const double* rstd, double* partial,
+                        int64_t P, int C, int nsets, const int* set_row0_host, const int* set_rows_host, utv2_stream_t stream);
+int utv2_bn_bwd_apply(const void* dy, const void* y, const void* x, void* dx, int dtype, const double* mean, const double* rstd,
+                      const float* gamma, const double* sums, float* dgamma, float* dbeta, int64_t P, int C, int nlevels, int nsets,
+                      const int* set_row0_host, const int* set_rows_host, const int* set_level_host, int count_mul, utv2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

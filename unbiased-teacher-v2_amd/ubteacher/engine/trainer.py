@@ -571,9 +571,19 @@ class _TrainerBase:
                 st["warm"] += 1
                 return self.run_step_full_semisup()
             g = torch.cuda.CUDAGraph()
+            ints = self.model.store.host_counters
+            before = [c.value for c in ints]
             with torch.cuda.graph(g):
                 st["loss"] = self.run_step_full_semisup()
             st["graph"], st["pending"] = g, self._pending_metrics
+            # host integers (BatchNorm's num_batches_tracked) advance in Python, which a replay does not run: the capture advanced them
+            # for its own replay below, later replays repeat the same advance
+            st["host_ints"] = [(c, c.value - b) for c, b in zip(ints, before)]
+        else:
+            if ema_step:
+                self._ema_host_ints(S.EMA_KEEP_RATE)
+            for c, d in st["host_ints"]:
+                c.value += d
         st["graph"].replay()
         self._pending_metrics = st["pending"]        # the captured metric tensors were just rewritten by the replay
         if flush:
@@ -597,6 +607,15 @@ class _TrainerBase:
         ts.touch()
         if m16 is not None:
             ts.mirror16_written()
+        self._ema_host_ints(keep_rate)
+
+    def _ema_host_ints(self, keep_rate):
+        """`num_batches_tracked` of BatchNorm layers (host integers, params.ParamStore.export_host_int): the reference's EMA loop treats
+        the int64 buffer like every other entry (trainer.py:478-481: student * (1 - keep) + teacher * keep, a float32 tensor) and
+        load_state_dict copies the result back into the int64 buffer, which truncates it."""
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        for ct, cs in zip(self.model_teacher.store.host_counters, self.model.store.host_counters):
+            ct.value = int(f32(cs.value) * f32(1 - keep_rate) + f32(ct.value) * f32(keep_rate))
 
     # -- gradient exchange: ONE flat all-reduce (DDP mean semantics) -------------------------------------
     def _setup_grad_sync(self):
@@ -831,7 +850,10 @@ class UBTeacherTrainer(_TrainerBase):
             # gradient per layer instead of two.  Different canvases (zero padding differs) keep the two passes.
             # (SEMISUPNET.PSEUDO_CLS_IGNORE_NEAR reaches the pseudo branch only - trainer.py:340,347 - where the reference never reads
             # the keep_locations it fills, fcos_outputs.py:487-631: it does not change a loss, so it does not constrain the fusion)
-            fuse = (self.fuse_student_passes
+            # (per-level BatchNorm towers, MODEL.FCOS.NORM "BN": one batch with two statistic sets per level, ops.BatchNormReLU.  "SyncBN" on
+            # several ranks keeps the two passes on EVERY rank: its all-reduces per layer and call must come in one order everywhere, and a
+            # rank whose canvases differ cannot fuse)
+            fuse = (self.fuse_student_passes and not (cfg.MODEL.FCOS.NORM == "SyncBN" and self.data_parallel)
                     and self.model.padded_canvas(all_label_data) == self.model.padded_canvas(unlabel_data_q))
             # The student's forward needs the pseudo labels only in its loss kernels: with one student batch the teacher (forward,
             # top-k, decode, NMS, thresholding - the last four latency-bound) runs on a side stream NEXT TO the student's backbone /

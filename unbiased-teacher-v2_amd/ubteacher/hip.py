@@ -76,7 +76,7 @@ _SIGS = _parse_header(HEADER_PATH)
 _PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats",
           "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
           "utv2_coco_eval_workspace_bytes", "utv2_gconv3x3_supported", "utv2_gconv3x3_wgrad_splits",
-          "utv2_gconv3x3_wgrad_workspace_floats"}  # return a value, not a status
+          "utv2_gconv3x3_wgrad_workspace_floats", "utv2_bn_chunks"}  # return a value, not a status
 
 
 _libs = {}
@@ -1622,3 +1622,99 @@ def coco_box_eval(det_boxes, det_scores, det_cls, det_off, gt_boxes, gt_crowd, g
     call("utv2_coco_accumulate", _p(perm2), _p(cat_off), _p(rank), K, D, ctypes.cast(_dbl_arr(rec_thrs), c_p), _p(ws), _p(precision),
          _p(recall), st)
     return precision, recall
+
+
+# ---- BatchNorm2d + ReLU of the FCOS towers (csrc/batchnorm.hip) -------------------------------------------------------------------
+class BnSets:
+    """The statistic sets of one level-first [P, C] activation as the kernels take them: (first row, rows, level) per set, host arrays
+    built once per geometry.  check_training() raises ValueError for a set of one row (torch: "Expected more than 1 value per channel")."""
+    MAX = 16
+
+    def __init__(self, sets, nlevels):
+        sets = [(int(r0), int(n), int(l)) for r0, n, l in sets]
+        if not 1 <= len(sets) <= self.MAX:
+            raise ValueError("BatchNorm: %d statistic sets (1 .. %d are built)" % (len(sets), self.MAX))
+        if any(n < 1 or r0 < 0 or not 0 <= l < nlevels for r0, n, l in sets):
+            raise ValueError("BatchNorm: bad statistic set in %r" % (sets,))
+        self.sets, self.n, self.nlevels = sets, len(sets), int(nlevels)
+        self.row0, self.rows, self.level = _iarr([s[0] for s in sets]), _iarr([s[1] for s in sets]), _iarr([s[2] for s in sets])
+        self.p_row0, self.p_rows, self.p_level = (ctypes.cast(a, c_p) for a in (self.row0, self.rows, self.level))
+        self.end = max(r0 + n for r0, n, _ in sets)
+        self.nchunks = sum((n + 63) // 64 for _, n, _ in sets)     # == utv2_bn_chunks
+
+    def check_training(self, count_mul=1):
+        for _, n, l in self.sets:
+            if n * count_mul < 2:
+                raise ValueError("Expected more than 1 value per channel when training, got %d row in a statistic set of level %d" % (n, l))
+
+
+def _bn_xc(x, sets):
+    P, C = x.shape
+    assert x.is_contiguous() and C % 4 == 0 and sets.end <= P, "BatchNorm: dense [P, C] activation, C % 4 == 0, sets inside it"
+    return P, C
+
+
+def bn_stats(x, sets, partial_only=False):
+    """-> moments [S, 2, C] fp64 = per (set, channel) [mean, mean of squares] of x (fp32 or the library's 16-bit type, as stored); the
+    first stage's per-chunk sums [chunks, 2, C] with partial_only"""
+    P, C = _bn_xc(x, sets)
+    assert sets.nchunks == load().utv2_bn_chunks(sets.n, sets.p_rows)
+    partial = torch.empty((sets.nchunks, 2, C), dtype=torch.float64, device=x.device)
+    call("utv2_bn_stats_partial", _p(x), _dt(x), _p(partial), P, C, sets.n, sets.p_row0, sets.p_rows, _stream())
+    return partial if partial_only else bn_reduce(partial, sets, divide=True)
+
+
+def bn_reduce(partial, sets, divide):
+    """second stage of both directions: the per-chunk sums of every set added up in a fixed order (divide: and divided by its rows)"""
+    C = partial.shape[2]
+    assert partial.dtype == torch.float64 and tuple(partial.shape) == (sets.nchunks, 2, C)
+    out = torch.empty((sets.n, 2, C), dtype=torch.float64, device=partial.device)
+    call("utv2_bn_reduce", _p(partial), _p(out), C, sets.n, sets.p_rows, int(bool(divide)), _stream())
+    return out
+
+
+def bn_finalize(moments, gamma, running_mean, running_var, sets, eps=1e-5, momentum=0.1, training=True, count_mul=1, biased_running=False):
+    """-> (mean, rstd, scale) [S, C] fp64.  training: from `moments` [S, 2, C] fp64 (bn_stats, or the mean of count_mul ranks' moments),
+    and the running statistics [L, C] are updated set by set in order; eval: from the running statistics, nothing is written."""
+    L, C = gamma.shape
+    assert L == sets.nlevels and tuple(running_mean.shape) == tuple(running_var.shape) == (L, C)
+    assert all(t.dtype == torch.float32 for t in (gamma, running_mean, running_var))
+    if training:
+        sets.check_training(count_mul)
+        assert moments.dtype == torch.float64 and tuple(moments.shape) == (sets.n, 2, C)
+    mean, rstd, scale = (torch.empty((sets.n, C), dtype=torch.float64, device=gamma.device) for _ in range(3))
+    call("utv2_bn_finalize", _p(moments) if training else None, _p(gamma), _p(running_mean), _p(running_var), _p(mean), _p(rstd), _p(scale),
+         C, L, sets.n, sets.p_rows, sets.p_level, float(eps), float(momentum), 0 if training else 1, int(count_mul), int(bool(biased_running)),
+         _stream())
+    return mean, rstd, scale
+
+
+def bn_apply_relu(x, mean, scale, beta, sets):
+    """y = relu((x - mean[set]) * scale[set] + beta[level]) in x's element type"""
+    P, C = _bn_xc(x, sets)
+    assert tuple(mean.shape) == tuple(scale.shape) == (sets.n, C) and tuple(beta.shape) == (sets.nlevels, C)
+    y = torch.empty_like(x)
+    call("utv2_bn_apply_relu", _p(x), _p(y), _dt(x), _p(mean), _p(scale), _p(beta), P, C, sets.nlevels, sets.n, sets.p_row0, sets.p_rows,
+         sets.p_level, _stream())
+    return y
+
+
+def bn_bwd_sums(dy, y, x, mean, rstd, sets):
+    """first backward stage -> sums [S, 2, C] fp64 = per (set, channel) [sum g, sum g * xhat], g = dy * [y > 0]"""
+    P, C = _bn_xc(x, sets)
+    assert dy.is_contiguous() and y.is_contiguous() and tuple(dy.shape) == tuple(y.shape) == (P, C)
+    partial = torch.empty((sets.nchunks, 2, C), dtype=torch.float64, device=x.device)
+    call("utv2_bn_bwd_partial", _p(dy), _p(y), _p(x), _same_dt(dy, y, x), _p(mean), _p(rstd), _p(partial), P, C, sets.n, sets.p_row0, sets.p_rows,
+         _stream())
+    return bn_reduce(partial, sets, divide=False)
+
+
+def bn_bwd_apply(dy, y, x, mean, rstd, gamma, sums, dgamma, dbeta, sets, count_mul=1):
+    """second backward stage -> dx; adds the parameter gradients into dgamma / dbeta [L, C].  `sums`: bn_bwd_sums, or their sum over
+    count_mul ranks"""
+    P, C = _bn_xc(x, sets)
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (sets.n, 2, C) and tuple(gamma.shape) == tuple(dgamma.shape) == tuple(dbeta.shape)
+    dx = torch.empty_like(x)
+    call("utv2_bn_bwd_apply", _p(dy), _p(y), _p(x), _p(dx), _same_dt(dy, y, x), _p(mean), _p(rstd), _p(gamma), _p(sums), _p(dgamma), _p(dbeta),
+         P, C, sets.nlevels, sets.n, sets.p_row0, sets.p_rows, sets.p_level, int(count_mul), _stream())
+    return dx

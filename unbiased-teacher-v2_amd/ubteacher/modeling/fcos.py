@@ -266,7 +266,14 @@ class FCOSHead:
 
     def __init__(self, cfg, store, in_channels, prefix):
         fc = cfg.MODEL.FCOS
-        assert fc.NORM == "GN", "only the GN towers of the shipped configs are built"
+        # fcos/fcos.py:239-283: "GN" (every shipped YAML), "BN" (one BatchNorm2d per FPN level behind each tower conv), "SyncBN" (the same
+        # with Detectron2's NaiveSyncBatchNorm) and "none" (conv + ReLU)
+        if fc.NORM not in ("GN", "BN", "SyncBN", "none"):
+            raise NotImplementedError("MODEL.FCOS.NORM %r (built: 'GN', 'BN', 'SyncBN', 'none')" % (fc.NORM,))
+        self.norm = fc.NORM
+        self.training = True                 # BN towers: batch statistics (True) or the running ones (eval: the teacher, Trainer.test)
+        self.bn_counter = ops.HostCounter()  # num_batches_tracked of every BatchNorm of this head
+        self.bn_layers = []
         assert not fc.REG_DISCRETE or fc.REG_MAX == 16, "the discrete (GFocal) head is built for REG_MAX 16"
         # REG_DISCRETE False (the config default; plain FCOS, fcos/fcos.py:294-297,363-364): bbox_pred is a 256 -> 4 conv followed by
         # Scale and ReLU.  Fused row [ltrb 4 | std 4 | ctr 1 | pad 7]; conv epilogue and Scale are the discrete head's, the ReLU is taken
@@ -291,21 +298,25 @@ class FCOSHead:
         # two gradients of the FPN feature are summed inside depth 0's dgrad K loop instead of by an add pass.
         self.paired = (fc.NUM_CLS_CONVS == fc.NUM_BOX_CONVS and fc.NUM_SHARE_CONVS == 0 and fc.NUM_CLS_CONVS > 0
                        and os.environ.get("UTV2_PAIR_TOWERS", "1") != "0")      # 0: two separate chains (A/B knob; another arena layout)
+        step = 2 if self.norm == "none" else 3      # "none": the reference's Sequential has no norm slot (conv keys _tower.{2i})
         if self.paired:
             n = fc.NUM_CLS_CONVS
             ws = []
             layers = []
             for i in range(n):
-                pc, pb = "%s.cls_tower.%d" % (prefix, 3 * i), "%s.bbox_tower.%d" % (prefix, 3 * i)
+                pc, pb = "%s.cls_tower.%d" % (prefix, step * i), "%s.bbox_tower.%d" % (prefix, step * i)
                 w = store.new((2 * C, 9 * C), "decay", None)
                 w.export(pc + ".weight", lambda t: t[:C].view(C, 3, 3, C).permute(0, 3, 1, 2))
                 w.export(pb + ".weight", lambda t: t[C:].view(C, 3, 3, C).permute(0, 3, 1, 2))
                 ws.append(w)
                 b = store.new((2 * C,), "decay", lambda t: t.zero_())
                 b.export(pc + ".bias", lambda t: t[:C]).export(pb + ".bias", lambda t: t[C:])
-                conv = ops.Conv(w, C, 2 * C, 3, 1, 1, bias=b, groups=1 if i == 0 else 2)
+                conv = ops.Conv(w, C, 2 * C, 3, 1, 1, bias=b, groups=1 if i == 0 else 2, relu=self.norm == "none")
                 conv.defer_wgrad = True     # see ops.defer_tower_wgrads (UTV2_DEFER_TOWER_WGRAD)
                 gc, gb = "%s.cls_tower.%d" % (prefix, 3 * i + 1), "%s.bbox_tower.%d" % (prefix, 3 * i + 1)
+                if self.norm != "GN":
+                    layers.append((conv, self._batchnorm(store, ((gc, 0, C), (gb, C, 2 * C)), 2 * C)))
+                    continue
                 ga = store.new((2 * C,), "nodecay", lambda t: t.fill_(1.0))
                 ga.export(gc + ".weight", lambda t: t[:C]).export(gb + ".weight", lambda t: t[C:])
                 be = store.new((2 * C,), "nodecay", lambda t: t.zero_())
@@ -322,12 +333,6 @@ class FCOSHead:
                         w.t[half * C:(half + 1) * C].normal_(0.0, 0.01)
             ws[0].init = init_all
             self.towers["pair"] = layers
-            order = []
-            for name in ("cls", "bbox"):
-                for i in range(n):
-                    order += ["%s.%s_tower.%d.weight" % (prefix, name, 3 * i), "%s.%s_tower.%d.bias" % (prefix, name, 3 * i),
-                              "%s.%s_tower.%d.weight" % (prefix, name, 3 * i + 1), "%s.%s_tower.%d.bias" % (prefix, name, 3 * i + 1)]
-            store.order_keys(order)
         for name, nconv in (("cls", fc.NUM_CLS_CONVS), ("bbox", fc.NUM_BOX_CONVS), ("share", fc.NUM_SHARE_CONVS)):
             if self.paired:
                 self.towers[name] = []
@@ -335,17 +340,35 @@ class FCOSHead:
 
             layers = []
             for i in range(nconv):
-                p = "%s.%s_tower.%d" % (prefix, name, 3 * i)
+                p = "%s.%s_tower.%d" % (prefix, name, step * i)
                 w = store.new((C, 9 * C), "decay", lambda t: t.normal_(0.0, 0.01)).export(p + ".weight", _nchw_view(C, C, 3))
                 b = store.new((C,), "decay", lambda t: t.zero_()).export(p + ".bias")
-                conv = ops.Conv(w, C, C, 3, 1, 1, bias=b)
+                conv = ops.Conv(w, C, C, 3, 1, 1, bias=b, relu=self.norm == "none")
                 pg = "%s.%s_tower.%d" % (prefix, name, 3 * i + 1)
+                if self.norm != "GN":
+                    layers.append((conv, self._batchnorm(store, ((pg, 0, C),), C)))
+                    continue
                 ga = store.new((C,), "nodecay", lambda t: t.fill_(1.0)).export(pg + ".weight")
                 be = store.new((C,), "nodecay", lambda t: t.zero_()).export(pg + ".bias")
                 layers.append(ops.pair_conv_gn(conv, ops.GroupNormReLU(ga, be, 32, 1e-5, True)))
                 if i > 0:
                     ops.chain_gn_conv(layers[i - 1][1], conv)
             self.towers[name] = layers
+        if self.paired or self.norm in ("BN", "SyncBN"):
+            # the reference's module order (state_dict() of its Sequential towers: cls, bbox, share; conv, then the norm slot)
+            order = []
+            for name, nconv in (("cls", fc.NUM_CLS_CONVS), ("bbox", fc.NUM_BOX_CONVS), ("share", fc.NUM_SHARE_CONVS)):
+                for i in range(nconv):
+                    order += ["%s.%s_tower.%d.weight" % (prefix, name, step * i), "%s.%s_tower.%d.bias" % (prefix, name, step * i)]
+                    pn = "%s.%s_tower.%d" % (prefix, name, 3 * i + 1)
+                    if self.norm == "GN":
+                        order += [pn + ".weight", pn + ".bias"]
+                    elif self.norm != "none":
+                        order += ["%s.%d.%s" % (pn, l, k) for l in range(self.num_levels)
+                                  for k in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+            store.order_keys(order)
+        if self.bn_layers:
+            self.bn_layers[0].count_calls = True
         nc = self.num_classes
         prior = fc.PRIOR_PROB
         bias_value = -math.log((1 - prior) / prior)
@@ -390,23 +413,60 @@ class FCOSHead:
             self.scales = [store.new((1,), "decay", lambda t: t.fill_(1.0)).export("%s.scales.%d.scale" % (prefix, l))
                            for l in range(self.num_levels)]
 
-    def __call__(self, big, meta):
+    def _batchnorm(self, store, halves, width):
+        """the norm slot of one tower depth under NORM "BN" / "SyncBN": per-level BatchNorm2d modules as [L, width] matrices (gamma, beta:
+        "nodecay", 1 / 0; running_mean, running_var: "buffer", 0 / 1 - the EMA's single launch over the arena averages them with the
+        weights, as the reference's EMA does).  halves: (key prefix, first column, end column) per reference tower that owns columns of
+        this layer (paired towers: two).  "none": no norm op (the conv applies the ReLU) -> None."""
+        if self.norm == "none":
+            return None
+        L = self.num_levels
+        ga = store.new((L, width), "nodecay", lambda t: t.fill_(1.0))
+        be = store.new((L, width), "nodecay", lambda t: t.zero_())
+        rm = store.new((L, width), "buffer", lambda t: t.zero_())
+        rv = store.new((L, width), "buffer", lambda t: t.fill_(1.0))
+        for p, c0, c1 in halves:
+            for l in range(L):
+                def view(t, l=l, c0=c0, c1=c1):
+                    return t[l, c0:c1]
+                for h, k in ((ga, "weight"), (be, "bias"), (rm, "running_mean"), (rv, "running_var")):
+                    h.export("%s.%d.%s" % (p, l, k), view)
+                store.export_host_int("%s.%d.num_batches_tracked" % (p, l), self.bn_counter)
+        bn = ops.BatchNormReLU(ga, be, rm, rv, self.bn_counter, 1e-5, 0.1, sync=self.norm == "SyncBN")
+        self.bn_layers.append(bn)
+        return bn
+
+    def train(self, mode=True):
+        self.training = mode
+        for bn in self.bn_layers:
+            bn.training = mode
+
+    def _layer(self, conv, norm, t, meta, calls):
+        t = conv(t, meta=meta)
+        if norm is None:                      # NORM "none"
+            return t
+        if self.norm == "GN":
+            return norm(t, meta)
+        return norm(t, meta, calls)
+
+    def __call__(self, big, meta, calls=None):
         """big: level-first [P, C] features of all levels; ONE launch per conv for all levels.
+        calls (BN towers): images per forward call of the reference in this batch, in order (fused student pass: [labeled, unlabeled]).
         Returns dict(logits [P,80], box [P,80], meta)."""
         t = big
         if self.paired:
             for conv, gn in self.towers["pair"]:
-                t = gn(conv(t, meta=meta), meta)          # [P, 2C]: cls | bbox
+                t = self._layer(conv, gn, t, meta, calls)  # [P, 2C]: cls | bbox
             tc, tb = ops.split_cols(t)                    # column-half views (row pitch 2C): the prediction convs read them in place
         else:
             for conv, gn in self.towers["share"]:
-                t = gn(conv(t, meta=meta), meta)
+                t = self._layer(conv, gn, t, meta, calls)
             tc = t
             for conv, gn in self.towers["cls"]:
-                tc = gn(conv(tc, meta=meta), meta)
+                tc = self._layer(conv, gn, tc, meta, calls)
             tb = t
             for conv, gn in self.towers["bbox"]:
-                tb = gn(conv(tb, meta=meta), meta)
+                tb = self._layer(conv, gn, tb, meta, calls)
         logits = self.cls_logits(tc, meta=meta)
         box = self.box_head(tb, meta=meta, colscale_handle=self.scales)
         out = {"logits": logits, "box": box, "meta": meta}
@@ -777,6 +837,7 @@ class FCOS:
     def train(self, mode=True):
         self.training = mode
         self.fcos_outputs.training = mode
+        self.fcos_head.train(mode)
 
     def forward(self, image_sizes, features, gt_instances=None, output_raw=False, nms_method="cls_n_ctr",
                 ignore_near=False, branch="labeled"):
@@ -828,7 +889,9 @@ class FCOS:
         feats = [features[f] for f in self.in_features]
         level_hw = [(f.shape[1], f.shape[2]) for f in feats]
         big, meta = features["_levelfirst"]
-        head_out = self.fcos_head(big, meta)
+        # the reference runs the labeled and the unlabeled images as two forward calls (engine/trainer.py:320-348): per-level BatchNorm
+        # towers take their statistics per call (two statistic sets per level, labeled first); per-image norms do not care
+        head_out = self.fcos_head(big, meta, calls=(n_labeled, meta.N - n_labeled) if 0 < n_labeled < meta.N else None)
         return dict(head_out=head_out, level_hw=level_hw, n_labeled=n_labeled, gt_labeled=gt_labeled, N=meta.N, device=big.device)
 
     def forward_joint_finish(self, ctx, gt_unlabeled, loss_weights=None):

@@ -1108,6 +1108,106 @@ class _GNFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+class HostCounter:
+    """`num_batches_tracked` of every BatchNorm of one model: the number of training forward calls so far, a host integer (each of the
+    reference's per-level BatchNorm2d modules is called once per forward call, so they all hold the same count)."""
+
+    def __init__(self):
+        self.value = 0
+
+
+class BatchNormReLU:
+    """nn.BatchNorm2d per FPN level + ReLU (MODEL.FCOS.NORM "BN" / "SyncBN", fcos/fcos.py:262-281 through ModuleListDial) on a level-first
+    [P, C] activation: gamma / beta / running_mean / running_var are [L, C] handles, row l = the module of level l.
+    `calls` = images per forward call of the reference that the batch holds, in call order (a fused student pass: [labeled, unlabeled];
+    anything else: [N]): each (level, call) is one STATISTIC SET, the rows of that level's BatchNorm2d in that call.  Two sets of a
+    level update its running statistics one after the other.  Eval mode (`training` False; the teacher, Trainer.test) normalises with
+    the running statistics and writes none.
+    sync ("SyncBN", [D2-recall] NaiveSyncBatchNorm of Detectron2 v0.6): with more than one rank, in training, the ranks' [mean, mean of
+    squares] are averaged by one all-reduce per layer (equal per-rank batch sizes assumed), var = meansqr - mean^2, the running variance
+    takes this BIASED variance, and the backward all-reduces [sum g, sum g * xhat]; with one rank or in eval mode it is plain BN."""
+
+    def __init__(self, gamma, beta, running_mean, running_var, counter, eps=1e-5, momentum=0.1, sync=False):
+        self.gamma, self.beta, self.running_mean, self.running_var = gamma, beta, running_mean, running_var
+        self.counter, self.eps, self.momentum, self.sync = counter, eps, momentum, sync
+        self.training = True
+        self.count_calls = False    # one layer of the model counts the forward calls (num_batches_tracked)
+        self._sets = {}
+
+    def sets(self, meta, calls):
+        calls = tuple(int(n) for n in (calls if calls is not None else (meta.N,)))
+        key = (meta.N, tuple(meta.level_hw), calls)
+        st = self._sets.get(key)
+        if st is None:
+            if sum(calls) != meta.N or min(calls) < 1:
+                raise ValueError("BatchNorm: forward calls of %r images in a batch of %d" % (calls, meta.N))
+            rows = []
+            for l, ((h, w), (r0, _)) in enumerate(zip(meta.level_hw, meta.rows)):
+                i0 = 0
+                for n in calls:
+                    rows.append((r0 + i0 * h * w, n * h * w, l))
+                    i0 += n
+            st = self._sets[key] = hip.BnSets(rows, len(meta.level_hw))
+        return st
+
+    def world(self):
+        from .utils import comm
+        return comm.get_world_size() if (self.sync and self.training) else 1
+
+    def __call__(self, x, meta, calls=None):
+        st = self.sets(meta, calls)
+        if self.training:
+            st.check_training(self.world())   # from the geometry, before any launch
+            if self.count_calls:
+                self.counter.value += len(calls) if calls is not None else 1
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if torch.is_grad_enabled() and self.training:
+            return _BNFn.apply(x, hook(x.device), self, st)
+        return self._fwd(x, st)[0]
+
+    def _fwd(self, x, st):
+        if not self.training:
+            mean, rstd, scale = hip.bn_finalize(None, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
+                                                training=False)
+            return hip.bn_apply_relu(x, mean, scale, self.beta.t, st), mean, rstd
+        moments = hip.bn_stats(x, st)
+        W = self.world()
+        if W > 1:   # [D2-recall] NaiveSyncBatchNorm: all-reduce of [mean, meansqr] / world; here in fp64, all sets of the layer at once
+            from .utils import comm
+            moments = comm.reduce_sum(moments) / W
+        mean, rstd, scale = hip.bn_finalize(moments, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
+                                            training=True, count_mul=W, biased_running=W > 1)
+        return hip.bn_apply_relu(x, mean, scale, self.beta.t, st), mean, rstd
+
+
+class _BNFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, hk, layer, st):
+        y, mean, rstd = layer._fwd(x, st)
+        ctx.layer, ctx.st, ctx.world = layer, st, layer.world()
+        if GRAD_SYNC[0] is not None:
+            GRAD_SYNC[0].on_forward(_sync_handles(layer))
+        ctx.save_for_backward(x, y, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        layer, st, W = ctx.layer, ctx.st, ctx.world
+        x, y, mean, rstd = ctx.saved_tensors
+        dy = dy.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        sums = hip.bn_bwd_sums(dy, y, x, mean, rstd, st)
+        if W > 1:   # [D2-recall] the backward of NaiveSyncBatchNorm's differentiable all-reduce: the ranks' sums added, / world inside
+            from .utils import comm
+            sums = comm.reduce_sum(sums)
+        dx = hip.bn_bwd_apply(dy, y, x, mean, rstd, layer.gamma.t, sums, layer.gamma.g, layer.beta.g, st, count_mul=W)
+        if GRAD_SYNC[0] is not None:
+            GRAD_SYNC[0].on_backward_done(_sync_handles(layer))
+        return dx, None, None, None
+
+
 class _UpAddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lateral, top):

@@ -139,6 +139,16 @@ class ParamStore:
         self.handles = []
         self.finalized = False
         self.key_orders = []   # lists of state_dict keys whose RELATIVE order is fixed (see order_keys)
+        self.host_counters = []   # distinct host-integer state objects (an int `.value` each): see export_host_int
+        self.host_int_keys = {}   # state_dict key -> (its counter, number of handles declared before the key)
+
+    def export_host_int(self, key, counter):
+        """state that is a host integer (BatchNorm's `num_batches_tracked`): state_dict() shows `counter.value` as an int64 scalar under
+        `key`, placed after the exports of the handles declared so far; load_state_dict() reads it when the checkpoint has the key and
+        never reports it missing."""
+        if not any(c is counter for c in self.host_counters):
+            self.host_counters.append(counter)
+        self.host_int_keys[key] = (counter, len(self.handles))
 
     def order_keys(self, keys):
         """state_dict() lists keys in handle-creation order; handles that fuse tensors of several reference modules (the paired FCOS
@@ -226,8 +236,12 @@ class ParamStore:
     # ---- state_dict surface ------------------------------------------------------------
     def state_dict(self):
         items = []
-        for h in self.handles:
-            for key, fn in h.exports:
+        ints, hi = list(self.host_int_keys.items()), 0      # in declaration order, positions ascending
+        for i, h in enumerate(self.handles + [None]):
+            while hi < len(ints) and ints[hi][1][1] <= i:
+                items.append((ints[hi][0], torch.tensor(int(ints[hi][1][0].value), dtype=torch.int64)))
+                hi += 1
+            for key, fn in (h.exports if h is not None else ()):
                 items.append((key, h.t if fn is None else fn(h.t)))
         for order in self.key_orders:
             pos = {k: i for i, (k, _) in enumerate(items)}
@@ -247,7 +261,8 @@ class ParamStore:
 
     def load_state_dict(self, sd, strict=True):
         mine = self.state_dict()
-        missing = [k for k in mine if k not in sd]
+        host = self.host_int_keys
+        missing = [k for k in mine if k not in sd and k not in host]
         unexpected = [k for k in sd if k not in mine]
         if strict and (missing or unexpected):
             raise RuntimeError("load_state_dict: missing %s unexpected %s" % (missing[:5], unexpected[:5]))
@@ -259,6 +274,9 @@ class ParamStore:
             for k, v in mine.items():
                 if k in sd:
                     src = sd[k]
+                    if k in host:
+                        host[k][0].value = int(src)
+                        continue
                     if tuple(src.shape) != tuple(v.shape):
                         raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(v.shape)))
                     src = src.to(device=v.device, dtype=v.dtype)
