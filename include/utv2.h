@@ -260,6 +260,20 @@ int utv2_groupnorm_relu_seg_bwd(const void* dy, const void* y, const void* x, co
 int utv2_groupnorm_seg_bwd_p64(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,
                                float* dgamma, float* dbeta, float* ws, int nseg, const int* seg_rows_host, int C, int G,
                                const float* part64, float* colsum_part, utv2_stream_t stream);
+/* GroupNorm (+ ReLU) over ROIS (csrc/groupnorm_roi.hip; the conv box head, Detectron2 FastRCNNConvFCHead with NORM "GN"): x, y dense
+ * [R][HW][C] of `dtype`, statistics per (ROI, group) into mean, rstd fp32 [R][G]; one workgroup per ROI, one pass over the tensor.
+ * 1 <= HW <= 196, C % 4 == 0, C <= 1024, C % G == 0, (C / G) % 4 == 0, every pointer 16-byte aligned; R == 0: nothing is launched.
+ * The mean, then the sum of squares of x - mean (centred; biased variance, eps inside the square root), all fp32; the ReLU acts on the
+ * fp32 value before the rounding to `dtype`. */
+int utv2_groupnorm_roi_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int R, int HW, int C,
+                           int G, float eps, int relu, int dtype, utv2_stream_t stream);
+/* dx written; dgamma / dbeta (fp32 [C]) accumulated (+=) from per-workgroup column sums by a second launch in a fixed order (no
+ * atomics: bit-identical from run to run).  The ReLU mask is recomputed from x with the forward's expression.
+ * ws: utv2_groupnorm_roi_workspace_floats(R, C) floats. */
+int64_t utv2_groupnorm_roi_workspace_floats(int R, int C);
+int utv2_groupnorm_roi_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                           void* dx, float* dgamma, float* dbeta, float* ws, int R, int HW, int C, int G, int relu, int dtype,
+                           utv2_stream_t stream);
 /* db[c] (+)= sum_b partial[b][c], partial fp32 [nb][K] (the colsum_part above; fixed summation order) */
 int utv2_colsum_partials(const float* partial, float* db, int nb, int K, int accumulate, utv2_stream_t stream);
 

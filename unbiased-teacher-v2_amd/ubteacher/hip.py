@@ -76,7 +76,7 @@ _SIGS = _parse_header(HEADER_PATH)
 _PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats",
           "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
           "utv2_coco_eval_workspace_bytes", "utv2_gconv3x3_supported", "utv2_gconv3x3_wgrad_splits",
-          "utv2_gconv3x3_wgrad_workspace_floats", "utv2_bn_chunks"}  # return a value, not a status
+          "utv2_gconv3x3_wgrad_workspace_floats", "utv2_bn_chunks", "utv2_groupnorm_roi_workspace_floats"}  # return a value, not a status
 
 
 _libs = {}
@@ -1457,6 +1457,31 @@ def groupnorm_seg_bwd_p64(g, x2d, seg_rows, mean, rstd, gamma, dgamma, dbeta, G,
     call("utv2_groupnorm_seg_bwd_p64", _p(g), _p(x2d), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), _p(ws), S,
          ctypes.cast(sr, c_p), C, G, _p(part64), _p(part), _stream())
     return (dx, part) if want_colsum else dx
+
+
+def groupnorm_roi_fwd(x, gamma, beta, G=32, eps=1e-5, relu=True):
+    """GroupNorm (+ ReLU) with statistics per (ROI, group): x dense [R, ..., C] (NHWC ROIs, fp32 or the library's 16-bit type), every
+    ROI one workgroup's tile (utv2_groupnorm_roi_fwd).  -> y, mean [R, G], rstd [R, G]"""
+    R, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (R * C) if R else 1
+    y = torch.empty_like(x)
+    mean = torch.empty((R, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((R, G), dtype=torch.float32, device=x.device)
+    call("utv2_groupnorm_roi_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), R, HW, C, G, float(eps), int(relu), _dt(x),
+         _stream())
+    return y, mean, rstd
+
+
+def groupnorm_roi_bwd(dy, x, mean, rstd, gamma, beta, dgamma, dbeta, G=32, relu=True):
+    """-> dx; dgamma / dbeta (fp32 [C]) are accumulated (+=), bit-identically from run to run; the ReLU mask is recomputed from x"""
+    R, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (R * C) if R else 1
+    assert tuple(dy.shape) == tuple(x.shape)
+    dx = torch.empty_like(x)
+    ws = workspace(load().utv2_groupnorm_roi_workspace_floats(R, C), x.device, "gn_roi")
+    call("utv2_groupnorm_roi_bwd", _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx), _p(dgamma), _p(dbeta), _p(ws), R, HW, C,
+         G, int(relu), _same_dt(dy, x), _stream())
+    return dx
 
 
 # ---- two-crop data path: Pillow-exact image arithmetic on uint8 [H][W][3] device tensors (csrc/augment.hip) ----------------------------

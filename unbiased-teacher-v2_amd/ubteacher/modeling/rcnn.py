@@ -22,7 +22,7 @@ from .. import hip, ops
 from ..d2.registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, ROI_HEADS_REGISTRY
 from ..d2.structures import Boxes, Instances
 from .arena_model import ArenaModel
-from .backbone import _nchw_view, _xavier_init
+from .backbone import _msra_init, _nchw_view, _xavier_init
 from .fcos import PaddedBoxes
 
 SCALE_CLAMP = math.log(1000.0 / 16)
@@ -793,8 +793,19 @@ class StandardROIHeadsPseudoLab:
         if not isinstance(bh.POOLER_SAMPLING_RATIO, int) or bh.POOLER_SAMPLING_RATIO < 0:
             raise ValueError("MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO must be an integer >= 0, got %r" % (bh.POOLER_SAMPLING_RATIO,))
         if bh.NUM_CONV != 0:
-            raise NotImplementedError("MODEL.ROI_BOX_HEAD.NUM_CONV %r: the conv layers of FastRCNNConvFCHead are not built, only NUM_CONV 0 "
-                                      "(fully connected layers on the pooled features)" % (bh.NUM_CONV,))
+            # the conv layers of FastRCNNConvFCHead are built in the form Detectron2's recipes use them: with GroupNorm ("4conv1fc")
+            if bh.NUM_CONV < 0 or bh.NORM == "":
+                raise NotImplementedError("MODEL.ROI_BOX_HEAD.NUM_CONV %r with NORM %r: the conv layers of FastRCNNConvFCHead are built with "
+                                          "NORM \"GN\" only (or NUM_CONV 0: fully connected layers on the pooled features)"
+                                          % (bh.NUM_CONV, bh.NORM))
+            if bh.NORM != "GN":
+                raise NotImplementedError("MODEL.ROI_BOX_HEAD.NORM %r: the conv box head is built with \"GN\" only" % (bh.NORM,))
+            if bh.NUM_FC == 0:
+                raise NotImplementedError("MODEL.ROI_BOX_HEAD.NUM_FC 0 with NUM_CONV %d: the predictors would read a [CONV_DIM, S, S] feature, "
+                                          "whose layout has no export; at least one fully connected layer is needed" % (bh.NUM_CONV,))
+            if bh.CONV_DIM % 32 or (bh.CONV_DIM // 32) % 4:
+                raise NotImplementedError("MODEL.ROI_BOX_HEAD.CONV_DIM %r: GroupNorm(32) of the conv box head needs a multiple of 128 "
+                                          "(channels per group a multiple of 4)" % (bh.CONV_DIM,))
         self.pooler_type, self.sampling_ratio = bh.POOLER_TYPE, bh.POOLER_SAMPLING_RATIO
         self.num_classes = rh.NUM_CLASSES
         self.batch_size_per_image = rh.BATCH_SIZE_PER_IMAGE
@@ -802,6 +813,18 @@ class StandardROIHeadsPseudoLab:
         self.iou_threshold = rh.IOU_THRESHOLDS[0]
         self.proposal_append_gt = rh.PROPOSAL_APPEND_GT
         C, S, FC = in_channels, self.res, bh.FC_DIM
+        # D2 FastRCNNConvFCHead's conv layers (NORM "GN"): Conv2d(3x3, pad 1, no bias) -> GroupNorm(32) -> ReLU on the [R, S, S, C] RoIAlign
+        # output; construction (= initialisation) order conv1..n, then the fcs
+        self.convs = []
+        for i in range(bh.NUM_CONV):
+            p, K = "%s.box_head.conv%d" % (prefix, i + 1), bh.CONV_DIM
+            w = store.new((K, 9 * C), "decay", _msra_init(K, C, 3))     # rows [K][3][3][C]
+            w.export(p + ".weight", _nchw_view(K, C, 3),
+                     load=lambda t, src, K=K, C=C: t.view(K, 3, 3, C).copy_(src.permute(0, 2, 3, 1)))
+            ga = store.new((K,), "nodecay", lambda t: t.fill_(1.0)).export(p + ".norm.weight")
+            be = store.new((K,), "nodecay", lambda t: t.zero_()).export(p + ".norm.bias")
+            self.convs.append((ops.Conv(w, C, K, 3, 1, 1), ops.RoiGroupNormReLU(ga, be, 32, 1e-5, True)))
+            C = K
         self.fcs = []
         dim_in = C * S * S
         for i in range(bh.NUM_FC):
@@ -884,6 +907,8 @@ class StandardROIHeadsPseudoLab:
         batch = torch.arange(N, device=rois.device, dtype=torch.int32)[:, None].expand(N, P).reshape(-1).contiguous()
         x = ops.roi_align(feats, self.scales, self.min_level, rois, batch, valid.reshape(-1).contiguous(), self.res, rois_per_image=P,
                           fanin=fanin, pooler=self.pooler_type, sampling_ratio=self.sampling_ratio)
+        for conv, norm in self.convs:
+            x = norm(conv(x))
         x = x.view(x.shape[0], 1, 1, -1)
         for fc in self.fcs:
             x = fc(x)

@@ -1108,6 +1108,42 @@ class _GNFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+class RoiGroupNormReLU:
+    """GroupNorm (+ ReLU) on a dense [R, S, S, C] stack of ROIs, statistics per (ROI, group): the norm of the conv box head (Detectron2
+    FastRCNNConvFCHead with NORM "GN").  Thousands of 49-row segments: one workgroup per ROI and one pass each way
+    (hip.groupnorm_roi_fwd / _bwd) instead of GroupNormReLU's three-stage segment kernels (at most 160 segments per launch)."""
+
+    def __init__(self, gamma, beta, groups=32, eps=1e-5, relu=True):
+        self.gamma, self.beta, self.groups, self.eps, self.relu = gamma, beta, groups, eps, relu
+
+    def __call__(self, x):
+        if torch.is_grad_enabled():
+            return _RoiGNFn.apply(x, hook(x.device), self)
+        return hip.groupnorm_roi_fwd(x, self.gamma.t, self.beta.t, self.groups, self.eps, self.relu)[0]
+
+
+class _RoiGNFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, hk, layer):
+        x = x.contiguous()
+        y, mean, rstd = hip.groupnorm_roi_fwd(x, layer.gamma.t, layer.beta.t, layer.groups, layer.eps, layer.relu)
+        ctx.layer = layer
+        if GRAD_SYNC[0] is not None:
+            GRAD_SYNC[0].on_forward(_sync_handles(layer))
+        ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        layer = ctx.layer
+        x, mean, rstd = ctx.saved_tensors
+        dx = hip.groupnorm_roi_bwd(dy.contiguous(), x, mean, rstd, layer.gamma.t, layer.beta.t, layer.gamma.g, layer.beta.g, layer.groups,
+                                   layer.relu)
+        if GRAD_SYNC[0] is not None:
+            GRAD_SYNC[0].on_backward_done(_sync_handles(layer))
+        return dx, None, None
+
+
 class HostCounter:
     """`num_batches_tracked` of every BatchNorm of one model: the number of training forward calls so far, a host integer (each of the
     reference's per-level BatchNorm2d modules is called once per forward call, so they all hold the same count)."""
