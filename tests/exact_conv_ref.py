@@ -1,5 +1,6 @@
-"""Exact-arithmetic operands and fp64 references for the 16-bit conv kernels (plain module; used by test_exact_conv_ref.py on the CPU and
-test_conv_exact_gpu.py on the GPU).
+"""Exact-arithmetic operands and fp64 references for the conv kernels: the 16-bit routes, the fp32 implicit-GEMM convs and the grouped 3x3
+conv (plain module; used by test_exact_conv_ref.py on the CPU and test_conv_exact_gpu.py, test_conv_f32_exact_gpu.py and
+test_gconv_exact_gpu.py on the GPU).
 
 The method: every operand is an integer multiple of a power of two (its *unit*), small enough that every product and every partial sum
 of a conv is an integer multiple of the product of the units (the *product grid*) below 2^24 of it.  An fp32 accumulation of such terms is
@@ -87,34 +88,45 @@ def _epilogue(y, scale, bias, residual, relu):
 
 # ----------------------------------------------------------------------------------------------------------------------------------
 # fp64 references
-def conv_fwd_ref(x, w2, k, stride, pad, scale=None, bias=None, residual=None, relu=False):
-    """NHWC fp64 relu?((conv(x, w) * scale + bias) + residual)"""
-    C = x.shape[-1]
-    y = F.conv2d(_x64(x), _w64(w2, k, C), None, stride, pad).permute(0, 2, 3, 1)
-    return _epilogue(y, scale, bias, residual, relu).contiguous()
+def conv_fwd_ref(x, w2, k, stride, pad, scale=None, bias=None, residual=None, relu=False, groups=1, acc0=None):
+    """NHWC fp64 relu?((conv(x, w) * scale + bias) + residual) (+ acc0: the output's earlier content under accumulate, added AFTER the ReLU as
+    the kernels do); groups > 1: w2 is the arena matrix [K, k*k*C/groups] of a grouped conv (row = output channel, reading its group's inputs)"""
+    C = x.shape[-1] // groups
+    y = F.conv2d(_x64(x), _w64(w2, k, C), None, stride, pad, 1, groups).permute(0, 2, 3, 1)
+    y = _epilogue(y, scale, bias, residual, relu)
+    if acc0 is not None:
+        y = y + _v64(acc0)
+    return y.contiguous()
 
 
-def conv_dgrad_ref(dy, w2, in_shape, k, stride, pad, mask=None, residual=None, post_mask=None):
-    """NHWC fp64 gradient of conv(x, w) w.r.t. x for the output gradient dy (w2: the FORWARD weights [K, k*k*C]);
-    dx = mask > 0 ? dx : 0; dx += residual; dx = post_mask > 0 ? dx : 0 (the expression of test_post_mask_epilogue_and_masked_zero_interleave)"""
+def conv_dgrad_ref(dy, w2, in_shape, k, stride, pad, mask=None, residual=None, post_mask=None, groups=1, scale=None, acc0=None):
+    """NHWC fp64 gradient of conv(x, w) w.r.t. x for the output gradient dy (w2: the FORWARD weights [K, k*k*C/groups]);
+    scale [K]: every weight of output channel k is multiplied by scale[k] BEFORE the accumulation (the grouped dgrad's folded FrozenBN);
+    dx = mask > 0 ? dx : 0; dx += residual; dx = post_mask > 0 ? dx : 0 (the expression of test_post_mask_epilogue_and_masked_zero_interleave);
+    dx += acc0 (accumulate)"""
     N, H, W, C = in_shape
     OH, OW = dy.shape[1:3]
     oph, opw = H - ((OH - 1) * stride - 2 * pad + k), W - ((OW - 1) * stride - 2 * pad + k)
-    dx = F.conv_transpose2d(_x64(dy), _w64(w2, k, C), None, stride, pad, output_padding=(oph, opw)).permute(0, 2, 3, 1)
+    w = _w64(w2, k, C // groups)
+    if scale is not None:
+        w = w * _v64(scale).view(-1, 1, 1, 1)
+    dx = F.conv_transpose2d(_x64(dy), w, None, stride, pad, output_padding=(oph, opw), groups=groups).permute(0, 2, 3, 1)
     if mask is not None:
         dx = torch.where(_v64(mask) > 0, dx, torch.zeros_like(dx))
     if residual is not None:
         dx = dx + _v64(residual)
     if post_mask is not None:
         dx = torch.where(_v64(post_mask) > 0, dx, torch.zeros_like(dx))
+    if acc0 is not None:
+        dx = dx + _v64(acc0)
     return dx.contiguous()
 
 
-def conv_wgrad_ref(x, dy, k, stride, pad, rowscale=None, dw0=None, db0=None):
-    """(dw [K, k*k*C], db [K]) fp64: dw0 + rowscale * weight gradient, db0 + rowscale * column sums of dy (autograd in float64)"""
-    C, K = x.shape[-1], dy.shape[-1]
+def conv_wgrad_ref(x, dy, k, stride, pad, rowscale=None, dw0=None, db0=None, groups=1):
+    """(dw [K, k*k*C/groups], db [K]) fp64: dw0 + rowscale * weight gradient, db0 + rowscale * column sums of dy (autograd in float64)"""
+    C, K = x.shape[-1] // groups, dy.shape[-1]
     w = torch.zeros(K, C, k, k, dtype=F64, requires_grad=True)
-    F.conv2d(_x64(x), w, None, stride, pad).backward(_x64(dy))
+    F.conv2d(_x64(x), w, None, stride, pad, 1, groups).backward(_x64(dy))
     dw = w.grad.permute(0, 2, 3, 1).reshape(K, -1)
     db = _v64(dy).reshape(-1, K).sum(0)
     if rowscale is not None:
@@ -167,12 +179,19 @@ def ml_views(t2d, level_hw, N):
     return [t2d[r0:r1].view(N, h, w, t2d.shape[1]) for (r0, r1), (h, w) in zip(level_rows(level_hw, N), level_hw)]
 
 
-def ml_fwd_ref(x2d, w2, level_hw, N, k, pad, scale=None, bias=None, residual=None, relu=False):
-    """level-first [P, K] fp64: conv_fwd_ref per level (stride 1)"""
+def ml_fwd_ref(x2d, w2, level_hw, N, k, pad, scale=None, bias=None, residual=None, relu=False, acc0=None):
+    """level-first [P, K] fp64: conv_fwd_ref per level (stride 1); acc0 [P, K]: added after the epilogue (accumulate)"""
     res = ml_views(residual, level_hw, N) if residual is not None else [None] * len(level_hw)
     outs = [conv_fwd_ref(xl, w2, k, 1, pad, scale, bias, rl, relu).reshape(-1, w2.shape[0])
             for xl, rl in zip(ml_views(x2d, level_hw, N), res)]
-    return torch.cat(outs)
+    y = torch.cat(outs)
+    return y if acc0 is None else y + _v64(acc0)
+
+
+def ml_dgrad_ref(dy2d, w2, level_hw, N, k, pad, C):
+    """level-first [P, C] fp64: conv_dgrad_ref per level (w2: the FORWARD weights [K, k*k*C])"""
+    return torch.cat([conv_dgrad_ref(dl, w2, (N, h, w, C), k, 1, pad).reshape(-1, C)
+                      for dl, (h, w) in zip(ml_views(dy2d, level_hw, N), level_hw)])
 
 
 def ml_wgrad_ref(x2d, dy2d, level_hw, N, k, pad, rowscale=None, dw0=None, db0=None):
@@ -256,43 +275,51 @@ def assert_exact_domain(bound64, ref64, unit_exp):
     assert torch.equal(ref64.to(torch.float32).to(F64), ref64)
 
 
-def fwd_domain(x, w2, k, stride, pad, unit_exp, scale=None, bias=None, residual=None, relu=False):
+def fwd_domain(x, w2, k, stride, pad, unit_exp, scale=None, bias=None, residual=None, relu=False, groups=1, acc0=None):
     """fp64 forward reference, after assert_exact_domain on it; unit_exp = exponent of unit(x) * unit(w) * unit(scale)"""
     ab = lambda t: None if t is None else t.detach().cpu().to(F64).abs()
-    ref = conv_fwd_ref(x, w2, k, stride, pad, scale, bias, residual, relu)
-    bound = conv_fwd_ref(ab(x), ab(w2), k, stride, pad, ab(scale), ab(bias), ab(residual))
-    for t, n in ((bias, "bias"), (residual, "residual")):
+    ref = conv_fwd_ref(x, w2, k, stride, pad, scale, bias, residual, relu, groups, acc0)
+    bound = conv_fwd_ref(ab(x), ab(w2), k, stride, pad, ab(scale), ab(bias), ab(residual), False, groups, ab(acc0))
+    for t, n in ((bias, "bias"), (residual, "residual"), (acc0, "accumulate addend")):
         if t is not None:
             assert_on_grid(t, unit_exp, n)
     assert_exact_domain(bound, ref, unit_exp)
     return ref
 
 
-def dgrad_domain(dy, w2, in_shape, k, stride, pad, unit_exp, mask=None, residual=None, post_mask=None):
+def dgrad_domain(dy, w2, in_shape, k, stride, pad, unit_exp, mask=None, residual=None, post_mask=None, groups=1, scale=None, acc0=None):
     ab = lambda t: None if t is None else t.detach().cpu().to(F64).abs()
-    ref = conv_dgrad_ref(dy, w2, in_shape, k, stride, pad, mask, residual, post_mask)
-    bound = conv_dgrad_ref(ab(dy), ab(w2), in_shape, k, stride, pad, None, ab(residual), None)
-    if residual is not None:
-        assert_on_grid(residual, unit_exp, "residual")
+    ref = conv_dgrad_ref(dy, w2, in_shape, k, stride, pad, mask, residual, post_mask, groups, scale, acc0)
+    bound = conv_dgrad_ref(ab(dy), ab(w2), in_shape, k, stride, pad, None, ab(residual), None, groups, ab(scale), ab(acc0))
+    for t, n in ((residual, "residual"), (acc0, "accumulate addend")):
+        if t is not None:
+            assert_on_grid(t, unit_exp, n)
     assert_exact_domain(bound, ref, unit_exp)
     return ref
 
 
-def wgrad_domain(x, dy, k, stride, pad, unit_exp, rowscale=None, dw0=None, db0=None, db_unit_exp=None):
+def wgrad_domain(x, dy, k, stride, pad, unit_exp, rowscale=None, dw0=None, db0=None, db_unit_exp=None, groups=1):
     """(dw, db) fp64 after assert_exact_domain on both; unit_exp = unit(x) * unit(dy) * unit(rowscale), db_unit_exp = unit(dy) * unit(rowscale)"""
     ab = lambda t: None if t is None else t.detach().cpu().to(F64).abs()
-    dw, db = conv_wgrad_ref(x, dy, k, stride, pad, rowscale, dw0, db0)
-    bw, bb = conv_wgrad_ref(ab(x), ab(dy), k, stride, pad, ab(rowscale), ab(dw0), ab(db0))
+    dw, db = conv_wgrad_ref(x, dy, k, stride, pad, rowscale, dw0, db0, groups)
+    bw, bb = conv_wgrad_ref(ab(x), ab(dy), k, stride, pad, ab(rowscale), ab(dw0), ab(db0), groups)
     assert_exact_domain(bw, dw, unit_exp)
     assert_exact_domain(bb, db, unit_exp if db_unit_exp is None else db_unit_exp)
     return dw, db
 
 
-def ml_fwd_domain(x2d, w2, level_hw, N, k, pad, unit_exp, scale=None, bias=None, residual=None, relu=False):
+def ml_fwd_domain(x2d, w2, level_hw, N, k, pad, unit_exp, scale=None, bias=None, residual=None, relu=False, acc0=None):
     ab = lambda t: None if t is None else t.detach().cpu().to(F64).abs()
-    ref = ml_fwd_ref(x2d, w2, level_hw, N, k, pad, scale, bias, residual, relu)
-    bound = ml_fwd_ref(ab(x2d), ab(w2), level_hw, N, k, pad, ab(scale), ab(bias), ab(residual))
+    ref = ml_fwd_ref(x2d, w2, level_hw, N, k, pad, scale, bias, residual, relu, acc0)
+    bound = ml_fwd_ref(ab(x2d), ab(w2), level_hw, N, k, pad, ab(scale), ab(bias), ab(residual), False, ab(acc0))
     assert_exact_domain(bound, ref, unit_exp)
+    return ref
+
+
+def ml_dgrad_domain(dy2d, w2, level_hw, N, k, pad, C, unit_exp):
+    ab = lambda t: t.detach().cpu().to(F64).abs()
+    ref = ml_dgrad_ref(dy2d, w2, level_hw, N, k, pad, C)
+    assert_exact_domain(ml_dgrad_ref(ab(dy2d), ab(w2), level_hw, N, k, pad, C), ref, unit_exp)
     return ref
 
 
@@ -550,3 +577,322 @@ def gaussian_ml_operands(name, seed=0):
     h = lambda t: t.to(torch.float16).to(torch.float32)
     return (h(torch.randn(P, C, generator=g)), h(torch.randn(K, 9 * C, generator=g) * 0.05), torch.randn(K, generator=g),
             h(torch.randn(P, K, generator=g)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the fp32 implicit-GEMM convs (csrc/conv.hip) and the grouped 3x3 conv (csrc/conv_grouped.hip): test_conv_f32_exact_gpu.py,
+# test_gconv_exact_gpu.py.  fp32 operands carry as many bits as the reduction length leaves room for.
+def dyadic_nonzero(shape, bits, scale_exp, generator):
+    """dyadic without a single zero (an integer 0 becomes 1): what an accumulate launch adds onto, so that an ignored flag shows everywhere"""
+    t = dyadic(shape, bits, scale_exp, generator, zero_frac=0.0)
+    t[t == 0] = 2.0 ** scale_exp
+    return t
+
+
+def f32_operand_bits(Kred):
+    """(bits_x, bits_w) of an fp32 case: the widest pair (x at most one bit ahead) with (2^bx - 1) * (2^bw - 1) * Kred * 6 < 2^23 - the
+    largest scale multiplier is 6 units, and half of the 2^24 units stay free for the bias, the residual and the accumulate addend"""
+    bx, bw = 12, 11
+    while (2 ** bx - 1) * (2 ** bw - 1) * Kred * 6 >= 2 ** 23:
+        if bx > bw:
+            bx -= 1
+        else:
+            bw -= 1
+    return bx, bw
+
+
+# channel cases of utv2_conv2d_nhwc_fwd: name -> (C, K).  The rules (conv.hip): K <= 64 -> conv_igemm_f32<64, .>, else <128, .>;
+# C % 16 == 0 -> MODE 0 (vector gather), else MODE 2 (scalar gather); K % 4 == 0 -> epilogue_rows, else the scalar epilogue
+F32_CASES = {
+    "m0_bn64_k8": (16, 8),          # MODE 0, 64-wide tile, 8 of its 64 columns
+    "m0_bn64_k64": (32, 64),        # MODE 0, the 64-wide tile full, two channel slabs
+    "m0_bn128_k72": (16, 72),       # MODE 0, one partial 128-wide tile
+    "m0_bn128_k136": (32, 136),     # MODE 0, two column tiles, the second 8 wide
+    "m2_bn64_k8": (20, 8),          # MODE 2: C = 20, a 16-wide k chunk straddles taps
+    "m2_bn64_k64": (12, 64),
+    "m2_bn128_k72": (20, 72),
+    "m2_bn128_k136": (12, 136),
+    "m0_bn64_k7_scalar": (16, 7),   # K % 4 != 0 -> the scalar epilogue, MODE 0 / 64
+    "m0_bn128_k73_scalar": (32, 73),
+    "m2_bn64_k7_scalar": (20, 7),
+    "m2_bn128_k73_scalar": (12, 73),
+}
+# geometries of every channel case: (N, H, W, k, stride, pad).  (2, 9, 7) stride 1: M = 126 < 128, one partial row tile; (2, 9, 8): M = 144,
+# two row tiles, the second 16 rows; stride 2: the odd sides 9 and 7 and the even side 8
+F32_GEOMS = [(2, 9, 7, 3, 1, 1), (2, 9, 8, 3, 1, 1), (2, 9, 7, 3, 2, 1), (2, 9, 8, 3, 2, 1),
+             (2, 9, 7, 1, 1, 0), (2, 9, 8, 1, 1, 0), (2, 9, 7, 1, 2, 0), (2, 9, 8, 1, 2, 0)]
+
+# dgrads (utv2_conv2d_nhwc_fwd over dY with in_dil = stride): name -> (N, H, W, C, K, k, stride, pad) of the FORWARD conv.  The gather
+# mode follows the reduction channels K (K % 16 == 0 -> MODE 0), the tile and the epilogue follow the output channels C
+F32_DGRAD = {
+    "m0_s1": (2, 9, 7, 16, 32, 3, 1, 1),            # MODE 0, in_dil 1, odd sides
+    "m0_s2": (2, 9, 8, 20, 16, 3, 2, 1),            # MODE 0, in_dil 2, an odd and an even side (output_padding 1 on the even one)
+    "m2_s2": (2, 9, 8, 16, 20, 3, 2, 1),            # MODE 2 with in_dil 2
+    "m2_s2_scalar": (2, 8, 7, 7, 12, 3, 2, 1),      # MODE 2, in_dil 2, C = 7: the scalar epilogue
+    "m2_s1_bn128": (2, 9, 7, 72, 24, 3, 1, 1),      # MODE 2, in_dil 1, the 128-wide tile
+    "m0_1x1_s2": (2, 9, 8, 16, 16, 1, 2, 0),        # 1x1 stride 2: only the even pixels receive a gradient (the last column of W = 8 none)
+    "m2_1x1_s2": (2, 9, 8, 12, 20, 1, 2, 0),
+}
+F32_FLIP = [(7, 3, 20), (64, 1, 16), (72, 3, 16)]   # (K, k, C) of weight_flip_transpose_f32
+
+# the image stem (utv2_conv2d_stem_fwd -> conv_igemm_f32<., 1>): 7x7 stride 2 pad 3 on an NHWC4 image, weight rows padded from 196 to 208;
+# K = 64 -> the 64-wide tile, K = 72 -> the 128-wide one.  (N, H, W): M = 60 (one partial row tile) and M = 144 (two)
+F32_STEM_K = [64, 72]
+F32_STEM_IMAGES = [(2, 9, 11), (2, 16, 18)]
+F32_STEM_UNIT_EXP = -9      # x 2^-3 * w 2^-5 * scale 2^-1
+
+# multi-level convs (utv2_conv2d_ml_fwd -> conv_igemm_f32<., 0, true>, utv2_conv2d_ml_wgrad -> conv_wgrad_f32<1, true>): C % 16 == 0 and
+# K % 4 == 0 are required; K <= 64 -> the 64-wide tile.  P = 2 * (35 + 12 + 1) = 96 rows: one partial 128-row tile across all levels and images
+F32_ML_LEVELS, F32_ML_N = [(5, 7), (3, 4), (1, 1)], 2
+F32_ML = {"ml64": (16, 8), "ml128": (32, 72)}       # name -> (C, K), each with k = 1 and k = 3
+
+# weight gradients (utv2_conv2d_nhwc_wgrad): name -> (N, H, W, C, K, k, stride, pad); C % 4 == 0 and K % 4 == 0 -> conv_wgrad_f32<1>, else <0>.
+# Every output is 2 x 12 x 11: M = 264 = 16 chunks of 16 + 8 -> 17 chunks -> max_by_chunks = 2 -> two splits of 9 and 8 chunks, the last partial
+F32_WGRAD = {
+    "vec_s1": (2, 12, 11, 16, 136, 3, 1, 1),        # Kred = 144: a second column tile of 16; K = 136: a second row tile of 8
+    "vec_s2": (2, 24, 21, 16, 136, 3, 2, 1),
+    "scalar_k7": (2, 12, 11, 20, 7, 3, 1, 1),       # K % 4 != 0
+    "scalar_k7_s2": (2, 23, 22, 16, 7, 3, 2, 1),
+    "scalar_c6": (2, 12, 11, 6, 8, 3, 1, 1),        # C % 4 != 0
+    "scalar_c6_1x1_s2": (2, 23, 21, 6, 8, 1, 2, 0),
+}
+F32_WGRAD_UNIT_EXP = -7     # x integers * 2^-3, dy integers * 2^-4
+F32_WGRAD_DB_UNIT_EXP = -4
+
+# column sums (utv2_colsum): name -> (M, C).  C % 4 == 0, 256 % (C / 4) == 0 and M >= 1024 -> colsum_partial_vec_f32 with 256-row blocks,
+# else colsum_partial_f32 with P = min(cdiv(M, 512), 64) row ranges.  The vector route doubles its block rows beyond 256 * 1024 rows: that
+# branch needs M > 262144 and stays untested.
+COLSUM_CASES = {
+    "vec_ragged": (1030, 16),       # 5 blocks, the last one 6 rows
+    "scalar_c24": (1030, 24),       # C / 4 = 6 does not divide 256; P = 3
+    "scalar_small_m": (600, 16),    # M < 1024; P = 2
+    "scalar_c72": (70, 72),         # P = 1, two 64-channel blocks, the second 8 wide
+}
+COLSUM_UNIT_EXP = -6
+
+
+def f32_wgrad_splits(M, K, Kred):
+    """utv2_conv2d_wgrad_splits (conv.hip) restated"""
+    chunks = -(-M // 16)
+    tiles = -(-K // 128) * -(-Kred // 128)
+    return max(1, min(-(-1024 // tiles), max(chunks // 8, 1), 256))
+
+
+def colsum_route(M, C):
+    """("vec", blocks, rows per block) or ("scalar", P, rows per range): the dispatch of utv2_colsum restated"""
+    if C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and M >= 1024:
+        rows = 256
+        while -(-M // rows) > 1024:
+            rows *= 2
+        return "vec", -(-M // rows), rows
+    P = max(1, min(-(-M // 512), 64))
+    return "scalar", P, -(-M // P)
+
+
+def _out_hw(H, W, k, s, p):
+    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+
+
+def f32_fwd_operands(C, K, geom, seed=0):
+    """dict of CPU fp32 operands of one (channel case, geometry): x integers * 2^-3, w integers * 2^-5 (f32_operand_bits), scale two-bit
+    multipliers of unit 2^-1, bias / residual / acc0 (the output's content before an accumulate launch, non-zero) on the grid 2^-9"""
+    N, H, W, k, s, p = geom
+    bx, bw = f32_operand_bits(k * k * C)
+    g = torch.Generator().manual_seed(seed)
+    OH, OW = _out_hw(H, W, k, s, p)
+    shp = (N, OH, OW, K)
+    return dict(x=dyadic((N, H, W, C), bx, -3, g), w=dyadic((K, k * k * C), bw, -5, g), scale=small_scale((K,), g),
+                bias=dyadic((K,), 12, -9, g), res=dyadic(shp, 12, -6, g), acc0=dyadic_nonzero(shp, 12, -7, g), unit=-8)
+
+
+def f32_dgrad_operands(name, seed=1):
+    N, H, W, C, K, k, s, p = F32_DGRAD[name]
+    bx, bw = f32_operand_bits(k * k * K)
+    g = torch.Generator().manual_seed(seed)
+    OH, OW = _out_hw(H, W, k, s, p)
+    return dict(dy=dyadic((N, OH, OW, K), bx, -3, g), w=dyadic((K, k * k * C), bw, -5, g),
+                acc0=dyadic_nonzero((N, H, W, C), 12, -7, g), unit=-8)
+
+
+def f32_stem_operands(K, image, seed=3):
+    """x4 NHWC4 (all four channels non-zero: the kernel multiplies every one), w [K, 208] with the 4 x 49 taps in [0, 196) and arbitrary
+    finite values in the padding [196, 208) - its taps 49 .. 51 do not exist, so the kernel feeds zeros against them"""
+    N, H, W = image
+    g = torch.Generator().manual_seed(seed)
+    return dict(x=dyadic((N, H, W, 4), 5, -3, g), w=dyadic((K, 208), 4, -5, g), scale=small_scale((K,), g), bias=dyadic((K,), 9, -9, g))
+
+
+def f32_stem_ref(o, epilogue, abs_bound=False):
+    """fp64 NHWC reference of the stem on f32_stem_operands: a 4-channel 7x7 stride-2 pad-3 conv over the first 196 weight columns"""
+    a = (lambda t: t.abs()) if abs_bound else (lambda t: t)
+    w = a(o["w"])[:, :196].contiguous()
+    if not epilogue:
+        return conv_fwd_ref(a(o["x"]), w, 7, 2, 3)
+    return conv_fwd_ref(a(o["x"]), w, 7, 2, 3, o["scale"], a(o["bias"]), relu=not abs_bound)
+
+
+def f32_stem_domain(o, epilogue):
+    ref = f32_stem_ref(o, epilogue)
+    assert_exact_domain(f32_stem_ref(o, epilogue, abs_bound=True), ref, F32_STEM_UNIT_EXP)
+    return ref
+
+
+def f32_ml_operands(C, K, k, seed=5):
+    P = F32_ML_N * sum(h * w for h, w in F32_ML_LEVELS)
+    bx, bw = f32_operand_bits(k * k * C)
+    g = torch.Generator().manual_seed(seed)
+    return dict(x=dyadic((P, C), bx, -3, g), w=dyadic((K, k * k * C), bw, -5, g), scale=small_scale((K,), g), bias=dyadic((K,), 12, -9, g),
+                res=dyadic((P, K), 12, -6, g), acc0=dyadic_nonzero((P, K), 12, -7, g),
+                dy=dyadic((P, K), 8, -4, g), xr=dyadic((P, C), 8, -3, g, relu_like=True),
+                dw0=dyadic_nonzero((K, k * k * C), 12, -4, g), unit=-8)
+
+
+def f32_wgrad_operands(name, seed=2):
+    N, H, W, C, K, k, s, p = F32_WGRAD[name]
+    g = torch.Generator().manual_seed(seed)
+    OH, OW = _out_hw(H, W, k, s, p)
+    return dict(x=dyadic((N, H, W, C), 8, -3, g, relu_like=True), dy=dyadic((N, OH, OW, K), 7, -4, g),
+                dw0=dyadic_nonzero((K, k * k * C), 12, -4, g))
+
+
+def colsum_operands(name, seed=6):
+    M, C = COLSUM_CASES[name]
+    g = torch.Generator().manual_seed(seed)
+    return dyadic((M, C), 13, COLSUM_UNIT_EXP, g), dyadic_nonzero((C,), 12, COLSUM_UNIT_EXP + 2, g)
+
+
+def colsum_domain(g2d, db0=None):
+    ref = _v64(g2d).sum(0)
+    bound = _v64(g2d).abs().sum(0)
+    if db0 is not None:
+        ref, bound = ref + _v64(db0), bound + _v64(db0).abs()
+    assert_exact_domain(bound, ref, COLSUM_UNIT_EXP)
+    return ref
+
+
+def relu_clamps_some(pre64):
+    """an epilogue case is not vacuous: the value before the ReLU is negative somewhere and positive somewhere"""
+    return bool((pre64 < 0).any()) and bool((pre64 > 0).any())
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# grouped 3x3 conv (csrc/conv_grouped.hip).  A forward / dgrad thread owns one channel quad of GPX = 4 consecutive pixels of a row; a wgrad
+# thread owns a 4 x 4 block of one tap over one split of the output pixels.
+GPX = 4
+# (g channels per group, G groups): (4, 3): C = 12, three channel quads (no power of two), every quad its own group; (8, 2): the second quad
+# of a group has co % g != 0; (32, 2): eight trips of the inner channel loop
+GCONV_GROUPS = [(4, 3), (8, 2), (32, 2)]
+# (N, H, W): a single pixel; OW < GPX (3 at stride 1, 2 at stride 2); W = 4 = GPX with H odd; both sides even, W and OW multiples of 4;
+# both sides odd and ragged (W = 9, OW = 5 at stride 2), three images
+GCONV_SHAPES = [(1, 1, 1), (2, 2, 3), (2, 5, 4), (2, 6, 8), (3, 7, 9)]
+# seeds of the forward and the dgrad operands where seed 0 does not give every 16-bit output of the case an exact tie and an inexact value
+# in bf16 AND fp16 (test_exact_conv_ref.py asserts it for every case): (g, G, N, H, W, stride) -> (forward seed, dgrad seed)
+GCONV_SEEDS = {
+    (4, 3, 1, 1, 1, 1): (19, 17), (4, 3, 1, 1, 1, 2): (19, 17),       # 12 output elements
+    (4, 3, 2, 2, 3, 2): (0, 1), (4, 3, 2, 5, 4, 2): (1, 0),
+    (8, 2, 1, 1, 1, 1): (4, 0), (8, 2, 1, 1, 1, 2): (4, 0),
+    (32, 2, 1, 1, 1, 1): (0, 8), (32, 2, 1, 1, 1, 2): (0, 8),
+}
+GCONV_CASES = {"g%d_G%d_%dx%dx%d_s%d" % (g, G, N, H, W, s): (g, G, N, H, W, s) + GCONV_SEEDS.get((g, G, N, H, W, s), (0, 0))
+               for g, G in GCONV_GROUPS for N, H, W in GCONV_SHAPES for s in (1, 2)}
+GCONV_UNIT_EXP = -9         # x 2^-3 * w 2^-5 * scale 2^-1 (forward and dgrad)
+GCONV_WGRAD_UNIT_EXP = -8   # x 2^-3 * dy 2^-4 * scale 2^-1
+GCONV_FWD_VARIANTS = {"plain": (False, False, False), "scale": (True, False, False), "shift": (False, True, False),
+                      "scale_shift_relu": (True, True, True)}                    # name -> (scale, shift, relu)
+GCONV_DGRAD_VARIANTS = {"plain": (False, False, False), "scale": (True, False, False), "scale_mask": (True, True, False),
+                        "scale_mask_residual": (True, True, True)}               # name -> (scale, mask, residual)
+
+
+def gconv_out_hw(H, W, stride):
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def gconv_wgrad_splits(N, OH, OW, C, G):
+    """(splits, per_split) of utv2_gconv3x3_wgrad (conv_grouped.hip) restated"""
+    g = C // G
+    tpl = (C // 4) * 9 * (g // 4)
+    M = N * OH * OW
+    s = min(-(-262144 // tpl), (1 << 25) // (C * 9 * g), 256, (M + 31) // 32)
+    s = max(s, 1)
+    return s, -(-M // s)
+
+
+def _gconv_bits(g):
+    """(bits_x, bits_w): at most 7 (exact in bf16 and fp16); sums of 9 * g products with 12 .. 16 significant bits"""
+    return {4: (6, 6), 8: (6, 5), 32: (5, 4)}[g]
+
+
+def _mask_with_every_kind(shape, generator):
+    """a ReLU-input stand-in: positive and negative integers (3 bits) with exact +0.0 and -0.0 planted: element 4 i + 1 is +0.0, 4 i + 3 is
+    -0.0 for every other i; the first four elements are (+1, +0.0, -1, -0.0) so that the smallest tensor holds all four kinds"""
+    m = dyadic(shape, 3, 0, generator, zero_frac=0.0).reshape(-1)
+    m[m == 0] = 1.0
+    m[1::8] = 0.0
+    m[3::8] = -0.0
+    m[0], m[2] = 1.0, -1.0
+    return m.reshape(shape)
+
+
+def gconv_fwd_operands(name):
+    g, G, N, H, W, s, seed, _ = GCONV_CASES[name]
+    C = g * G
+    bx, bw = _gconv_bits(g)
+    gen = torch.Generator().manual_seed(seed)
+    return dict(x=dyadic((N, H, W, C), bx, -3, gen), w=dyadic((C, 9 * g), bw, -5, gen), scale=small_scale((C,), gen),
+                shift=dyadic((C,), 9, GCONV_UNIT_EXP, gen))
+
+
+def gconv_dgrad_operands(name):
+    g, G, N, H, W, s, _, seed = GCONV_CASES[name]
+    C = g * G
+    bx, bw = _gconv_bits(g)
+    OH, OW = gconv_out_hw(H, W, s)
+    gen = torch.Generator().manual_seed(1000 + seed)
+    return dict(dy=dyadic((N, OH, OW, C), bx, -3, gen), w=dyadic((C, 9 * g), bw, -5, gen), scale=small_scale((C,), gen),
+                mask=_mask_with_every_kind((N, H, W, C), gen), res=dyadic((N, H, W, C), 7, GCONV_UNIT_EXP + 3, gen))
+
+
+def gconv_wgrad_operands(name):
+    g, G, N, H, W, s = GCONV_CASES[name][:6]
+    C = g * G
+    OH, OW = gconv_out_hw(H, W, s)
+    gen = torch.Generator().manual_seed(2000)
+    return dict(x=dyadic((N, H, W, C), 6, -3, gen), dy=dyadic((N, OH, OW, C), 6, -4, gen), scale=small_scale((C,), gen),
+                dw0=dyadic_nonzero((C, 9 * g), 12, GCONV_WGRAD_UNIT_EXP + 2, gen))
+
+
+def gconv_fwd_domain(name, o, variant):
+    """fp64 reference relu?((acc * scale) + shift) of one forward variant, after assert_exact_domain; a ReLU variant clamps some elements"""
+    g, G, N, H, W, s = GCONV_CASES[name][:6]
+    use_sc, use_sh, relu = GCONV_FWD_VARIANTS[variant]
+    sc, sh = (o["scale"] if use_sc else None), (o["shift"] if use_sh else None)
+    ref = fwd_domain(o["x"], o["w"], 3, s, 1, GCONV_UNIT_EXP, sc, sh, None, relu, groups=G)
+    if relu:
+        assert relu_clamps_some(conv_fwd_ref(o["x"], o["w"], 3, s, 1, sc, sh, groups=G)), name
+    return ref
+
+
+def gconv_dgrad_domain(name, o, variant):
+    """fp64 reference (mask > 0 ? sum of dy * (w * scale) : 0) + residual of one dgrad variant, after assert_exact_domain; a mask variant
+    holds +0.0, -0.0, a negative and a positive value"""
+    g, G, N, H, W, s = GCONV_CASES[name][:6]
+    use_sc, use_mk, use_rs = GCONV_DGRAD_VARIANTS[variant]
+    mk = o["mask"] if use_mk else None
+    if use_mk:
+        m = mk.reshape(-1)
+        pz, nz = (m == 0) & ~torch.signbit(m), (m == 0) & torch.signbit(m)
+        assert bool(pz.any()) and bool(nz.any()) and bool((m < 0).any()) and bool((m > 0).any()), name
+    return dgrad_domain(o["dy"], o["w"], (N, H, W, g * G), 3, s, 1, GCONV_UNIT_EXP, mk, o["res"] if use_rs else None, None,
+                        groups=G, scale=o["scale"] if use_sc else None)
+
+
+def gconv_wgrad_domain(name, o, use_scale, accumulate):
+    g, G, N, H, W, s = GCONV_CASES[name][:6]
+    dw, _ = wgrad_domain(o["x"], o["dy"], 3, s, 1, GCONV_WGRAD_UNIT_EXP, o["scale"] if use_scale else None, o["dw0"] if accumulate else None,
+                         None, GCONV_WGRAD_UNIT_EXP + 3, groups=G)
+    return dw
+
+
+def has_tie_and_inexact(ref64, h16):
+    tie, inexact = tie_and_inexact_share(ref64, h16)
+    return tie > 0 and inexact > 0

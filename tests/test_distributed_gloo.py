@@ -22,7 +22,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, received):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "unbiased-teacher-v2_amd"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -164,6 +164,9 @@ def _worker(rank, world, port, q):
         whole_gt[i], whole_pr[i] = _img(i)
     out["eval_whole"] = {"bbox": coco_box_ap(whole_pr, whole_gt, 2)}
     q.put((rank, out))
+    # the tensors in `out` travel as shared-memory handles that the parent fetches from THIS process while it unpickles them: stay alive
+    # until the parent has both results (a rank that exits first takes its handle server with it and the parent's q.get fails)
+    assert received.wait(300)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -172,11 +175,13 @@ def test_world_size_2_gloo():
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
+    received = ctx.Event()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, received)) for r in range(world)]
     for p in procs:
         p.start()
     res = dict(q.get(timeout=300) for _ in range(world))
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

@@ -181,3 +181,162 @@ def test_fp64_multi_level_reference_rounded_to_fp16_meets_the_gaussian_criteria(
     x, w2, b, res = R.gaussian_ml_operands(name)
     ref = R.ml_fwd_ref(x, w2, level_hw, N, 3, 1, None, b, res, True)
     assert R.close16(ref.to(torch.float16), ref, 2.0 ** -11) and R.relerr(ref.float(), ref) < 2e-4
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the fp32 implicit-GEMM and grouped-conv tables (test_conv_f32_exact_gpu.py, test_gconv_exact_gpu.py)
+@pytest.mark.parametrize("name", sorted(R.F32_CASES))
+def test_f32_forward_cases_are_inside_the_exact_domain_and_obey_their_dispatch_rules(name):
+    C, K = R.F32_CASES[name]
+    assert ("bn64" in name) == (K <= 64) and ("m0" in name) == (C % 16 == 0) and ("scalar" in name) == (K % 4 != 0)
+    for geom in R.F32_GEOMS:
+        N, H, W, k, s, p = geom
+        o = R.f32_fwd_operands(C, K, geom)
+        epi = (o["scale"], o["bias"], o["res"])
+        assert float(R.fwd_domain(o["x"], o["w"], k, s, p, o["unit"]).abs().max()) > 0
+        R.fwd_domain(o["x"], o["w"], k, s, p, o["unit"], acc0=o["acc0"])
+        R.fwd_domain(o["x"], o["w"], k, s, p, o["unit"] - 1, *epi, True)
+        ref = R.fwd_domain(o["x"], o["w"], k, s, p, o["unit"] - 1, *epi, True, acc0=o["acc0"])
+        assert R.relu_clamps_some(R.conv_fwd_ref(o["x"], o["w"], k, s, p, *epi)) and bool((o["acc0"] != 0).all())
+        assert not torch.equal(ref, torch.relu(ref))
+
+
+def test_f32_geometries_cover_both_row_tile_cases():
+    Ms = {g: g[0] * R._out_hw(g[1], g[2], g[3], g[4], g[5])[0] * R._out_hw(g[1], g[2], g[3], g[4], g[5])[1] for g in R.F32_GEOMS}
+    assert Ms[(2, 9, 7, 3, 1, 1)] == 126 and Ms[(2, 9, 8, 3, 1, 1)] == 144
+    assert {(g[3], g[4]) for g in R.F32_GEOMS} == {(3, 1), (3, 2), (1, 1), (1, 2)}
+    assert all(b * 6 * (2 ** a[0] - 1) * (2 ** a[1] - 1) < 2 ** 23 for b in (12, 16, 20, 32, 108, 288) for a in [R.f32_operand_bits(b)])
+
+
+@pytest.mark.parametrize("name", sorted(R.F32_DGRAD))
+def test_f32_dgrad_cases_are_inside_the_exact_domain_and_obey_their_dispatch_rules(name):
+    N, H, W, C, K, k, s, p = R.F32_DGRAD[name]
+    assert ("m0" in name) == (K % 16 == 0) and ("scalar" in name) == (C % 4 != 0) and ("s2" in name) == (s == 2) and ("bn128" in name) == (C > 64)
+    o = R.f32_dgrad_operands(name)
+    R.dgrad_domain(o["dy"], o["w"], (N, H, W, C), k, s, p, o["unit"])
+    ref = R.dgrad_domain(o["dy"], o["w"], (N, H, W, C), k, s, p, o["unit"], acc0=o["acc0"])
+    # the reference is the gradient autograd computes
+    x = torch.zeros(N, C, H, W, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, R._w64(o["w"], k, C), None, s, p).backward(R._x64(o["dy"]))
+    assert torch.equal(x.grad.permute(0, 2, 3, 1) + o["acc0"].double(), ref)
+
+
+@pytest.mark.parametrize("h16", H16S)
+@pytest.mark.parametrize("image", R.F32_STEM_IMAGES)
+@pytest.mark.parametrize("K", R.F32_STEM_K)
+def test_f32_stem_cases_are_inside_the_exact_domain_and_exercise_the_rounding(K, image, h16):
+    o = R.f32_stem_operands(K, image)
+    assert K % 4 == 0 and o["w"].shape[1] == 208 and bool((o["w"][:, 196:] != 0).any()) and bool((o["x"][..., 3] != 0).any())
+    for epilogue in (False, True):
+        assert R.has_tie_and_inexact(R.f32_stem_domain(o, epilogue), h16), (K, image, h16, epilogue)
+    assert R.relu_clamps_some(R.conv_fwd_ref(o["x"], o["w"][:, :196].contiguous(), 7, 2, 3, o["scale"], o["bias"]))
+
+
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("name", sorted(R.F32_ML))
+def test_f32_multi_level_cases_are_inside_the_exact_domain(name, k):
+    C, K = R.F32_ML[name]
+    assert C % 16 == 0 and K % 4 == 0 and (name == "ml64") == (K <= 64)
+    lv, N, pad = R.F32_ML_LEVELS, R.F32_ML_N, k // 2
+    o = R.f32_ml_operands(C, K, k)
+    epi = (o["scale"], o["bias"], o["res"])
+    R.ml_fwd_domain(o["x"], o["w"], lv, N, k, pad, o["unit"])
+    R.ml_fwd_domain(o["x"], o["w"], lv, N, k, pad, o["unit"] - 1, *epi, True, acc0=o["acc0"])
+    assert R.relu_clamps_some(R.ml_fwd_ref(o["x"], o["w"], lv, N, k, pad, *epi))
+    wf = o["w"].view(K, k, k, C).permute(3, 1, 2, 0).reshape(C, k * k * K).contiguous()
+    ref = R.ml_dgrad_domain(o["x"], wf, lv, N, k, pad, K, o["unit"])
+    # the per-level transposed conv equals the stride-1 conv of dY with the flipped / transposed weight image
+    assert torch.equal(ref, R.ml_fwd_ref(o["x"], R.flip_transpose_ref(wf, C, k, K), lv, N, k, k - 1 - pad))
+    R.ml_wgrad_domain(o["xr"], o["dy"], lv, N, k, pad, R.F32_WGRAD_UNIT_EXP, None, o["dw0"], None, R.F32_WGRAD_DB_UNIT_EXP)
+    assert R.f32_wgrad_splits(N * sum(h * w for h, w in lv), K, k * k * C) == 1
+
+
+@pytest.mark.parametrize("name", sorted(R.F32_WGRAD))
+def test_f32_wgrad_cases_are_inside_the_exact_domain_and_split_twice(name):
+    N, H, W, C, K, k, s, p = R.F32_WGRAD[name]
+    assert ("vec" in name) == (C % 4 == 0 and K % 4 == 0)
+    o = R.f32_wgrad_operands(name)
+    assert tuple(o["dy"].shape) == (2, 12, 11, K)
+    M = 264
+    splits = R.f32_wgrad_splits(M, K, k * k * C)
+    assert splits == 2 and -(-M // 16) == 17 and M % 16 == 8
+    R.wgrad_domain(o["x"], o["dy"], k, s, p, R.F32_WGRAD_UNIT_EXP, None, o["dw0"], None, R.F32_WGRAD_DB_UNIT_EXP)
+
+
+@pytest.mark.parametrize("name", sorted(R.COLSUM_CASES))
+def test_colsum_cases_are_inside_the_exact_domain_and_obey_their_dispatch_rules(name):
+    M, C = R.COLSUM_CASES[name]
+    g2d, db0 = R.colsum_operands(name)
+    R.colsum_domain(g2d)
+    R.colsum_domain(g2d, db0)
+    route, parts, rows = R.colsum_route(M, C)
+    assert (route == "vec") == name.startswith("vec")
+    want = {"vec_ragged": (5, 256), "scalar_c24": (3, 344), "scalar_small_m": (2, 300), "scalar_c72": (1, 70)}[name]
+    assert (parts, rows) == want and (name != "vec_ragged" or M % rows == 6)
+
+
+def _per_group(fn, G):
+    """the grouped operation as G ungrouped ones over the channel slices, concatenated on the channel axis"""
+    return torch.cat([fn(i) for i in range(G)], dim=-1)
+
+
+@pytest.mark.parametrize("name", sorted(R.GCONV_CASES))
+def test_gconv_cases_are_inside_the_exact_domain_and_match_a_per_group_loop(name):
+    g, G, N, H, W, s = R.GCONV_CASES[name][:6]
+    C = g * G
+    assert g % 4 == 0 and (g, G) in R.GCONV_GROUPS
+    sl = lambda i: slice(i * g, (i + 1) * g)
+    o = R.gconv_fwd_operands(name)
+    for variant in R.GCONV_FWD_VARIANTS:
+        ref = R.gconv_fwd_domain(name, o, variant)
+        for h16 in H16S:
+            assert R.has_tie_and_inexact(ref, h16), (variant, h16)
+    loop = _per_group(lambda i: R.conv_fwd_ref(o["x"][..., sl(i)], o["w"][sl(i)], 3, s, 1, o["scale"][sl(i)], o["shift"][sl(i)], None, True), G)
+    assert torch.equal(loop, R.gconv_fwd_domain(name, o, "scale_shift_relu"))
+    for t in (o["x"], o["w"]):
+        assert all(torch.equal(t.to(h).float(), t) for h in H16S)
+    o = R.gconv_dgrad_operands(name)
+    for variant in R.GCONV_DGRAD_VARIANTS:
+        ref = R.gconv_dgrad_domain(name, o, variant)
+        for h16 in H16S:
+            assert R.has_tie_and_inexact(ref, h16), (variant, h16)
+    for t in (o["dy"], o["w"], o["mask"], o["res"]):
+        assert all(torch.equal(t.to(h).float(), t) for h in H16S)
+    ws = o["w"] * o["scale"][:, None]
+    loop = _per_group(lambda i: R.conv_dgrad_ref(o["dy"][..., sl(i)], ws[sl(i)], (N, H, W, g), 3, s, 1, o["mask"][..., sl(i)],
+                                                 o["res"][..., sl(i)]), G)
+    assert torch.equal(loop, R.gconv_dgrad_domain(name, o, "scale_mask_residual"))
+    o = R.gconv_wgrad_operands(name)
+    for use_sc in (False, True):
+        R.gconv_wgrad_domain(name, o, use_sc, False)
+    got = R.gconv_wgrad_domain(name, o, True, True)
+    loop = torch.cat([R.conv_wgrad_ref(o["x"][..., sl(i)], o["dy"][..., sl(i)], 3, s, 1, o["scale"][sl(i)], o["dw0"][sl(i)])[0] for i in range(G)])
+    assert torch.equal(loop, got)
+
+
+def test_gconv_shapes_reach_the_thread_tile_edges_and_the_split_boundaries():
+    hw = {(H, W, s): R.gconv_out_hw(H, W, s) for _, H, W in R.GCONV_SHAPES for s in (1, 2)}
+    assert hw[(2, 3, 1)][1] < R.GPX and hw[(1, 1, 2)] == (1, 1)
+    assert hw[(6, 8, 2)] == (3, 4) and hw[(6, 8, 1)][1] % R.GPX == 0 and hw[(7, 9, 2)][1] % R.GPX != 0
+    for g, G in R.GCONV_GROUPS:
+        C = g * G
+        (s1, per1), (s2, per2) = R.gconv_wgrad_splits(3, 7, 9, C, G), R.gconv_wgrad_splits(3, 4, 5, C, G)
+        assert (s1, per1) == (6, 32) and per1 % 9 != 0 and per1 % 63 != 0        # stride 1: splits begin mid-row and mid-image
+        assert (s2, per2) == (2, 30) and per2 % 20 != 0                          # stride 2: the second split begins mid-image
+    assert (12 // 4) & (12 // 4 - 1) != 0                                        # (4, 3): three channel quads
+
+
+@pytest.mark.gpu
+def test_restated_split_counts_equal_the_library():
+    from ubteacher import hip
+    lib = hip.load()
+    for N, H, W, C, K, k, s, p in R.F32_WGRAD.values():
+        OH, OW = R._out_hw(H, W, k, s, p)
+        assert lib.utv2_conv2d_wgrad_splits(N, OH, OW, K, k * k * C) == R.f32_wgrad_splits(N * OH * OW, K, k * k * C)
+    for C, K in R.F32_ML.values():
+        for k in (1, 3):
+            P = R.F32_ML_N * sum(h * w for h, w in R.F32_ML_LEVELS)
+            assert lib.utv2_conv2d_wgrad_splits(1, 1, P, K, k * k * C) == R.f32_wgrad_splits(P, K, k * k * C)
+    for g, G, N, H, W, s in [c[:6] for c in R.GCONV_CASES.values()]:
+        OH, OW = R.gconv_out_hw(H, W, s)
+        assert lib.utv2_gconv3x3_wgrad_splits(N, OH, OW, g * G, G) == R.gconv_wgrad_splits(N, OH, OW, g * G, G)[0]
