@@ -209,6 +209,74 @@ def test_one_row_training_set_raises_before_any_launch():
     assert tuple(bn(torch.ones((1, C), device="cuda"), ops.LevelMeta(1, [(1, 1)])).shape) == (1, C)
 
 
+BN_ENTRIES = ("stats_partial", "reduce", "finalize", "apply_relu", "bwd_partial", "bwd_apply")
+BN_TILE_ENTRIES = ("stats_partial", "apply_relu", "bwd_partial", "bwd_apply")        # the entries that walk the [P, C] activation
+
+
+def bn_raw(entry, t, sets, nsets=None, P=67, C=8, nlevels=2, count_mul=1, mode=0, **ptr):
+    """return code of the raw entry utv2_bn_<entry> on the tensors of `t` (a name in `ptr` replaces that tensor's pointer: an int or None)"""
+    import ctypes
+    from ubteacher import hip
+    p = lambda name: ptr[name] if name in ptr else t[name].data_ptr()
+    row0, rows, level = (ctypes.cast(hip._iarr([s[k] for s in sets]), hip.c_p) for k in range(3))
+    n, s = len(sets) if nsets is None else nsets, hip._stream()
+    args = dict(
+        stats_partial=lambda: (p("x"), 0, p("partial"), P, C, n, row0, rows, s),
+        reduce=lambda: (p("partial"), p("out"), C, n, rows, 0, s),
+        finalize=lambda: (p("out"), p("gamma"), p("rm"), p("rv"), p("mean"), p("rstd"), p("scale"), C, nlevels, n, rows, level, R.EPS, R.MOMENTUM,
+                          mode, count_mul, 0, s),
+        apply_relu=lambda: (p("x"), p("y"), 0, p("mean"), p("scale"), p("beta"), P, C, nlevels, n, row0, rows, level, s),
+        bwd_partial=lambda: (p("dy"), p("y"), p("x"), 0, p("mean"), p("rstd"), p("partial"), P, C, n, row0, rows, s),
+        bwd_apply=lambda: (p("dy"), p("y"), p("x"), p("dx"), 0, p("mean"), p("rstd"), p("gamma"), p("out"), p("dgamma"), p("dbeta"), P, C, nlevels,
+                           n, row0, rows, level, count_mul, s))[entry]()
+    return getattr(hip.load(), "utv2_bn_" + entry)(*args)
+
+
+def test_argument_gate_rejects_without_launching():
+    """every bad argument of the list gives UTV2_EARG (-1000) from every entry it concerns and nothing is launched (all outputs keep
+    their fill); one well-formed call per entry returns 0.  What the entries accept although it looks odd is recorded at the end:
+    reduce and finalize take any C >= 1 (they touch no quads), a one-row set is fine in eval mode and with count_mul = 2."""
+    from ubteacher import hip
+    select("fp32")
+    FILL = -7.0
+    sets, P, C, Lv = [(0, 65, 0), (65, 2, 1)], 67, 8, 2          # three chunks
+    f32 = lambda *s: torch.full(s, FILL, device="cuda")
+    f64 = lambda *s: torch.full(s, FILL, dtype=torch.float64, device="cuda")
+    t = dict(x=f32(P + 1, C), dy=f32(P + 1, C), y=f32(P + 1, C), dx=f32(P + 1, C),      # a spare row: the shifted pointer stays inside
+             partial=f64(3, 2, C), out=f64(2, 2, C), mean=f64(2, C), rstd=f64(2, C), scale=f64(2, C),
+             gamma=f32(Lv, C), beta=f32(Lv, C), rm=f32(Lv, C), rv=f32(Lv, C), dgamma=f32(Lv, C), dbeta=f32(Lv, C))
+    bad = [
+        ("nsets 0", BN_ENTRIES, dict(nsets=0)),
+        ("nsets 17", BN_ENTRIES, dict(sets=[(2 * i, 2, 0) for i in range(17)])),
+        ("a set of 0 rows", BN_ENTRIES, dict(sets=[(0, 65, 0), (65, 0, 1)])),
+        ("row0 + rows > P", BN_TILE_ENTRIES, dict(sets=[(0, 65, 0), (65, 3, 1)])),
+        ("level == nlevels", ("finalize", "apply_relu", "bwd_apply"), dict(sets=[(0, 65, 0), (65, 2, 2)])),
+        ("C 6", BN_TILE_ENTRIES, dict(C=6)),
+        ("activation pointer one element off", BN_TILE_ENTRIES, dict(x=t["x"].data_ptr() + 4)),
+        ("null partial", ("stats_partial", "reduce", "bwd_partial"), dict(partial=None)),
+        ("count_mul 0", ("finalize", "bwd_apply"), dict(count_mul=0)),
+        ("mode 2", ("finalize",), dict(mode=2)),
+        ("training finalize, rows * count_mul = 1", ("finalize",), dict(sets=[(0, 65, 0), (65, 1, 1)])),
+    ]
+    for label, entries, kw in bad:
+        for e in entries:
+            assert bn_raw(e, t, **dict(dict(sets=sets), **kw)) == -1000, (label, e)
+    st = hip.BnSets(sets, Lv)
+    chunks = hip.load().utv2_bn_chunks
+    assert chunks(0, st.p_rows) == -1000 and chunks(17, st.p_rows) == -1000 and chunks(2, None) == -1000 and chunks(2, st.p_rows) == 3
+    torch.cuda.synchronize()
+    for k, v in t.items():
+        assert bool((v == FILL).all()), "a rejected call wrote %s" % k
+    for e in BN_ENTRIES:
+        assert bn_raw(e, t, sets) == 0, e
+    for e in ("reduce", "finalize"):
+        assert bn_raw(e, t, sets, C=6) == 0, e
+    assert bn_raw("finalize", t, [(0, 65, 0), (65, 1, 1)], mode=1) == 0
+    assert bn_raw("finalize", t, [(0, 65, 0), (65, 1, 1)], count_mul=2) == 0
+    assert bn_raw("finalize", t, sets, mode=1, out=None) == 0         # eval mode reads no moments
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("kind", ["fp32", "bf16", "fp16"])
 def test_nan_activation_stays_nan_as_in_torch(kind):
     """torch's ReLU hands a NaN on (relu(nan) is nan) and gives it no gradient (nan > 0 is false): eval mode, so that the NaN does not

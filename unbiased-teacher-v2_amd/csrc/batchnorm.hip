@@ -10,6 +10,7 @@
 // The two moments are carried in fp64 from the first add on (the square of a 24-bit value is exact in fp64), so var = E[x^2] - mean^2
 // is taken in fp64: a channel of mean 300 and spread 0.05 keeps 8 significant digits of its variance.  No fp32 E[x^2] - mean^2.
 #include <stdint.h>
+#include <initializer_list>
 #include "common.h"
 
 #define UTV2_BN_MAX_SETS 16
@@ -26,22 +27,21 @@ struct BnSets {
   int chunk0[UTV2_BN_MAX_SETS + 1];  // first chunk of the set; [n] = number of chunks
 };
 
-// Host tables -> the kernel argument.  `rows` is always needed (it defines the chunks); an entry point whose kernels do not place rows
-// in the activation passes row0 == NULL, one whose kernels touch no per-level matrix passes level == NULL: what is given is validated
-// (rows inside [0, P), levels inside [0, nlevels)), what is not given is zero and unused.
-static int bn_fill_sets(BnSets& st, int nsets, const int* row0, const int* rows, const int* level, int nlevels, int64_t P) {
-  if (nsets < 1 || nsets > UTV2_BN_MAX_SETS || !rows) return UTV2_EARG;
+static inline int bn_chunks_of(int rows) { return (rows + BN_CHUNK - 1) / BN_CHUNK; }
+// Host tables -> the kernel argument.  `rows` is always needed (it defines the chunks); `need` says which other tables the entry's
+// kernels use: BN_ROW0 when they place rows in the activation, BN_LEVEL when they touch a per-level matrix.  What is needed must be
+// given and is validated (rows inside [0, P), levels inside [0, nlevels)); what is not needed is not read, zero in `st` and unused.
+enum { BN_ROWS_ONLY = 0, BN_ROW0 = 1, BN_LEVEL = 2 };
+static int bn_fill_sets(BnSets& st, int need, int nsets, const int* row0, const int* rows, const int* level, int nlevels, int64_t P) {
+  const bool pos = need & BN_ROW0, lev = need & BN_LEVEL;
+  if (nsets < 1 || nsets > UTV2_BN_MAX_SETS || !rows || (pos && !row0) || (lev && !level)) return UTV2_EARG;
   st.n = nsets;
   int c = 0;
   for (int s = 0; s < nsets; ++s) {
-    if (rows[s] < 1) return UTV2_EARG;
-    if (row0 && (row0[s] < 0 || (int64_t)row0[s] + rows[s] > P)) return UTV2_EARG;
-    if (level && (level[s] < 0 || level[s] >= nlevels)) return UTV2_EARG;
-    st.row0[s] = row0 ? row0[s] : 0;
-    st.rows[s] = rows[s];
-    st.level[s] = level ? level[s] : 0;
+    if (rows[s] < 1 || (pos && (row0[s] < 0 || (int64_t)row0[s] + rows[s] > P)) || (lev && (level[s] < 0 || level[s] >= nlevels))) return UTV2_EARG;
+    st.row0[s] = pos ? row0[s] : 0, st.rows[s] = rows[s], st.level[s] = lev ? level[s] : 0;
     st.chunk0[s] = c;
-    c += (rows[s] + BN_CHUNK - 1) / BN_CHUNK;
+    c += bn_chunks_of(rows[s]);
   }
   st.chunk0[nsets] = c;
   return UTV2_OK;
@@ -56,57 +56,78 @@ __device__ __forceinline__ void bn_chunk(const BnSets& st, int chunk, int& s, in
   nr = min(BN_CHUNK, st.rows[s] - off);
 }
 
+// A thread's tile in the five chunk x 256-channel kernels: channel quad q (channels c .. c + 3), row lane rl, which takes rows rl,
+// rl + BN_LANES, ... < nr of the chunk that starts at row r0 of set s.  c may lie past C in the last column block.
+struct BnTile {
+  int q, rl, c, s, r0, nr;
+  __device__ __forceinline__ size_t quad(int r, int C) const { return ((size_t)(r0 + r) * C + c) >> 2; }   // ld4 / st4 index of row r
+};
+__device__ __forceinline__ BnTile bn_tile(const BnSets& st) {
+  BnTile t;
+  t.q = threadIdx.x & 63, t.rl = threadIdx.x >> 6, t.c = blockIdx.y * BN_COLS + t.q * 4;
+  bn_chunk(st, blockIdx.x, t.s, t.r0, t.nr);
+  return t;
+}
+
+// the quad's four fp64 per-channel coefficients from row `row` of an [S][C] (row = s) or [S][2][C] (row = 2 s + k) table
+__device__ __forceinline__ void bn_coef4(const double* __restrict__ tab, size_t row, int C, int c, double (&out)[4]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) out[e] = tab[row * C + c + e];
+}
+// the backward's g = dy * [y > 0] and xhat = (x - mean) * rstd in fp64 (the mask in float, then widened: the value of y > 0 ? (double)dy : 0.0)
+__device__ __forceinline__ void bn_gx(float dy, float y, float x, double mu, double rs, double& g, double& xh) {
+  g = (double)(y > 0.f ? dy : 0.f), xh = ((double)x - mu) * rs;
+}
+// torch's ReLU: a NaN stays a NaN (fmax would make it 0)
+__device__ __forceinline__ double bn_relu(double t) { return t > 0.0 ? t : (t != t ? t : 0.0); }
+
 // lane-ordered sum of the four row lanes' fp64 pairs; result in lane 0 of each quad column.  red: [2][BN_LANES][BN_COLS] doubles
 __device__ __forceinline__ void bn_combine_lanes(double (&a)[4], double (&b)[4], double* red, int q, int rl) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[(0 * BN_LANES + rl) * BN_COLS + q * 4 + e] = a[e];
-    red[(1 * BN_LANES + rl) * BN_COLS + q * 4 + e] = b[e];
-  }
+  for (int e = 0; e < 4; ++e) red[(0 * BN_LANES + rl) * BN_COLS + q * 4 + e] = a[e], red[(1 * BN_LANES + rl) * BN_COLS + q * 4 + e] = b[e];
   __syncthreads();
   if (rl == 0) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       double sa = red[q * 4 + e], sb = red[(BN_LANES)*BN_COLS + q * 4 + e];
 #pragma unroll
-      for (int l = 1; l < BN_LANES; ++l) {
-        sa += red[(0 * BN_LANES + l) * BN_COLS + q * 4 + e];
-        sb += red[(1 * BN_LANES + l) * BN_COLS + q * 4 + e];
-      }
-      a[e] = sa;
-      b[e] = sb;
+      for (int l = 1; l < BN_LANES; ++l) sa += red[(0 * BN_LANES + l) * BN_COLS + q * 4 + e], sb += red[(1 * BN_LANES + l) * BN_COLS + q * 4 + e];
+      a[e] = sa, b[e] = sb;
     }
   }
+}
+
+// stage-1 epilogue: the row lanes combined, then partial[chunk][0][c .. c + 3] = a, [1][...] = b
+__device__ __forceinline__ void bn_store_partial(double (&a)[4], double (&b)[4], double* red, const BnTile& t, int C, double* __restrict__ partial) {
+  bn_combine_lanes(a, b, red, t.q, t.rl);
+  if (t.rl == 0 && t.c < C) {
+    double* p = partial + (size_t)blockIdx.x * 2 * C + t.c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] = a[e], p[C + e] = b[e];
+  }
+}
+
+// Stage 1 of both directions: row(i4, a, b) adds row quad i4's terms into the lane's two fp64 sums, rows in order; then the epilogue.
+template <typename Row>
+__device__ __forceinline__ void bn_stage1(const BnTile& t, int C, double* __restrict__ partial, Row row) {
+  __shared__ double red[2 * BN_LANES * BN_COLS];
+  double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+  if (t.c < C)
+    for (int r = t.rl; r < t.nr; r += BN_LANES) row(t.quad(r, C), a, b);
+  bn_store_partial(a, b, red, t, C, partial);
 }
 
 // stage 1, forward: partial[chunk][0][c] = sum x, [1][c] = sum x^2 over the chunk's rows
 template <typename T>
 __global__ void __launch_bounds__(256) bn_stats_partial_kernel(const T* __restrict__ x, double* __restrict__ partial, BnSets st, int C) {
-  __shared__ double red[2 * BN_LANES * BN_COLS];
-  const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.y * BN_COLS + q * 4;
-  int s, r0, nr;
-  bn_chunk(st, blockIdx.x, s, r0, nr);
-  double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-  if (c < C)
-    for (int r = rl; r < nr; r += BN_LANES) {
-      const f32x4 v = ld4(x, ((size_t)(r0 + r) * C + c) >> 2);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double d = (double)v[e];
-        a[e] += d;
-        b[e] += d * d;
-      }
-    }
-  bn_combine_lanes(a, b, red, q, rl);
-  if (rl == 0 && c < C) {
-    double* p = partial + (size_t)blockIdx.x * 2 * C + c;
+  bn_stage1(bn_tile(st), C, partial, [&](size_t i4, double (&a)[4], double (&b)[4]) {
+    const f32x4 v = ld4(x, i4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      p[e] = a[e];
-      p[C + e] = b[e];
+      const double d = (double)v[e];
+      a[e] += d, b[e] += d * d;
     }
-  }
+  });
 }
 
 // stage 2 (both directions): out[s][k][c] = (sum over the set's chunks of partial[chunk][k][c]) * (divide ? 1 / rows(s) : 1)
@@ -176,27 +197,17 @@ __global__ void bn_finalize_kernel(const double* __restrict__ moments, const flo
 template <typename T>
 __global__ void __launch_bounds__(256) bn_apply_relu_kernel(const T* __restrict__ x, T* __restrict__ y, const double* __restrict__ mean,
                                                             const double* __restrict__ scale, const float* __restrict__ beta, BnSets st, int C) {
-  const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.y * BN_COLS + q * 4;
-  if (c >= C) return;
-  int s, r0, nr;
-  bn_chunk(st, blockIdx.x, s, r0, nr);
+  const BnTile t = bn_tile(st);
+  if (t.c >= C) return;
   double mu[4], sc[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    mu[e] = mean[(size_t)s * C + c + e];
-    sc[e] = scale[(size_t)s * C + c + e];
-  }
-  const f32x4 be = ld4(beta, ((size_t)st.level[s] * C + c) >> 2);
-  for (int r = rl; r < nr; r += BN_LANES) {
-    const size_t i4 = ((size_t)(r0 + r) * C + c) >> 2;
+  bn_coef4(mean, t.s, C, t.c, mu), bn_coef4(scale, t.s, C, t.c, sc);
+  const f32x4 be = ld4(beta, ((size_t)st.level[t.s] * C + t.c) >> 2);
+  for (int r = t.rl; r < t.nr; r += BN_LANES) {
+    const size_t i4 = t.quad(r, C);
     const f32x4 v = ld4(x, i4);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const double t = ((double)v[e] - mu[e]) * sc[e] + (double)be[e];
-      o[e] = (float)(t > 0.0 ? t : (t != t ? t : 0.0));      // torch's ReLU: a NaN stays a NaN (fmax would make it 0)
-    }
+    for (int e = 0; e < 4; ++e) o[e] = (float)bn_relu(((double)v[e] - mu[e]) * sc[e] + (double)be[e]);
     st4(y, i4, o);
   }
 }
@@ -206,39 +217,18 @@ template <typename T>
 __global__ void __launch_bounds__(256) bn_bwd_partial_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
                                                              const double* __restrict__ mean, const double* __restrict__ rstd,
                                                              double* __restrict__ partial, BnSets st, int C) {
-  __shared__ double red[2 * BN_LANES * BN_COLS];
-  const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.y * BN_COLS + q * 4;
-  int s, r0, nr;
-  bn_chunk(st, blockIdx.x, s, r0, nr);
-  double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-  if (c < C) {
-    double mu[4], rs[4];
+  const BnTile t = bn_tile(st);
+  double mu[4], rs[4];
+  if (t.c < C) bn_coef4(mean, t.s, C, t.c, mu), bn_coef4(rstd, t.s, C, t.c, rs);
+  bn_stage1(t, C, partial, [&](size_t i4, double (&a)[4], double (&b)[4]) {
+    const f32x4 g = ld4(dy, i4), yy = ld4(y, i4), xx = ld4(x, i4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      mu[e] = mean[(size_t)s * C + c + e];
-      rs[e] = rstd[(size_t)s * C + c + e];
+      double ge, xh;
+      bn_gx(g[e], yy[e], xx[e], mu[e], rs[e], ge, xh);
+      a[e] += ge, b[e] += ge * xh;
     }
-    for (int r = rl; r < nr; r += BN_LANES) {
-      const size_t i4 = ((size_t)(r0 + r) * C + c) >> 2;
-      const f32x4 g = ld4(dy, i4), yy = ld4(y, i4), xx = ld4(x, i4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float ge = yy[e] > 0.f ? g[e] : 0.f;
-        a[e] += (double)ge;
-        b[e] += (double)ge * (((double)xx[e] - mu[e]) * rs[e]);
-      }
-    }
-  }
-  bn_combine_lanes(a, b, red, q, rl);
-  if (rl == 0 && c < C) {
-    double* p = partial + (size_t)blockIdx.x * 2 * C + c;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      p[e] = a[e];
-      p[C + e] = b[e];
-    }
-  }
+  });
 }
 
 // parameter gradients: dgamma[level] += sum g * xhat, dbeta[level] += sum g, the sets of a level in order; sums of several ranks
@@ -261,63 +251,66 @@ __global__ void __launch_bounds__(256) bn_bwd_dx_kernel(const T* __restrict__ dy
                                                         const double* __restrict__ mean, const double* __restrict__ rstd,
                                                         const float* __restrict__ gamma, const double* __restrict__ sums, T* __restrict__ dx,
                                                         BnSets st, int C, int count_mul) {
-  const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.y * BN_COLS + q * 4;
-  if (c >= C) return;
-  int s, r0, nr;
-  bn_chunk(st, blockIdx.x, s, r0, nr);
-  const f32x4 ga = ld4(gamma, ((size_t)st.level[s] * C + c) >> 2);
-  const double n = (double)st.rows[s] * (double)count_mul;
+  const BnTile t = bn_tile(st);
+  if (t.c >= C) return;
+  const f32x4 ga = ld4(gamma, ((size_t)st.level[t.s] * C + t.c) >> 2);
+  const double n = (double)st.rows[t.s] * (double)count_mul;
   double mu[4], rs[4], mg[4], mgx[4], k[4];   // fp64 throughout, as in the apply pass
+  bn_coef4(mean, t.s, C, t.c, mu), bn_coef4(rstd, t.s, C, t.c, rs);
+  bn_coef4(sums, (size_t)t.s * 2 + 0, C, t.c, mg), bn_coef4(sums, (size_t)t.s * 2 + 1, C, t.c, mgx);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    mu[e] = mean[(size_t)s * C + c + e];
-    rs[e] = rstd[(size_t)s * C + c + e];
-    mg[e] = sums[((size_t)s * 2 + 0) * C + c + e] / n;
-    mgx[e] = sums[((size_t)s * 2 + 1) * C + c + e] / n;
-    k[e] = (double)ga[e] * rs[e];
-  }
-  for (int r = rl; r < nr; r += BN_LANES) {
-    const size_t i4 = ((size_t)(r0 + r) * C + c) >> 2;
+  for (int e = 0; e < 4; ++e) mg[e] = mg[e] / n, mgx[e] = mgx[e] / n, k[e] = (double)ga[e] * rs[e];
+  for (int r = t.rl; r < t.nr; r += BN_LANES) {
+    const size_t i4 = t.quad(r, C);
     const f32x4 g = ld4(dy, i4), yy = ld4(y, i4), xx = ld4(x, i4);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const double ge = yy[e] > 0.f ? (double)g[e] : 0.0;
-      const double xh = ((double)xx[e] - mu[e]) * rs[e];
+      double ge, xh;
+      bn_gx(g[e], yy[e], xx[e], mu[e], rs[e], ge, xh);
       o[e] = (float)(k[e] * ((ge - mg[e]) - xh * mgx[e]));
     }
     st4(dx, i4, o);
   }
 }
 
-static inline bool bn_aligned(const void* p, int dtype) { return p && !((uintptr_t)p & (dtype == UTV2_BF16 ? 7 : 15)); }
+// The argument test of all six entries.  Every pointer non-null; BN_F32Q ones (fp32 read as quads) 16-byte aligned, BN_ACTQ ones (quads of
+// the activation type `dtype`) 8 or 16 bytes.  C: whole quads when the entry's kernels walk quads, else >= 1.  Then the set tables -> st.
+enum BnAlign { BN_ANY, BN_F32Q, BN_ACTQ };
+struct BnPtr { const void* p; BnAlign a; };
+static int bn_gate(BnSets& st, int need, int nsets, const int* row0, const int* rows, const int* level, int nlevels, int64_t P,
+                   std::initializer_list<BnPtr> ptrs, int dtype, int C, bool quads) {
+  for (const BnPtr& q : ptrs) {
+    if (!q.p || ((uintptr_t)q.p & (q.a == BN_ANY ? 0 : (q.a == BN_ACTQ && dtype == UTV2_BF16) ? 7 : 15))) return UTV2_EARG;
+  }
+  if (quads ? (C < 4 || (C & 3)) : C < 1) return UTV2_EARG;
+  return bn_fill_sets(st, need, nsets, row0, rows, level, nlevels, P);
+}
+static inline dim3 bn_grid(const BnSets& st, int C) { return dim3(st.chunk0[st.n], cdiv(C, BN_COLS)); }
 
 extern "C" {
 
 int utv2_bn_chunks(int nsets, const int* set_rows_host) {
   if (nsets < 1 || nsets > UTV2_BN_MAX_SETS || !set_rows_host) return UTV2_EARG;
   int c = 0;
-  for (int s = 0; s < nsets; ++s) c += (set_rows_host[s] + BN_CHUNK - 1) / BN_CHUNK;
+  for (int s = 0; s < nsets; ++s) c += bn_chunks_of(set_rows_host[s]);
   return c;
 }
 
 int utv2_bn_stats_partial(const void* x, int dtype, double* partial, int64_t P, int C, int nsets, const int* set_row0_host,
                           const int* set_rows_host, hipStream_t stream) {
   BnSets st;
-  if (!set_row0_host || bn_fill_sets(st, nsets, set_row0_host, set_rows_host, nullptr, 0, P) != UTV2_OK) return UTV2_EARG;
-  if (!bn_aligned(x, dtype) || !partial || C < 4 || (C & 3)) return UTV2_EARG;
-  const dim3 grid(st.chunk0[st.n], (C + BN_COLS - 1) / BN_COLS);
+  if (bn_gate(st, BN_ROW0, nsets, set_row0_host, set_rows_host, nullptr, 0, P, {{x, BN_ACTQ}, {partial, BN_ANY}}, dtype, C, true)) return UTV2_EARG;
   with_type(dtype, [&](auto t) {
     using T = TAG_T(t);
-    hipLaunchKernelGGL(bn_stats_partial_kernel<T>, grid, dim3(256), 0, stream, (const T*)x, partial, st, C);
+    hipLaunchKernelGGL(bn_stats_partial_kernel<T>, bn_grid(st, C), dim3(256), 0, stream, (const T*)x, partial, st, C);
   });
   return utv2_launch_status();
 }
 
 int utv2_bn_reduce(const double* partial, double* out, int C, int nsets, const int* set_rows_host, int divide, hipStream_t stream) {
   BnSets st;
-  if (!partial || !out || C < 1 || bn_fill_sets(st, nsets, nullptr, set_rows_host, nullptr, 0, 0) != UTV2_OK) return UTV2_EARG;
+  if (bn_gate(st, BN_ROWS_ONLY, nsets, nullptr, set_rows_host, nullptr, 0, 0, {{partial, BN_ANY}, {out, BN_ANY}}, UTV2_F32, C, false)) return UTV2_EARG;
   hipLaunchKernelGGL(bn_reduce_kernel, dim3((C + 63) / 64, nsets), dim3(64 * BN_SLICES), 0, stream, partial, out, st, C, divide);
   return utv2_launch_status();
 }
@@ -325,10 +318,11 @@ int utv2_bn_reduce(const double* partial, double* out, int C, int nsets, const i
 int utv2_bn_finalize(const double* moments, const float* gamma, float* running_mean, float* running_var, double* mean, double* rstd,
                      double* scale, int C, int nlevels, int nsets, const int* set_rows_host, const int* set_level_host, double eps,
                      double momentum, int mode, int count_mul, int biased_running, hipStream_t stream) {
-  if (!gamma || !running_mean || !running_var || !mean || !rstd || !scale || C < 1 || count_mul < 1 || (mode != 0 && mode != 1)) return UTV2_EARG;
-  if (mode == 0 && !moments) return UTV2_EARG;
+  if (count_mul < 1 || (mode != 0 && mode != 1) || (mode == 0 && !moments)) return UTV2_EARG;
   BnSets st;
-  if (!set_level_host || bn_fill_sets(st, nsets, nullptr, set_rows_host, set_level_host, nlevels, 0) != UTV2_OK) return UTV2_EARG;
+  if (bn_gate(st, BN_LEVEL, nsets, nullptr, set_rows_host, set_level_host, nlevels, 0,
+              {{gamma, BN_ANY}, {running_mean, BN_ANY}, {running_var, BN_ANY}, {mean, BN_ANY}, {rstd, BN_ANY}, {scale, BN_ANY}}, UTV2_F32, C, false))
+    return UTV2_EARG;
   for (int s = 0; s < nsets && mode == 0; ++s)
     if ((int64_t)set_rows_host[s] * count_mul < 2) return UTV2_EARG;   // "Expected more than 1 value per channel"
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, moments, gamma, running_mean, running_var, mean, rstd,
@@ -340,14 +334,12 @@ int utv2_bn_apply_relu(const void* x, void* y, int dtype, const double* mean, co
                        int nlevels, int nsets, const int* set_row0_host, const int* set_rows_host, const int* set_level_host,
                        hipStream_t stream) {
   BnSets st;
-  if (!set_row0_host || !set_level_host || bn_fill_sets(st, nsets, set_row0_host, set_rows_host, set_level_host, nlevels, P) != UTV2_OK) return UTV2_EARG;
-  if (!bn_aligned(x, dtype) || !bn_aligned(y, dtype) || !mean || !scale || !bn_aligned(beta, UTV2_F32) ||
-      C < 4 || (C & 3))
+  if (bn_gate(st, BN_ROW0 | BN_LEVEL, nsets, set_row0_host, set_rows_host, set_level_host, nlevels, P,
+              {{x, BN_ACTQ}, {y, BN_ACTQ}, {mean, BN_ANY}, {scale, BN_ANY}, {beta, BN_F32Q}}, dtype, C, true))
     return UTV2_EARG;
-  const dim3 grid(st.chunk0[st.n], (C + BN_COLS - 1) / BN_COLS);
   with_type(dtype, [&](auto t) {
     using T = TAG_T(t);
-    hipLaunchKernelGGL(bn_apply_relu_kernel<T>, grid, dim3(256), 0, stream, (const T*)x, (T*)y, mean, scale, beta, st, C);
+    hipLaunchKernelGGL(bn_apply_relu_kernel<T>, bn_grid(st, C), dim3(256), 0, stream, (const T*)x, (T*)y, mean, scale, beta, st, C);
   });
   return utv2_launch_status();
 }
@@ -355,13 +347,12 @@ int utv2_bn_apply_relu(const void* x, void* y, int dtype, const double* mean, co
 int utv2_bn_bwd_partial(const void* dy, const void* y, const void* x, int dtype, const double* mean, const double* rstd, double* partial,
                         int64_t P, int C, int nsets, const int* set_row0_host, const int* set_rows_host, hipStream_t stream) {
   BnSets st;
-  if (!set_row0_host || bn_fill_sets(st, nsets, set_row0_host, set_rows_host, nullptr, 0, P) != UTV2_OK) return UTV2_EARG;
-  if (!bn_aligned(dy, dtype) || !bn_aligned(y, dtype) || !bn_aligned(x, dtype) || !mean || !rstd || !partial || C < 4 || (C & 3))
+  if (bn_gate(st, BN_ROW0, nsets, set_row0_host, set_rows_host, nullptr, 0, P,
+              {{dy, BN_ACTQ}, {y, BN_ACTQ}, {x, BN_ACTQ}, {mean, BN_ANY}, {rstd, BN_ANY}, {partial, BN_ANY}}, dtype, C, true))
     return UTV2_EARG;
-  const dim3 grid(st.chunk0[st.n], (C + BN_COLS - 1) / BN_COLS);
   with_type(dtype, [&](auto t) {
     using T = TAG_T(t);
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, grid, dim3(256), 0, stream, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, partial, st, C);
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, bn_grid(st, C), dim3(256), 0, stream, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, partial, st, C);
   });
   return utv2_launch_status();
 }
@@ -370,15 +361,15 @@ int utv2_bn_bwd_apply(const void* dy, const void* y, const void* x, void* dx, in
                       const float* gamma, const double* sums, float* dgamma, float* dbeta, int64_t P, int C, int nlevels, int nsets,
                       const int* set_row0_host, const int* set_rows_host, const int* set_level_host, int count_mul, hipStream_t stream) {
   BnSets st;
-  if (!set_row0_host || !set_level_host || bn_fill_sets(st, nsets, set_row0_host, set_rows_host, set_level_host, nlevels, P) != UTV2_OK) return UTV2_EARG;
-  if (!bn_aligned(dy, dtype) || !bn_aligned(y, dtype) || !bn_aligned(x, dtype) || !bn_aligned(dx, dtype) || !mean || !rstd || !bn_aligned(gamma, UTV2_F32) || !sums || !dgamma || !dbeta || C < 4 || (C & 3) || count_mul < 1)
+  if (count_mul < 1 || bn_gate(st, BN_ROW0 | BN_LEVEL, nsets, set_row0_host, set_rows_host, set_level_host, nlevels, P,
+                               {{dy, BN_ACTQ}, {y, BN_ACTQ}, {x, BN_ACTQ}, {dx, BN_ACTQ}, {mean, BN_ANY}, {rstd, BN_ANY}, {gamma, BN_F32Q},
+                                {sums, BN_ANY}, {dgamma, BN_ANY}, {dbeta, BN_ANY}}, dtype, C, true))
     return UTV2_EARG;
   hipLaunchKernelGGL(bn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, dgamma, dbeta, st, C, count_mul);
-  const dim3 grid(st.chunk0[st.n], (C + BN_COLS - 1) / BN_COLS);
   with_type(dtype, [&](auto t) {
     using T = TAG_T(t);
-    hipLaunchKernelGGL(bn_bwd_dx_kernel<T>, grid, dim3(256), 0, stream, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, gamma, sums, (T*)dx,
-                       st, C, count_mul);
+    hipLaunchKernelGGL(bn_bwd_dx_kernel<T>, bn_grid(st, C), dim3(256), 0, stream, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, gamma, sums,
+                       (T*)dx, st, C, count_mul);
   });
   return utv2_launch_status();
 }

@@ -1206,14 +1206,14 @@ class BatchNormReLU:
         if not self.training:
             mean, rstd, scale = hip.bn_finalize(None, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
                                                 training=False)
-            return hip.bn_apply_relu(x, mean, scale, self.beta.t, st), mean, rstd
-        moments = hip.bn_stats(x, st)
-        W = self.world()
-        if W > 1:   # [D2-recall] NaiveSyncBatchNorm: all-reduce of [mean, meansqr] / world; here in fp64, all sets of the layer at once
-            from .utils import comm
-            moments = comm.reduce_sum(moments) / W
-        mean, rstd, scale = hip.bn_finalize(moments, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
-                                            training=True, count_mul=W, biased_running=W > 1)
+        else:
+            moments = hip.bn_stats(x, st)
+            W = self.world()
+            if W > 1:   # [D2-recall] NaiveSyncBatchNorm: all-reduce of [mean, meansqr] / world; here in fp64, all sets of the layer at once
+                from .utils import comm
+                moments = comm.reduce_sum(moments) / W
+            mean, rstd, scale = hip.bn_finalize(moments, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
+                                                training=True, count_mul=W, biased_running=W > 1)
         return hip.bn_apply_relu(x, mean, scale, self.beta.t, st), mean, rstd
 
 
