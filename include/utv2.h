@@ -742,6 +742,32 @@ int utv2_bn_bwd_apply(const void* dy, const void* y, const void* x, void* dx, in
                       const float* gamma, const double* sums, float* dgamma, float* dbeta, int64_t P, int C, int nlevels, int nsets,
                       const int* set_row0_host, const int* set_rows_host, const int* set_level_host, int count_mul, utv2_stream_t stream);
 
+/* ---- test-time augmentation (TEST.AUG; Detectron2 GeneralizedRCNNWithTTA._inverse_augmented_boxes and the head of _merge_detections
+ * [D2-recall]): the detections of the V views of ONE image, each in its view's pixel frame, brought back to the original image and
+ * packed view-major into one candidate set for utv2_nms_batched.
+ * boxes_host / scores_host / classes_host / valid_host: HOST arrays of V device pointers - view v's padded detections as the inference
+ * chains leave them (boxes fp32 [D][4] xyxy, 16-byte aligned; scores fp32 [D]; classes int32 [D]; valid u8 [D]).
+ * table: DEVICE fp32 [V][UTV2_TTA_STRIDE], the view's inverse transform chain: FLIP (0 / 1), WVIEW (the view's width, read when FLIP),
+ * RX_VIEW / RY_VIEW = fp32(w_loader / w_view) / fp32(h_loader / h_view), RX_LEAD / RY_LEAD = fp32(w_orig / w_loader) /
+ * fp32(h_orig / h_loader) (1 when the loader image is the original), ORIG_H / ORIG_W.
+ * Per slot, in fp32 with one rounding per operation: x <- WVIEW - x when FLIP, (x1, x2) <- (min, max), x *= RX_VIEW, x *= RX_LEAD (y
+ * likewise), clip to [0, ORIG_W] x [0, ORIG_H]; ovalid = valid && score > 1e-8f.  Outputs [V * D] (oboxes [V * D][4], 16-byte aligned);
+ * a slot that is not valid is written as zeros.  One thread per (view, slot), one launch per UTV2_TTA_MAX_VIEWS views, no atomics.
+ * Checked (UTV2_EARG, nothing launched): non-null pointers (each view's included), the alignment, V >= 1, D >= 1, V * D < 2^31. */
+#define UTV2_TTA_MAX_VIEWS 32
+#define UTV2_TTA_STRIDE 8
+#define UTV2_TTA_FLIP 0
+#define UTV2_TTA_WVIEW 1
+#define UTV2_TTA_RX_VIEW 2
+#define UTV2_TTA_RY_VIEW 3
+#define UTV2_TTA_RX_LEAD 4
+#define UTV2_TTA_RY_LEAD 5
+#define UTV2_TTA_ORIG_H 6
+#define UTV2_TTA_ORIG_W 7
+int utv2_tta_collect(const void* const* boxes_host, const void* const* scores_host, const void* const* classes_host,
+                     const void* const* valid_host, const float* table, int V, int D, float* oboxes, float* oscores, int* oclasses,
+                     unsigned char* ovalid, utv2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,10 +83,20 @@ def main(args):
             model_teacher = Trainer.build_model(cfg)
             ensem_ts_model = EnsembleTSModel(model_teacher, model)
             DetectionTSCheckpointer(ensem_ts_model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
-            return Trainer.test(cfg, ensem_ts_model.modelTeacher)
-        from ubteacher.checkpoint import DetectionCheckpointer
-        DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
-        return Trainer.test(cfg, model)
+            model = ensem_ts_model.modelTeacher
+        else:
+            from ubteacher.checkpoint import DetectionCheckpointer
+            DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
+        res = Trainer.test(cfg, model)
+        if cfg.TEST.AUG.ENABLED:
+            # Detectron2's own train_net.py [D2-recall]: res.update(Trainer.test_with_TTA(cfg, model)) - the `_TTA` keys next to the plain ones
+            tta = Trainer.test_with_TTA(cfg, model)
+            if len(cfg.DATASETS.TEST) > 1:
+                for name, r in tta.items():
+                    res[name].update(r)
+            else:
+                res.update(tta)
+        return res
 
     trainer = Trainer(cfg)
     trainer.resume_or_load(resume=args.resume)

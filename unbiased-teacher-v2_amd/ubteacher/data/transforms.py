@@ -32,12 +32,17 @@ class ResizeShortestEdge:
             size = int(rng.integers(self.short_edge_length[0], self.short_edge_length[1] + 1))
         else:
             size = int(rng.choice(self.short_edge_length))
+        return self.output_size(h, w, size, self.max_size)
+
+    @staticmethod
+    def output_size(h, w, size, max_size):
+        """(newh, neww) of an h x w image for the short-edge length `size`"""
         if size == 0:
             return h, w
         scale = size * 1.0 / min(h, w)
         newh, neww = (size, scale * w) if h < w else (scale * h, size)
-        if max(newh, neww) > self.max_size:
-            scale = self.max_size * 1.0 / max(newh, neww)
+        if max(newh, neww) > max_size:
+            scale = max_size * 1.0 / max(newh, neww)
             newh, neww = newh * scale, neww * scale
         return int(newh + 0.5), int(neww + 0.5)
 

@@ -748,6 +748,18 @@ class _TrainerBase:
             results = list(results.values())[0]
         return results
 
+    @classmethod
+    def test_with_TTA(cls, cfg, model):
+        """Detectron2's train_net.py Trainer.test_with_TTA [D2-recall]: the loaders and evaluators of test() on the model behind TEST.AUG
+        (modeling/test_time_augmentation.py), every result key with `_TTA` appended"""
+        from ..modeling.test_time_augmentation import DetectorWithTTA
+        logging.getLogger(__name__).info("Running inference with test-time augmentation ...")
+        res = cls.test(cfg, DetectorWithTTA(cfg, model))
+        names = list(cfg.DATASETS.TEST) or ["synthetic_val"]
+        if len(names) == 1:
+            return OrderedDict((k + "_TTA", v) for k, v in res.items())
+        return OrderedDict((name, OrderedDict((k + "_TTA", v) for k, v in r.items())) for name, r in res.items())
+
 
 class UBTeacherTrainer(_TrainerBase):
     """FCOS trainer (reference trainer.py:38-608)."""

@@ -705,6 +705,9 @@ def scale_cols_bwd_ml_pad16(g2d, ypost2d, rows, ncols, scales, sgrads, cpad):
 
 # --------------------------------------------------------------------------------------------
 # NMS / IoU
+NMS_MAX_CANDIDATES = 64 * 64 * 4   # utv2_nms_batched: next_pow2(M) <= 64 * 64 * NMS_MAXW (csrc/nms.hip), UTV2_EARG above it
+
+
 def nms_batched(boxes, scores, classes, valid, iou_thr, class_aware=True, post_topk=-1, max_out=128):
     """boxes [N,M,4], scores [N,M], classes [N,M] int32, valid [N,M] uint8 ->
     keep [N,max_out] int32 (slot ids, -1 padded, descending score), count [N] int32."""
@@ -1589,6 +1592,35 @@ def aug_to_chw(img):
     out = torch.empty((3, img.shape[0], img.shape[1]), dtype=torch.uint8, device=img.device)
     call("utv2_aug_hwc_to_chw_u8", _p(img), _p(out), img.shape[0] * img.shape[1], _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# test-time augmentation (modeling/test_time_augmentation.py, csrc/tta.hip)
+TTA_STRIDE = 8      # floats per view in the transform table: UTV2_TTA_* of include/utv2.h
+TTA_FLIP, TTA_WVIEW, TTA_RX_VIEW, TTA_RY_VIEW, TTA_RX_LEAD, TTA_RY_LEAD, TTA_ORIG_H, TTA_ORIG_W = range(8)
+
+
+def tta_collect(views, table):
+    """views: V (boxes fp32 [D, 4], scores fp32 [D], classes int32 [D], valid uint8 [D]) tuples, one per view, the padded detections in
+    the view's own pixel frame; table: device fp32 [V, TTA_STRIDE], the views' inverse transform chains.  -> boxes [1, V*D, 4] in the
+    original image's frame and clipped to it, scores [1, V*D], classes [1, V*D], valid [1, V*D] (valid && score > 1e-8), view-major:
+    the candidate set of one image, in the shape nms_batched takes.  One launch (per 32 views); nothing synchronises."""
+    V = len(views)
+    D = int(views[0][1].numel())
+    assert V >= 1 and D >= 1
+    assert table.dtype == torch.float32 and tuple(table.shape) == (V, TTA_STRIDE)
+    for b, s, c, m in views:
+        assert b.dtype == torch.float32 and s.dtype == torch.float32 and c.dtype == torch.int32 and m.dtype == torch.uint8
+        assert b.numel() == 4 * D and s.numel() == D and c.numel() == D and m.numel() == D, "every view carries the same D slots"
+        assert all(t.is_cuda and t.is_contiguous() and t.device == table.device for t in (b, s, c, m)), "contiguous tensors on the table's device"
+    dev = table.device
+    ob = torch.empty((1, V * D, 4), dtype=torch.float32, device=dev)
+    osc = torch.empty((1, V * D), dtype=torch.float32, device=dev)
+    oc = torch.empty((1, V * D), dtype=torch.int32, device=dev)
+    ov = torch.empty((1, V * D), dtype=torch.uint8, device=dev)
+    ptrs = [ctypes.cast((ctypes.c_void_p * V)(*[_p(v[k]) for v in views]), c_p) for k in range(4)]
+    call("utv2_tta_collect", ptrs[0], ptrs[1], ptrs[2], ptrs[3], _p(table), V, D, _p(ob), _p(osc), _p(oc), _p(ov), _stream())
+    return ob, osc, oc, ov
 
 
 # --------------------------------------------------------------------------------------------

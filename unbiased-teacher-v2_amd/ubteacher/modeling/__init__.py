@@ -7,3 +7,4 @@ from .one_stage_detector import OneStageDetector, PseudoProposalNetwork  # noqa:
 from .ts_ensemble import EnsembleTSModel  # noqa: F401
 from .pseudo_generator import PseudoGenerator  # noqa: F401
 from .build import build_model  # noqa: F401
+from .test_time_augmentation import DetectorWithTTA, GeneralizedRCNNWithTTA, tta_views  # noqa: F401

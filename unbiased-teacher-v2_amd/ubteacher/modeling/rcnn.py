@@ -1081,7 +1081,9 @@ class TwoStagePseudoLabGeneralizedRCNN(ArenaModel):
     __call__ = forward
 
     @torch.no_grad()
-    def inference(self, batched_inputs):
+    def detect(self, batched_inputs):
+        """eval-mode inference up to the predictor's output: (padded detections in the network input's pixel frame, image_sizes) - what
+        `inference` rescales, and what test-time augmentation merges across views (modeling/test_time_augmentation.py)"""
         images = [x["image"].to(self.device) for x in batched_inputs]
         x4, image_sizes = hip.preprocess_images(images, self._mean_host, self._std_host, self.backbone.size_divisibility,
                                                  bf16_stem=ops.amp() and not self.backbone.bottom_up.stem.trainable)
@@ -1089,6 +1091,11 @@ class TwoStagePseudoLabGeneralizedRCNN(ArenaModel):
         features = self.backbone(x4)
         proposals, _ = self.proposal_generator(image_sizes, features, None, compute_loss=False)
         dets, _ = self.roi_heads(features, proposals, targets=None, compute_loss=False)
+        return dets, image_sizes
+
+    @torch.no_grad()
+    def inference(self, batched_inputs):
+        dets, image_sizes = self.detect(batched_inputs)
         from .one_stage_detector import detector_postprocess
         out = []
         for inst, inp, size in zip(_dets_to_instances(dets), batched_inputs, image_sizes):
