@@ -1186,6 +1186,7 @@ def gnb_eligible(x2d, w16, k, pad, groups):
     C = x2d.shape[1] // groups
     K = w16.shape[0]
     return (x2d.dtype == h16_dtype() and C % 64 == 0 and k * k * C >= 1024 and K % groups == 0 and (K // groups) % 128 == 0
+            and int((__import__("re").match(r"\s*[+-]?\d+", os.environ.get("UTV2_EPI_PLAIN", "1")) or ["0"])[0]) != 0  # the entry refuses under UTV2_EPI_PLAIN=0 (env_int: atoi)
             and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.shape[0] * x2d.stride(0) < (1 << 31))
 
 

@@ -434,6 +434,18 @@ class Conv:
     def use_bf16_dgrad(self):
         return amp() and self.cout % 8 == 0
 
+    def own_relu_mask(self):
+        """the backward masks dy by the ReLU output - unless every consumer of that output already did (grad_premasked, premask_on)"""
+        return self.relu and not (self.grad_premasked and premask_on())
+
+    def premask(self, x):
+        """x when dx must leave masked by x > 0 (premask_input: x is a ReLU output whose producer makes no mask pass), else None"""
+        return x if (self.premask_input and premask_on()) else None
+
+    def bias_dst(self):
+        """where a 16-bit wgrad adds the bias gradient; None: no bias, or the GroupNorm behind the conv makes it (bias_grad_from_gn)"""
+        return self.bias.g if (self.bias is not None and not self.bias_grad_from_gn()) else None
+
     def __call__(self, x, residual=None, out=None, colscale_handle=None, meta=None):
         """x: NHWC tensor, or a level-first [P, C] matrix with `meta` (one launch for all levels; k x k
         'same' convs only).  colscale_handle: one Handle per level (the Scale layers of a level-first matrix; `meta` required)."""
@@ -479,10 +491,9 @@ class Conv:
                                            relu=self.relu, out=out, groups=self.groups, gn_part=part, **kw)
                 self._gn_part = (y.data_ptr(), part) if part is not None else None
             elif self.groups > 1:   # exact-f32 mode: one dense conv per group (the fp32 kernel has no grouped form)
-                Kg = self.cout // self.groups
-                y = torch.cat([hip.conv2d_ml_fwd(x[:, gi * self.cin:(gi + 1) * self.cin].contiguous(), w[gi * Kg:(gi + 1) * Kg], meta.level_hw,
-                                                 meta.N, scale=None, bias=None if sh is None else sh[gi * Kg:(gi + 1) * Kg], k=self.k,
-                                                 pad=self.pad, relu=self.relu) for gi in range(self.groups)], dim=1)
+                y = torch.cat(_per_group(self, lambda ci, co: hip.conv2d_ml_fwd(
+                    x[:, ci].contiguous(), w[co], meta.level_hw, meta.N, scale=None, bias=None if sh is None else sh[co], k=self.k,
+                    pad=self.pad, relu=self.relu)), dim=1)
             else:
                 y = hip.conv2d_ml_fwd(x, w, meta.level_hw, meta.N, scale=sc, bias=sh, residual=residual, k=self.k, pad=self.pad,
                                       relu=self.relu, out=out, **kw)
@@ -529,145 +540,52 @@ class _ConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def _scale_backward(ctx, dy, y, sc):
-        """Backward of the Scale layers (one per level) on the conv's output y: adds each level's d s_l and returns (the scaled gradient
-        the conv's own backward starts from, gp_ready = that gradient as the zero-padded 16-bit matrix the dgrad reads, or None)."""
-        layer, meta = ctx.layer, ctx.meta
-        s, sg = [h.t for h in ctx.cs], [h.g for h in ctx.cs]
-        if (dy.dtype == torch.float32 and layer.k > 1 and ctx.needs_input_grad[0] and layer.use_bf16_dgrad() and layer.use_bf16_wgrad()
-                and layer.dgrad_cout() != layer.cout and not layer.relu and sc is None and not ctx.has_res
-                and os.environ.get("UTV2_SCALE_BWD_PAD16", "1") != "0"):
-            # the bbox prediction conv (fcos.py:338-364): Scale backward, conversion and zero padding of the gradient in ONE pass, out of
-            # place - no clone of the incoming gradient, no in-place scale, no separate pad pass (568 -> 224 MB on the student batch)
-            return dy, hip.scale_cols_bwd_ml_pad16(dy, y, meta.rows, layer.colscale, s, sg, layer.dgrad_cout())
-        g = dy.clone()
-        hip.scale_cols_bwd_ml(g, y, meta.rows, layer.colscale, s, sg)   # all levels in two launches, in place
-        return g, None
+    def _grad_in(ctx, dy, y):
+        """Stage 1, elementwise: Scale backward, ReLU mask, FrozenBN multiplier -> (g: what dgrad and wgrad start from, gres: the residual's
+        gradient or None, gp_ready: g as the zero-padded 16-bit matrix the dgrad reads, or None, wsc: the multiplier the dgrad weight image
+        and the wgrad row scale still apply - `fold`: AMP, FrozenBN, no bias; only the ReLU mask is left as a pass - else None: g carries it)"""
+        layer, gp_ready = ctx.layer, None
+        sc, _ = layer.scale_shift()
+        if ctx.cs is not None:      # the Scale layers (one per level) on the conv's output y: adds each level's d s_l
+            s, sg = [h.t for h in ctx.cs], [h.g for h in ctx.cs]
+            if (dy.dtype == torch.float32 and layer.k > 1 and ctx.needs_input_grad[0] and layer.use_bf16_dgrad() and layer.use_bf16_wgrad()
+                    and layer.dgrad_cout() != layer.cout and not layer.relu and sc is None and not ctx.has_res
+                    and os.environ.get("UTV2_SCALE_BWD_PAD16", "1") != "0"):
+                # the bbox prediction conv (fcos.py:338-364): Scale backward, conversion and zero padding of the gradient in ONE pass, out of
+                # place - no clone of the incoming gradient, no in-place scale, no separate pad pass (568 -> 224 MB on the student batch)
+                gp_ready = hip.scale_cols_bwd_ml_pad16(dy, y, ctx.meta.rows, layer.colscale, s, sg, layer.dgrad_cout())
+            else:
+                dy = dy.clone()
+                hip.scale_cols_bwd_ml(dy, y, ctx.meta.rows, layer.colscale, s, sg)   # all levels in two launches, in place
+        fold = sc is not None and layer.use_bf16_dgrad() and layer.use_bf16_wgrad() and layer.bias is None
+        relu = layer.own_relu_mask()
+        if fold:
+            g = hip.relu_bwd_scale(dy, y, None) if relu else dy
+            return g, (g if ctx.has_res else None), gp_ready, sc
+        if ctx.has_res:
+            gres = hip.relu_bwd_scale(dy, y, None) if relu else dy
+            return (hip.relu_bwd_scale(gres, None, sc) if sc is not None else gres), gres, gp_ready, None
+        g = hip.relu_bwd_scale(dy, y if relu else None, sc) if (relu or sc is not None) else dy
+        return g, None, gp_ready, None
 
     @staticmethod
     def backward(ctx, dy):
-        layer = ctx.layer
+        layer, meta = ctx.layer, ctx.meta
         if layer.gconv:
             return _ConvFn._backward_grouped(ctx, dy)
         x, y = ctx.saved_tensors
         dy = dy.contiguous()
         if not x.is_contiguous() and not (layer.use_bf16_wgrad() and layer.use_bf16_dgrad()):
             x = x.contiguous()   # a column slice (paired towers) in exact-f32 mode: the fp32 kernels take dense matrices
-        sc, _ = layer.scale_shift()
-        meta = ctx.meta
-        gp_ready = None
-        if ctx.cs is not None:
-            dy, gp_ready = _ConvFn._scale_backward(ctx, dy, y, sc)
-        gres = None
-        d16 = layer.use_bf16_dgrad()
-        # AMP + FrozenBN: the BN multiplier is folded into the dgrad weight image and the wgrad slab reduction, so the
-        # only elementwise backward pass left is the ReLU mask (none at all for the ReLU-less shortcut convs)
-        fold = sc is not None and d16 and layer.use_bf16_wgrad() and layer.bias is None
-        wsc = sc if fold else None
-        relu = layer.relu and not (layer.grad_premasked and premask_on())   # premasked: dy arrives with the ReLU mask applied
-        if fold:
-            g = hip.relu_bwd_scale(dy, y, None) if relu else dy
-            gres = g if ctx.has_res else None
-        elif ctx.has_res:
-            gm = hip.relu_bwd_scale(dy, y if relu else None, None) if relu else dy
-            gres = gm
-            g = hip.relu_bwd_scale(gm, None, sc) if sc is not None else gm
-        else:
-            if relu or sc is not None:
-                g = hip.relu_bwd_scale(dy, y if relu else None, sc)
-            else:
-                g = dy
-        dx = None
-        bias_done = False
+        g, gres, gp_ready, wsc = _ConvFn._grad_in(ctx, dy, y)
         if meta is not None and layer.k > 1:
-            G = layer.groups
-            Kg = layer.cout // G
-            if ctx.needs_input_grad[0]:
-                if d16:
-                    gp = gp_ready if gp_ready is not None else (g if layer.dgrad_cout() == layer.cout else hip.pad_cols_bf16(g, layer.dgrad_cout()))
-                    other = ctx.fanin.take() if ctx.fanin is not None else None
-                    if other is not None and (other.dtype != x.dtype or tuple(other.shape) != tuple(x.shape)):
-                        raise RuntimeError("FanIn: stored gradient does not match the conv input")
-                    # x a column half of a paired tower's output: the gradient is written straight into its half of ONE [P, 2C] buffer
-                    # (row pitch 2C), which ColPair's backward hands on as the gradient of the whole matrix - no cat pass
-                    dest = ctx.pair[0].grad_half(ctx.pair[1], x) if (ctx.pair is not None and other is None) else None
-                    wt = layer.wt16(wsc)
-                    if (ctx.gnb is not None and other is None and dest is None and x.dtype == hip.h16_dtype()
-                            and hip.gnb_eligible(gp, wt, layer.k, layer.k - 1 - layer.pad, G)):
-                        src, gx, bits = ctx.gnb
-                        part = hip.gnb_part_buffer(x.shape[0], x.shape[1], x.device)
-                        dx = hip.conv2d_ml_fwd_bf16(gp, wt, meta.level_hw, meta.N, k=layer.k, pad=layer.k - 1 - layer.pad, out_dtype=x.dtype,
-                                                    groups=G, gnb=(bits, gx, part))
-                        src._gnb_bwd = (dx.data_ptr(), part)
-                    else:
-                        dx = hip.conv2d_ml_fwd_bf16(gp, wt, meta.level_hw, meta.N, k=layer.k, pad=layer.k - 1 - layer.pad,
-                                                    residual=other, out_dtype=x.dtype, out=dest, groups=G)
-                elif G > 1:
-                    dx = torch.cat([hip.conv2d_ml_dgrad(g[:, gi * Kg:(gi + 1) * Kg].contiguous(),
-                                                        hip.weight_flip_transpose(layer.w.t[gi * Kg:(gi + 1) * Kg], Kg, layer.k, layer.k, layer.cin),
-                                                        meta.level_hw, meta.N, layer.k, layer.pad) for gi in range(G)], dim=1)
-                else:
-                    dx = hip.conv2d_ml_dgrad(g, layer.wt(), meta.level_hw, meta.N, layer.k, layer.pad)
-            if layer.use_bf16_wgrad():
-                # the 80-channel prediction convs: the weight gradient reads the zero-padded bf16 copy of the gradient the dgrad was given
-                # (its leading `cout` columns; the same RNE-rounded values the kernel would make of the fp32 gradient while staging it -
-                # identical results from 60 % of the bytes and no conversion work in the staging loop)
-                gw = gp[:, :layer.cout] if (d16 and ctx.needs_input_grad[0] and gp is not g) else g
-                _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(
-                    x, gw, layer.w.g, hip.rowinfo_ml(meta.N, meta.level_hw, layer.pad, layer.k, x.device), layer.cin, layer.k, layer.k,
-                    accumulate=True, db=layer.bias.g if (layer.bias is not None and not layer.bias_grad_from_gn()) else None, rowscale=wsc,
-                    groups=G, x_pitch=x.stride(0)), x, gw, key=layer)
-                bias_done = True
-            elif G > 1:
-                for gi in range(G):
-                    xg, gg = x[:, gi * layer.cin:(gi + 1) * layer.cin].contiguous(), g[:, gi * Kg:(gi + 1) * Kg].contiguous()
-                    _wgrad_launch(lambda xg=xg, gg=gg, gi=gi: hip.conv2d_ml_wgrad(xg, gg, layer.w.g[gi * Kg:(gi + 1) * Kg], meta.level_hw, meta.N,
-                                                                                   layer.k, layer.pad, accumulate=True), xg, gg, key=layer)
-            else:
-                _wgrad_launch(lambda: hip.conv2d_ml_wgrad(x, g, layer.w.g, meta.level_hw, meta.N, layer.k, layer.pad, accumulate=True), x, g, key=layer)
+            dx, gp = _dgrad_levels(ctx, x, g, gp_ready, wsc) if ctx.needs_input_grad[0] else (None, g)
+            bias_done = _wgrad_levels(layer, meta, x, g, gp, wsc)
         else:
             x4 = x.view(1, x.shape[0], 1, x.shape[1]) if meta is not None else x
             g4 = g.view(1, g.shape[0], 1, g.shape[1]) if meta is not None else g
-            if ctx.needs_input_grad[0]:
-                # premask_input: x is the ReLU output of a fused bottleneck that expects its incoming gradient already masked by x > 0
-                pm = x4 if (layer.premask_input and premask_on()) else None
-                if d16 and layer.k == 1 and layer.stride == 2 and layer.pad == 0:
-                    # only the even input pixels receive gradient: a plain GEMM on the compact grid + a zero-interleave,
-                    # instead of a 4x larger dilated gather that is 3/4 masked
-                    dxc = hip.conv2d_fwd_bf16(g4, layer.wt16(wsc), out_dtype=x.dtype)
-                    dx = hip.zero_interleave2x(dxc, x4.shape[1], x4.shape[2], mask=pm)
-                elif (d16 and layer.k == 3 and layer.stride == 2 and layer.pad == 1 and g4.shape[-1] % 32 == 0
-                      and x4.shape[0] * x4.shape[1] * x4.shape[2] <= 65536):
-                    # small stride-2 3x3 layers (FPN p6 / p7): the dilated-gather dgrad only exists in the generic kernel, whose long K loop
-                    # on a 52-workgroup grid sat on the backward's critical path (78 us alone, ~250 us in the step; -0.12 ms / step); the gradient
-                    # zero-interleaved to the input grid is a plain stride-1 conv for the LDS-DMA kernel (4x the MACs of a tiny layer)
-                    gd = hip.zero_interleave2x(g4.contiguous(), x4.shape[1], x4.shape[2])
-                    dx = hip.conv2d_fwd_bf16(gd, layer.wt16(wsc), pad=1, kh=3, kw=3, out_dtype=x.dtype, mask=pm)
-                elif d16:
-                    gd = g4
-                    if layer.dgrad_cout() != layer.cout:
-                        gd = hip.pad_cols_bf16(g4.reshape(-1, layer.cout), layer.dgrad_cout()).view(g4.shape[:-1] + (layer.dgrad_cout(),))
-                    pb = ctx.x_bits if (pm is not None and relu_bits_on() and x.dtype == hip.h16_dtype()) else None
-                    BITS_STATS["reads"] += pb is not None
-                    dx = hip.conv2d_dgrad_bf16(gd, layer.wt16(wsc), tuple(x4.shape), layer.stride, layer.pad, layer.k, layer.k,
-                                               out_dtype=x.dtype, mask=None if pb is not None else pm, mask_bits=pb)
-                else:
-                    dx = hip.conv2d_dgrad(g4, layer.wt(), tuple(x4.shape), layer.stride, layer.pad, layer.k, layer.k)
-                    if pm is not None:
-                        dx = hip.relu_bwd_scale(dx, x4, None)
-                if meta is not None:
-                    dx = dx.view(x.shape)
-                elif ctx.handoff is not None and pm is not None and dx.dtype == hip.h16_dtype() and ctx.handoff.park(dx):
-                    dx = None    # the next stage's first block adds it where it makes its own gradient of x (GradHandoff)
-            if layer.use_bf16_wgrad():
-                n_, h_, w_, _ = x4.shape
-                ri = hip.rowinfo_nhwc(n_, h_, w_, g4.shape[1], g4.shape[2], layer.stride, layer.pad, layer.k, layer.k, x.device)
-                _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(
-                    x4, g4.reshape(-1, layer.cout), layer.w.g, ri, layer.cin, layer.k, layer.k, accumulate=True,
-                    db=layer.bias.g if (layer.bias is not None and not layer.bias_grad_from_gn()) else None, rowscale=wsc), x4, g4, key=layer)
-                bias_done = True
-            else:
-                _wgrad_launch(lambda: hip.conv2d_wgrad(x4, g4, layer.w.g, layer.stride, layer.pad, layer.k, layer.k, accumulate=True), x4, g4, key=layer)
+            dx = _dgrad_nhwc(ctx, x4, g4, wsc, layer.premask(x4)) if ctx.needs_input_grad[0] else None
+            bias_done = _wgrad_nhwc(layer, x4, g4, wsc)
         if layer.bias is not None and not bias_done:
             _wgrad_launch(lambda: hip.colsum(g.view(-1, layer.cout), layer.bias.g, accumulate=True), g, key=layer)
         if GRAD_SYNC[0] is not None:
@@ -676,26 +594,121 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_grouped(ctx, dy):
-        """grouped conv (ResNeXt conv2): ReLU mask, then dgrad (FrozenBN multiplier folded, the input's ReLU mask in the epilogue when
-        premasked) and wgrad (multiplier as row scale) on the grouped kernels"""
+        """grouped conv (ResNeXt conv2): ReLU mask, then dgrad (FrozenBN multiplier and premask in the epilogue) and wgrad (row scale)"""
         layer = ctx.layer
         x, y = ctx.saved_tensors
         w = layer.gconv_weight()
         g = dy.contiguous()
         if g.dtype != w.dtype:
             g = g.to(w.dtype)
-        relu = layer.relu and not (layer.grad_premasked and premask_on())
-        if relu:
+        if layer.own_relu_mask():
             g = hip.relu_bwd_scale(g, y if y.dtype == g.dtype else y.to(g.dtype), None)
-        sc, _ = layer.scale_shift()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            pm = x if (layer.premask_input and premask_on()) else None
-            dx = hip.gconv3x3_dgrad(g, w, layer.groups, layer.stride, tuple(x.shape), scale=sc, mask=pm, out_dtype=x.dtype)
-        _wgrad_launch(lambda: hip.gconv3x3_wgrad(x, g, layer.w.g, layer.groups, layer.stride, scale=sc, accumulate=True), x, g, key=layer)
+        dx = _dgrad16(layer, g, x.shape, layer.bn.scale, mask=layer.premask(x), out_dtype=x.dtype) if ctx.needs_input_grad[0] else None
+        _wgrad_nhwc(layer, x, g, layer.bn.scale)
         if GRAD_SYNC[0] is not None:
             GRAD_SYNC[0].on_backward_done(_sync_handles(layer))
         return dx, None, None, None, None, None, None
+
+
+# The stages of a conv's backward (DESIGN.md section 32; none keeps state on ctx).  _BottleneckFn chains _wgrad_nhwc / _dgrad16 itself.
+def _per_group(layer, fn):
+    """exact-f32 mode of a grouped level-first conv (no grouped fp32 kernel): [fn(input-channel slice, output-channel slice)] per group"""
+    Kg = layer.cout // layer.groups
+    return [fn(slice(gi * layer.cin, (gi + 1) * layer.cin), slice(gi * Kg, (gi + 1) * Kg)) for gi in range(layer.groups)]
+
+
+def _dgrad_levels(ctx, x, g, gp_ready, wsc):
+    """Input gradient of a level-first k x k layer -> (dx, gp: the matrix the 16-bit dgrad read - g, or its zero-padded 16-bit copy, whose
+    leading columns the wgrad then reads).  In the 16-bit kernel's epilogue: FanIn's stored gradient of x is added (`residual`); x a column
+    half of a paired tower's output (ColPair): dx goes straight into its half of ONE [P, 2C] buffer, no cat pass; ctx.gnb (x is the output of
+    GroupNorm `src`): the ReLU mask of x is applied, GroupNorm backward's first reduction left in `part`.  That hand-over lives on the LAYERS,
+    matched by data_ptr, not in autograd state: GroupNormReLU._fwd sets src._gnb_fwd = (y's pointer, its input, bit plane), this conv's forward
+    takes it (ctx.gnb); src._gnb_bwd = (dx's pointer, part) is set here and taken by _GNFn.backward when its dy is that dx (else: unfused)."""
+    layer, meta, G, k = ctx.layer, ctx.meta, ctx.layer.groups, ctx.layer.k
+    if layer.use_bf16_dgrad():
+        gp = gp_ready if gp_ready is not None else (g if layer.dgrad_cout() == layer.cout else hip.pad_cols_bf16(g, layer.dgrad_cout()))
+        other = ctx.fanin.take() if ctx.fanin is not None else None
+        if other is not None and (other.dtype != x.dtype or tuple(other.shape) != tuple(x.shape)):
+            raise RuntimeError("FanIn: stored gradient does not match the conv input")
+        dest = ctx.pair[0].grad_half(ctx.pair[1], x) if (ctx.pair is not None and other is None) else None
+        wt = layer.wt16(wsc)
+        if (ctx.gnb is not None and other is None and dest is None and x.dtype == hip.h16_dtype()
+                and hip.gnb_eligible(gp, wt, k, k - 1 - layer.pad, G)):
+            src, gx, bits = ctx.gnb
+            part = hip.gnb_part_buffer(x.shape[0], x.shape[1], x.device)
+            dx = hip.conv2d_ml_fwd_bf16(gp, wt, meta.level_hw, meta.N, k=k, pad=k - 1 - layer.pad, out_dtype=x.dtype, groups=G,
+                                        gnb=(bits, gx, part))
+            src._gnb_bwd = (dx.data_ptr(), part)
+            return dx, gp
+        return hip.conv2d_ml_fwd_bf16(gp, wt, meta.level_hw, meta.N, k=k, pad=k - 1 - layer.pad, residual=other, out_dtype=x.dtype,
+                                      out=dest, groups=G), gp
+    if G > 1:
+        return torch.cat(_per_group(layer, lambda ci, co: hip.conv2d_ml_dgrad(
+            g[:, co].contiguous(), hip.weight_flip_transpose(layer.w.t[co], layer.cout // G, k, k, layer.cin), meta.level_hw, meta.N, k,
+            layer.pad)), dim=1), g
+    return hip.conv2d_ml_dgrad(g, layer.wt(), meta.level_hw, meta.N, k, layer.pad), g
+
+
+def _wgrad_levels(layer, meta, x, g, gp, wsc):
+    """Weight gradient of a level-first k x k layer (16-bit with the bias gradient fused, exact-f32 per group or dense) -> bias done?"""
+    if layer.use_bf16_wgrad():
+        # the 80-channel prediction convs read the leading `cout` columns of the zero-padded 16-bit copy the dgrad was given (the same
+        # RNE-rounded values the kernel would make of the fp32 gradient while staging it: 60 % of the bytes, no conversion work)
+        gw = gp[:, :layer.cout] if gp is not g else g
+        _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(
+            x, gw, layer.w.g, hip.rowinfo_ml(meta.N, meta.level_hw, layer.pad, layer.k, x.device), layer.cin, layer.k, layer.k,
+            accumulate=True, db=layer.bias_dst(), rowscale=wsc, groups=layer.groups, x_pitch=x.stride(0)), x, gw, key=layer)
+        return True
+    if layer.groups > 1:
+        def one(ci, co):
+            xg, gg = x[:, ci].contiguous(), g[:, co].contiguous()
+            _wgrad_launch(lambda: hip.conv2d_ml_wgrad(xg, gg, layer.w.g[co], meta.level_hw, meta.N, layer.k, layer.pad, accumulate=True),
+                          xg, gg, key=layer)
+        _per_group(layer, one)
+    else:
+        _wgrad_launch(lambda: hip.conv2d_ml_wgrad(x, g, layer.w.g, meta.level_hw, meta.N, layer.k, layer.pad, accumulate=True), x, g, key=layer)
+    return False
+
+
+def _dgrad_nhwc(ctx, x4, g4, wsc, pm):
+    """Input gradient of an NHWC layer (or a 1x1 layer on a level-first matrix as [1, P, 1, C]); pm: Conv.premask.  Routes: 16-bit 1x1 s2
+    (only the even input pixels receive gradient: a GEMM on the compact grid + a masked zero-interleave, not a 4x larger dilated gather),
+    16-bit small 3x3 s2 (FPN p6 / p7: the zero-interleaved gradient is a stride-1 conv for the LDS-DMA kernel; the generic kernel's long K
+    loop on 52 workgroups cost 0.12 ms / step), 16-bit generic, exact-f32 + mask pass.  None when a GradHandoff took the masked gradient: the next stage's first block adds it to its own gradient of x."""
+    layer, d16 = ctx.layer, ctx.layer.use_bf16_dgrad()
+    if d16 and layer.k == 1 and layer.stride == 2 and layer.pad == 0:
+        dxc = hip.conv2d_fwd_bf16(g4, layer.wt16(wsc), out_dtype=x4.dtype)
+        dx = hip.zero_interleave2x(dxc, x4.shape[1], x4.shape[2], mask=pm)
+    elif (d16 and layer.k == 3 and layer.stride == 2 and layer.pad == 1 and g4.shape[-1] % 32 == 0
+          and x4.shape[0] * x4.shape[1] * x4.shape[2] <= 65536):
+        gd = hip.zero_interleave2x(g4.contiguous(), x4.shape[1], x4.shape[2])
+        dx = hip.conv2d_fwd_bf16(gd, layer.wt16(wsc), pad=1, kh=3, kw=3, out_dtype=x4.dtype, mask=pm)
+    elif d16:
+        gd = g4 if layer.dgrad_cout() == layer.cout else \
+            hip.pad_cols_bf16(g4.reshape(-1, layer.cout), layer.dgrad_cout()).view(g4.shape[:-1] + (layer.dgrad_cout(),))
+        pb = ctx.x_bits if (pm is not None and relu_bits_on() and x4.dtype == hip.h16_dtype()) else None
+        dx = _dgrad16(layer, gd, x4.shape, wsc, mask=pm, mask_bits=pb, out_dtype=x4.dtype)
+    else:
+        dx = hip.conv2d_dgrad(g4, layer.wt(), tuple(x4.shape), layer.stride, layer.pad, layer.k, layer.k)
+        if pm is not None:
+            dx = hip.relu_bwd_scale(dx, x4, None)
+    if ctx.meta is None and ctx.handoff is not None and pm is not None and dx.dtype == hip.h16_dtype() and ctx.handoff.park(dx):
+        return None
+    return dx if ctx.meta is None else dx.view(x4.shape[1], x4.shape[3])
+
+
+def _wgrad_nhwc(layer, x4, g4, wsc):
+    """Weight gradient of an NHWC layer -> bias done?  Grouped kernel, exact-f32, or THE 16-bit form (geometry table + fused bias gradient)"""
+    if layer.gconv:
+        _wgrad_launch(lambda: hip.gconv3x3_wgrad(x4, g4, layer.w.g, layer.groups, layer.stride, scale=wsc, accumulate=True), x4, g4, key=layer)
+        return True
+    if not layer.use_bf16_wgrad():
+        _wgrad_launch(lambda: hip.conv2d_wgrad(x4, g4, layer.w.g, layer.stride, layer.pad, layer.k, layer.k, accumulate=True), x4, g4, key=layer)
+        return False
+    ri = hip.rowinfo_nhwc(x4.shape[0], x4.shape[1], x4.shape[2], g4.shape[1], g4.shape[2], layer.stride, layer.pad, layer.k, layer.k, x4.device)
+    _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(x4, g4.reshape(-1, layer.cout), layer.w.g, ri, layer.cin, layer.k, layer.k, accumulate=True,
+                                                db=layer.bias_dst(), rowscale=wsc), x4, g4, key=layer)
+    return True
 
 
 # ------------------------------------------------------------------------------------------------
@@ -703,30 +716,16 @@ class _ConvFn(torch.autograd.Function):
 # backward of conv1 / conv2 rides in the epilogue of the dgrad that produces their gradient (mask), the identity / shortcut
 # gradient is added in the epilogue of conv1's dgrad (residual) and a stride-2 block interleaves zeros once for both
 # branches.  Left as elementwise work: one ReLU-mask pass over the block output's gradient.
-def _wgrad16(layer, x4, g4):
-    if layer.gconv:
-        _wgrad_launch(lambda: hip.gconv3x3_wgrad(x4, g4, layer.w.g, layer.groups, layer.stride, scale=layer.bn.scale, accumulate=True),
-                      x4, g4, key=layer)
-        return
-    n_, h_, w_, _ = x4.shape
-    ri = hip.rowinfo_nhwc(n_, h_, w_, g4.shape[1], g4.shape[2], layer.stride, layer.pad, layer.k, layer.k, x4.device)
-    _wgrad_launch(lambda: hip.conv2d_wgrad_bf16(x4, g4.reshape(-1, layer.cout), layer.w.g, ri, layer.cin, layer.k, layer.k, accumulate=True,
-                                                rowscale=layer.bn.scale), x4, g4, key=layer)
-
-
-def _dgrad16(layer, g4, in_shape, mask=None, residual=None, post_mask=None, mask_bits=None, post_mask_bits=None):
-    if mask_bits is not None:
-        mask = None
-    if post_mask_bits is not None:
-        post_mask = None
-    if layer.gconv:     # the grouped kernel reads the 16-bit activation for its mask (no bit plane)
+def _dgrad16(layer, g4, in_shape, wsc, mask=None, residual=None, post_mask=None, mask_bits=None, post_mask_bits=None, out_dtype=None):
+    """generic 16-bit NHWC dgrad (wsc: FrozenBN multiplier baked into the weight image), epilogue masks - bit planes where given - and residual"""
+    if layer.gconv:     # the grouped kernel reads the activation for its mask (no bit plane)
         assert post_mask is None and post_mask_bits is None and mask_bits is None
-        return hip.gconv3x3_dgrad(g4, layer.gconv_weight(), layer.groups, layer.stride, tuple(in_shape), scale=layer.bn.scale, mask=mask,
-                                  residual=residual, out_dtype=hip.h16_dtype())
+        return hip.gconv3x3_dgrad(g4, layer.gconv_weight(), layer.groups, layer.stride, tuple(in_shape), scale=wsc, mask=mask,
+                                  residual=residual, out_dtype=out_dtype or hip.h16_dtype())
     BITS_STATS["reads"] += (mask_bits is not None) + (post_mask_bits is not None)
-    return hip.conv2d_dgrad_bf16(g4, layer.wt16(layer.bn.scale), tuple(in_shape), layer.stride, layer.pad, layer.k, layer.k,
-                                 out_dtype=hip.h16_dtype(), mask=mask, residual=residual, post_mask=post_mask, mask_bits=mask_bits,
-                                 post_mask_bits=post_mask_bits)
+    return hip.conv2d_dgrad_bf16(g4, layer.wt16(wsc), tuple(in_shape), layer.stride, layer.pad, layer.k, layer.k,
+                                 out_dtype=out_dtype or hip.h16_dtype(), mask=None if mask_bits is not None else mask, residual=residual,
+                                 post_mask=None if post_mask_bits is not None else post_mask, mask_bits=mask_bits, post_mask_bits=post_mask_bits)
 
 
 class GradHandoff:
@@ -832,20 +831,20 @@ class _BottleneckFn(torch.autograd.Function):
         bx, b1, b2 = ctx.bits
         if pm is None:
             bx = None
-        _wgrad16(c3, y2, gm)
-        g2 = _dgrad16(c3, gm, y2.shape, mask=y2, mask_bits=b2)      # ... through ReLU(conv2): at conv2's BN output
-        _wgrad16(c2, y1, g2)
-        g1 = _dgrad16(c2, g2, y1.shape, mask=y1, mask_bits=b1)
-        _wgrad16(c1, x, g1)
+        _wgrad_nhwc(c3, y2, gm, c3.bn.scale)
+        g2 = _dgrad16(c3, gm, y2.shape, c3.bn.scale, mask=y2, mask_bits=b2)      # ... through ReLU(conv2): at conv2's BN output
+        _wgrad_nhwc(c2, y1, g2, c2.bn.scale)
+        g1 = _dgrad16(c2, g2, y1.shape, c2.bn.scale, mask=y1, mask_bits=b1)
+        _wgrad_nhwc(c1, x, g1, c1.bn.scale)
         if cs is not None:
-            _wgrad16(cs, x, gm)
+            _wgrad_nhwc(cs, x, gm, cs.bn.scale)
         dx = None
         if ctx.needs_input_grad[0]:
             parked = ctx.handoff.take() if ctx.handoff is not None else None   # the FPN lateral's gradient of x (masked by x > 0 there)
             if parked is not None and (parked.dtype != hip.h16_dtype() or tuple(parked.shape) != tuple(x.shape)):
                 raise RuntimeError("GradHandoff: parked gradient of another shape / type")
             if cs is None:
-                dx = _dgrad16(c1, g1, x.shape, residual=gm, post_mask=pm, post_mask_bits=bx)   # identity branch added in the epilogue
+                dx = _dgrad16(c1, g1, x.shape, c1.bn.scale, residual=gm, post_mask=pm, post_mask_bits=bx)   # identity branch added in the epilogue
                 if parked is not None:
                     dx = dx + parked
             elif c1.stride == 2:
@@ -860,10 +859,10 @@ class _BottleneckFn(torch.autograd.Function):
                 assert c1.stride == 1 and cs.k == 1 and cs.pad == 0
                 c = hip.conv2d_fwd_bf16(gm, cs.wt16(cs.bn.scale), out_dtype=hip.h16_dtype())
                 d = hip.zero_interleave2x(c, x.shape[1], x.shape[2], add=parked)
-                dx = _dgrad16(c1, g1, x.shape, residual=d, post_mask=pm, post_mask_bits=bx)
+                dx = _dgrad16(c1, g1, x.shape, c1.bn.scale, residual=d, post_mask=pm, post_mask_bits=bx)
             else:
-                d = _dgrad16(cs, gm, x.shape, residual=parked)
-                dx = _dgrad16(c1, g1, x.shape, residual=d, post_mask=pm, post_mask_bits=bx)
+                d = _dgrad16(cs, gm, x.shape, cs.bn.scale, residual=parked)
+                dx = _dgrad16(c1, g1, x.shape, c1.bn.scale, residual=d, post_mask=pm, post_mask_bits=bx)
         if GRAD_SYNC[0] is not None:
             for l in (c3, c2, c1, cs):
                 if l is not None:
