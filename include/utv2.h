@@ -638,6 +638,20 @@ int utv2_bottleneck_fwd_bf16(const void* x, void* y, const void* w1, const void*
                              const float* b1, const float* s2, const float* b2, const float* s3, const float* b3, const float* ssc,
                              const float* bsc, int N, int H, int W, int C, int MID, utv2_stream_t stream);
 
+/* ---- one frozen identity BasicBlock as ONE kernel (csrc/basicblock.hip): D2 BasicBlock conv1 3x3 -> conv2 3x3 + identity, both stride 1
+ * pad 1 and 64 -> 64 channels, FrozenBN folded to scale / shift - every res2 block of R-18 / R-34 (MODEL.RESNETS.DEPTH 18 / 34 with
+ * RES2_OUT_CHANNELS 64) under MODEL.BACKBONE.FREEZE_AT 2.
+ * x, y: [N, H, W, C = 64] of the library's 16-bit type, y != x; w1, w2: [64][3][3][64] 16-bit (tap-major, channel-minor: the layout
+ * utv2_conv2d_nhwc_fwd_bf16_bits reads); s* / b*: fp32 per output channel.
+ * c1 = h16(relu(conv1(x) s1 + b1)), zero outside the image; y = h16(relu(conv2(c1) s2 + b2 + x)): fp32 accumulation and the roundings of the
+ * two-launch chain (conv, ReLU; conv, residual x, ReLU).  c1 never leaves LDS.  C != 64, y == x, a null operand or an image of more than
+ * 2^31 - 1 elements: UTV2_EARG.
+ * utv2_basicblock_supported: 1 when the kernel takes a block of C channels whose conv1 has this stride, with / without a shortcut conv
+ * ((64, 1, 0) only). */
+int utv2_basicblock_supported(int C, int stride, int has_shortcut);
+int utv2_basicblock_fwd_bf16(const void* x, void* y, const void* w1, const void* w2, const float* s1, const float* b1, const float* s2,
+                             const float* b2, int N, int H, int W, int C, utv2_stream_t stream);
+
 /* ---- two-crop data path: the pixel arithmetic of the reference's weak / strong views, on uint8 [H][W][3] images
  * in HBM, bit-exact to Pillow (which Detectron2 / torchvision / the reference call on the CPU) ------------------------------------- */
 /* detectron2 ResizeTransform.apply_image (used by ubteacher/data/dataset_mapper.py:97-99) = PIL.Image.resize(BILINEAR): Resample.c

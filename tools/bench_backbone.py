@@ -9,6 +9,10 @@
         Under `rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/bench_backbone.py kernels --trace-order` the launches run
         in a fixed order, and `python tools/bench_backbone.py table --trace DIR/.../run_kernel_trace.csv` turns the trace into the same table
         with the profiler's kernel times.
+    python tools/bench_backbone.py basicblock [--reps R --rounds N --out profiles/basicblock_kernel.json]
+        the fused frozen BasicBlock launch (csrc/basicblock.hip) against the two conv launches it replaces at the res2 shape of the benchmark
+        (8 images, 200 x 336 x 64), both 16-bit builds: device events around R launches back to back, the two versions alternating for N
+        rounds (median and range over the rounds), bytes from the shapes, achieved bytes/s.
 """
 import argparse
 import csv
@@ -23,6 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "unbiased-teacher-v2_amd"))
 
 HBM_TBS = 6.3            # achievable HBM rate (MI355X, float4 copy)
 BACKBONES = {
+    "R-18": ["MODEL.RESNETS.DEPTH", 18, "MODEL.RESNETS.RES2_OUT_CHANNELS", 64],
+    "R-34": ["MODEL.RESNETS.DEPTH", 34, "MODEL.RESNETS.RES2_OUT_CHANNELS", 64],
     "R-50": [],
     "R-101": ["MODEL.RESNETS.DEPTH", 101],
     "X-101-32x8d": ["MODEL.RESNETS.DEPTH", 101, "MODEL.RESNETS.NUM_GROUPS", 32, "MODEL.RESNETS.WIDTH_PER_GROUP", 8,
@@ -114,6 +120,60 @@ def kernels(reps, dtype):
     return rows
 
 
+BASICBLOCK_SHAPE = (8, 200, 336, 64)     # res2 of R-18 / R-34 on the padded 1344x800 canvas, 4 + 4 images
+
+
+def basicblock(reps, rounds):
+    """fused launch against the two-launch chain, alternating; bytes each must move at least: fused x + y, chain x + c1 (conv1) and
+    c1 + x + y (conv2) - weights (147 KB) and the halo re-reads from caches are not counted"""
+    import statistics
+    import torch
+    from ubteacher import hip
+    N, H, W, C = BASICBLOCK_SHAPE
+    act = N * H * W * C * 2
+    rows = []
+    for kind in ("bf16", "fp16"):
+        hip.set_h16(kind)
+        dt = hip.h16_dtype()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        x = (torch.randn(N, H, W, C, device="cuda", generator=g).relu() * 0.7).to(dt)
+        w1, w2 = [(torch.randn(C, 9 * C, device="cuda", generator=g) * 0.05).to(dt) for _ in range(2)]
+        s1, s2 = [torch.rand(C, device="cuda", generator=g) + 0.5 for _ in range(2)]
+        b1, b2 = [torch.randn(C, device="cuda", generator=g) * 0.2 for _ in range(2)]
+        y, c1, y2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+
+        def fused():
+            hip.basicblock_fwd_bf16(x, w1, w2, s1, b1, s2, b2, out=y)
+
+        def chain():
+            hip.conv2d_fwd_bf16(x, w1, scale=s1, bias=b1, relu=True, kh=3, kw=3, pad=1, out=c1)
+            hip.conv2d_fwd_bf16(c1, w2, scale=s2, bias=b2, relu=True, kh=3, kw=3, pad=1, residual=x, out=y2)
+
+        for fn in (fused, chain):
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        differing = float((y != y2).float().mean())
+        times = {"fused": [], "chain": []}
+        for _ in range(rounds):
+            for name, fn in (("fused", fused), ("chain", chain)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(1e3 * e0.elapsed_time(e1) / reps)
+        for name, nbytes in (("fused", 2 * act), ("chain", 5 * act)):
+            us = statistics.median(times[name])
+            rows.append({"op": name, "dtype": kind, "shape": list(BASICBLOCK_SHAPE), "us_median": us, "us_min": min(times[name]),
+                         "us_max": max(times[name]), "bytes": nbytes, "achieved_TBps": nbytes / us / 1e6,
+                         "flops": (2 * 9 * C * C * N * H * W) * 2, "share_of_elements_differing_from_chain": differing,
+                         "time_source": "device events, %d launches back to back, %d alternating rounds" % (reps, rounds)})
+        hip.set_h16("bf16")
+    return rows
+
+
 def _row(op, stage, n, H, W, C, G, us, source):
     b = launch_bytes(op, n, H, W, C, G)
     bound_us = b / (HBM_TBS * 1e12) * 1e6
@@ -140,7 +200,9 @@ def table(trace, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["steps", "kernels", "table"])
+    ap.add_argument("what", choices=["steps", "kernels", "table", "basicblock"])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--dtypes", default="f16,bf16")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
@@ -153,13 +215,19 @@ def main():
     a = ap.parse_args()
     if a.what == "steps":
         res = []
-        for dtype in ("f16", "bf16"):
+        for dtype in a.dtypes.split(","):
             for kind in a.models.split(","):
                 for bb in a.backbones.split(","):
                     r = step_rate(kind, bb, dtype, a.steps, a.warmup)
                     print(json.dumps(r), flush=True)
                     res.append(r)
         out = {"what": "step images/sec, 4 + 4 images of 1333x800 per step", "results": res}
+    elif a.what == "basicblock":
+        out = {"what": "fused frozen BasicBlock launch against the two conv launches it replaces, res2 of R-18 / R-34 at 4 + 4 images",
+               "results": basicblock(a.reps, a.rounds)}
+        for r in out["results"]:
+            print("%-5s %-4s %8.1f us (%.1f .. %.1f)  %.2f TB/s of the bytes its shapes require" % (
+                r["op"], r["dtype"], r["us_median"], r["us_min"], r["us_max"], r["achieved_TBps"]))
     elif a.what == "kernels":
         if a.trace_order:
             import torch

@@ -74,7 +74,7 @@ def _parse_header(path):
 
 _SIGS = _parse_header(HEADER_PATH)
 _PLAIN = {"utv2_aug_resize_workspace_bytes", "utv2_topk_rows_workspace_bytes", "utv2_groupnorm_seg_workspace_floats", "utv2_groupnorm_seg_chunks", "utv2_conv2d_wgrad_bf16_splits", "utv2_conv2d_wgrad_bf16_workspace_floats", "utv2_conv2d_bf16_supported", "utv2_conv2d_wgrad_splits", "utv2_conv2d_wgrad_workspace_floats",
-          "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
+          "utv2_nms_mpad", "utv2_nms_workspace_bytes", "utv2_bottleneck_supported", "utv2_basicblock_supported", "utv2_wgrad_fold_table_bytes", "utv2_wgrad_fold_pending",
           "utv2_coco_eval_workspace_bytes", "utv2_gconv3x3_supported", "utv2_gconv3x3_wgrad_splits",
           "utv2_gconv3x3_wgrad_workspace_floats", "utv2_bn_chunks", "utv2_groupnorm_roi_workspace_floats"}  # return a value, not a status
 
@@ -1151,6 +1151,22 @@ def bottleneck_fwd_bf16(x, w1, w2, w3, s1, b1, s2, b2, s3, b3, wsc=None, ssc=Non
 
 def bottleneck_supported(C, MID, has_shortcut):
     return bool(load().utv2_bottleneck_supported(C, MID, int(has_shortcut)))
+
+
+def basicblock_fwd_bf16(x, w1, w2, s1, b1, s2, b2, out=None):
+    """one frozen identity BasicBlock (conv1 3x3 -> conv2 3x3 + x, 64 channels, FrozenBN as scale / shift, ReLUs) in one launch
+    (utv2_basicblock_fwd_bf16): x [N, H, W, 64] 16-bit NHWC -> y of the same shape"""
+    N, H, W, C = x.shape
+    assert x.dtype == h16_dtype() and w1.dtype == w2.dtype == h16_dtype()
+    assert tuple(w1.shape) == (C, 9 * C) and tuple(w2.shape) == (C, 9 * C)
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    call("utv2_basicblock_fwd_bf16", _p(x), _p(out), _p(w1), _p(w2), _p(s1), _p(b1), _p(s2), _p(b2), N, H, W, C, _stream())
+    return out
+
+
+def basicblock_supported(C, stride, has_shortcut):
+    return bool(load().utv2_basicblock_supported(C, int(stride), int(has_shortcut)))
 
 
 def conv2d_dgrad_bf16(dy, wt16, in_shape, stride, pad, kh, kw, out=None, out_dtype=None, mask=None, residual=None, post_mask=None,

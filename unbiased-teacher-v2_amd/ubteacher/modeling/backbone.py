@@ -1,6 +1,6 @@
-"""ResNet-50 / 101 / 152 and ResNeXt + FPN on the HIP conv path.
+"""ResNet-18 / 34 / 50 / 101 / 152 and ResNeXt + FPN on the HIP conv path.
 
-Behavioural spec: Detectron2 v0.6 ResNet (DEPTH, NUM_GROUPS, WIDTH_PER_GROUP, STRIDE_IN_1X1, FrozenBN, FREEZE_AT) and FPN
+Behavioural spec: Detectron2 v0.6 ResNet (DEPTH, RES2_OUT_CHANNELS, NUM_GROUPS, WIDTH_PER_GROUP, STRIDE_IN_1X1, FrozenBN, FREEZE_AT) and FPN
 [D2-recall, SURVEY.md appendix C]; FCOS top block: reference ubteacher/modeling/backbone/fpn.py:11-78
 (P6 = conv3x3 s2 (P5), P7 = conv3x3 s2 (relu(P6))).  State-dict keys follow Detectron2's
 (`bottom_up.stem.conv1.weight`, `bottom_up.res3.0.conv1.norm.running_mean`, `fpn_lateral3.weight`,
@@ -112,25 +112,46 @@ class Bottleneck:
         return ops.bottleneck(self, x)
 
 
-# Detectron2 build_resnet_backbone: blocks per stage of the bottleneck depths
-RESNET_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+class BasicBlock:
+    """Detectron2 BasicBlock (R-18 / R-34): conv1 3x3 (carries the stride) + FrozenBN + ReLU, conv2 3x3 + FrozenBN, a 1x1 shortcut conv +
+    FrozenBN only where the channel count changes (the first block of res3 / res4 / res5), relu(conv2 + shortcut)."""
+
+    def __init__(self, store, folder, prefix, cin, cout, stride, trainable):
+        self.conv1 = _conv_bn(store, folder, prefix + ".conv1", cin, cout, 3, stride, 1, True, trainable)
+        self.conv2 = _conv_bn(store, folder, prefix + ".conv2", cout, cout, 3, 1, 1, True, trainable)  # relu after add
+        self.shortcut = None
+        if cin != cout:
+            self.shortcut = _conv_bn(store, folder, prefix + ".shortcut", cin, cout, 1, stride, 0, False, trainable)
+
+    def __call__(self, x):
+        return ops.basic_block(self, x)
+
+
+# Detectron2 build_resnet_backbone: blocks per stage; 18 / 34 are built from BasicBlock, the others from Bottleneck
+RESNET_DEPTHS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+BASIC_BLOCK_DEPTHS = (18, 34)
 
 
 def resnet_spec(cfg):
     """(blocks per stage, groups, width per group, stride_in_1x1) of cfg.MODEL.RESNETS, or NotImplementedError naming the key of a
-    configuration this backbone does not build (it would otherwise be built as something else without a word)."""
+    configuration this backbone does not build (it would otherwise be built as something else without a word).  The BasicBlock depths
+    (cfg.MODEL.RESNETS.DEPTH in BASIC_BLOCK_DEPTHS) come with RES2_OUT_CHANNELS 64, one group of width 64 (Detectron2's assertions)."""
     r = cfg.MODEL.RESNETS
     if r.DEPTH not in RESNET_DEPTHS:
-        raise NotImplementedError("MODEL.RESNETS.DEPTH %r: only the bottleneck depths %s are built (BasicBlock depths 18 / 34 are not)"
-                                  % (r.DEPTH, sorted(RESNET_DEPTHS)))
+        raise NotImplementedError("MODEL.RESNETS.DEPTH %r: only the depths %s are built" % (r.DEPTH, sorted(RESNET_DEPTHS)))
+    basic = r.DEPTH in BASIC_BLOCK_DEPTHS
+    if basic and r.RES2_OUT_CHANNELS != 64:
+        raise NotImplementedError("MODEL.RESNETS.DEPTH %r is built from BasicBlocks and needs MODEL.RESNETS.RES2_OUT_CHANNELS 64 (got %r)"
+                                  % (r.DEPTH, r.RES2_OUT_CHANNELS))
     if any(bool(d) for d in r.DEFORM_ON_PER_STAGE):
         raise NotImplementedError("MODEL.RESNETS.DEFORM_ON_PER_STAGE %r: deformable convolutions are not built" % (list(r.DEFORM_ON_PER_STAGE),))
     if r.RES5_DILATION != 1:
         raise NotImplementedError("MODEL.RESNETS.RES5_DILATION %r: only 1 is built" % (r.RES5_DILATION,))
     if r.NORM != "FrozenBN":
         raise NotImplementedError("MODEL.RESNETS.NORM %r: only FrozenBN is built" % (r.NORM,))
-    if r.RES2_OUT_CHANNELS != 256:
-        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS %r: only 256 is built" % (r.RES2_OUT_CHANNELS,))
+    if not basic and r.RES2_OUT_CHANNELS != 256:
+        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS %r: the bottleneck depths are built with 256 only (64 goes with DEPTH 18 / 34)"
+                                  % (r.RES2_OUT_CHANNELS,))
     if r.STEM_OUT_CHANNELS != 64:
         raise NotImplementedError("MODEL.RESNETS.STEM_OUT_CHANNELS %r: only 64 is built" % (r.STEM_OUT_CHANNELS,))
     if cfg.MODEL.FPN.NORM != "":
@@ -138,17 +159,22 @@ def resnet_spec(cfg):
     if cfg.MODEL.FPN.FUSE_TYPE != "sum":
         raise NotImplementedError("MODEL.FPN.FUSE_TYPE %r: only 'sum' is built" % (cfg.MODEL.FPN.FUSE_TYPE,))
     groups, wpg = int(r.NUM_GROUPS), int(r.WIDTH_PER_GROUP)
+    if basic and groups != 1:
+        raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS %r: DEPTH %r (BasicBlocks) takes 1 only" % (groups, r.DEPTH))
+    if basic and wpg != 64:
+        raise NotImplementedError("MODEL.RESNETS.WIDTH_PER_GROUP %r: DEPTH %r (BasicBlocks) takes 64 only" % (wpg, r.DEPTH))
     if groups > 1 and wpg % 4:
         raise NotImplementedError("MODEL.RESNETS.WIDTH_PER_GROUP %r: the grouped conv kernels take a multiple of 4 channels per group" % wpg)
     return RESNET_DEPTHS[r.DEPTH], groups, wpg, bool(r.STRIDE_IN_1X1)
 
 
 class ResNet:
-    """Detectron2 build_resnet_backbone for bottleneck ResNets / ResNeXts: DEPTH 50 / 101 / 152, NUM_GROUPS x WIDTH_PER_GROUP bottleneck
-    width of res2 (doubling per stage; only conv2 is grouped), STRIDE_IN_1X1, FrozenBN, FREEZE_AT."""
+    """Detectron2 build_resnet_backbone: bottleneck ResNets / ResNeXts (DEPTH 50 / 101 / 152, NUM_GROUPS x WIDTH_PER_GROUP bottleneck
+    width of res2, doubling per stage; only conv2 is grouped; STRIDE_IN_1X1) and, with basic=True, the BasicBlock ResNets (DEPTH 18 / 34).
+    Stage output widths are res2_out * 2^i.  FrozenBN, FREEZE_AT."""
 
     def __init__(self, store, folder, prefix, out_features, freeze_at=2, num_blocks=(3, 4, 6, 3), groups=1, width_per_group=64,
-                 stride_in_1x1=True):
+                 stride_in_1x1=True, basic=False, res2_out=256):
         self.out_features = out_features
         # stem on the NHWC4 image: [64][7*7*4 -> padded to 208]
         def stem_init(t):
@@ -161,18 +187,22 @@ class ResNet:
         self.stem_bn = folder.add(FrozenBN(store, prefix + ".stem.conv1.norm", 64))
         self.stem = ops.Conv(self.stem_w, 4, 64, 7, 2, 3, bn=self.stem_bn, relu=True, trainable=stem_train, kred=208)
         self.stages = []
+        self.channels = {}
         cin = 64
         for si, nblocks in enumerate(num_blocks):
-            name, mid, cout = "res%d" % (si + 2), groups * width_per_group * 2 ** si, 256 * 2 ** si
+            name, mid, cout = "res%d" % (si + 2), groups * width_per_group * 2 ** si, res2_out * 2 ** si
             trainable = freeze_at < si + 2
             blocks = []
             for b in range(nblocks):
                 stride = 2 if (b == 0 and name != "res2") else 1
-                blocks.append(Bottleneck(store, folder, "%s.%s.%d" % (prefix, name, b), cin, cout, mid, stride, trainable, groups,
-                                         stride_in_1x1))
+                bp = "%s.%s.%d" % (prefix, name, b)
+                if basic:
+                    blocks.append(BasicBlock(store, folder, bp, cin, cout, stride, trainable))
+                else:
+                    blocks.append(Bottleneck(store, folder, bp, cin, cout, mid, stride, trainable, groups, stride_in_1x1))
                 cin = cout
             self.stages.append((name, blocks, trainable))
-        self.channels = {"res2": 256, "res3": 512, "res4": 1024, "res5": 2048}
+            self.channels[name] = cout
         self.strides = {"res2": 4, "res3": 8, "res4": 16, "res5": 32}
 
     def __call__(self, x4):
@@ -220,7 +250,9 @@ def ResNet50(store, folder, prefix, out_features, freeze_at=2):
 
 def build_resnet(cfg, store, folder, prefix):
     blocks, groups, wpg, s1x1 = resnet_spec(cfg)
-    return ResNet(store, folder, prefix, cfg.MODEL.RESNETS.OUT_FEATURES, cfg.MODEL.BACKBONE.FREEZE_AT, blocks, groups, wpg, s1x1)
+    r = cfg.MODEL.RESNETS
+    return ResNet(store, folder, prefix, r.OUT_FEATURES, cfg.MODEL.BACKBONE.FREEZE_AT, blocks, groups, wpg, s1x1,
+                  basic=r.DEPTH in BASIC_BLOCK_DEPTHS, res2_out=int(r.RES2_OUT_CHANNELS))
 
 
 def _conv_bias(store, prefix, cin, cout, k, stride, pad, init, relu=False):
@@ -244,9 +276,10 @@ class FPN:
             self.output[f] = _conv_bias(store, "backbone.fpn_output%d" % stage, oc, oc, 3, 1, 1, _xavier_init)
         # Gradient pre-masking (ops.premask_on): a stage output is consumed by the next block / next stage's first block and by this
         # stage's lateral only, and all of them mask the gradient they return by (output > 0) in their dgrad epilogue - so the fused
-        # bottlenecks of the trainable stages skip the mask pass at the top of their backward.
+        # bottlenecks of the trainable stages skip the mask pass at the top of their backward.  BasicBlock stages (R-18 / R-34) run as
+        # plain ops.Conv nodes, each of which masks its own incoming gradient: nothing is pre-masked for them, blocks or laterals.
         for name, blocks, trainable in self.bottom_up.stages:
-            if trainable:
+            if trainable and all(isinstance(blk, Bottleneck) for blk in blocks):
                 for blk in blocks:
                     blk.input_relu = True
                     blk.grad_premasked = True

@@ -909,6 +909,26 @@ def bottleneck(block, x):
     return block.conv3(out, residual=sc)
 
 
+def basic_block(block, x):
+    """A D2 BasicBlock (R-18 / R-34): relu(conv2(relu(conv1(x))) + shortcut(x) or x).  A frozen 64-channel identity block under AMP (every
+    res2 block under FREEZE_AT 2; the teacher's too) keeps nothing for a backward and runs as one kernel with c1 in LDS
+    (csrc/basicblock.hip); everything else is the per-conv graph, conv2 with the residual and the ReLU in its epilogue."""
+    convs = [c for c in (block.conv1, block.conv2, block.shortcut) if c is not None]
+    if (amp() and x.dtype == hip.h16_dtype() and x.is_contiguous() and _fused_frozen_block_on()
+            and (not torch.is_grad_enabled() or not any(c.trainable for c in convs)) and not x.requires_grad
+            and block.conv1.k == 3 and block.conv2.k == 3 and block.conv1.pad == 1 and block.conv2.pad == 1 and block.conv2.stride == 1
+            and block.conv1.cin == block.conv1.cout == block.conv2.cin == block.conv2.cout == x.shape[3]
+            and all(c.bn is not None and c.bias is None and c.groups == 1 and c.use_bf16() for c in convs)
+            and block.conv1.relu and block.conv2.relu
+            and x.shape[1] * x.shape[2] * x.shape[3] < 2 ** 31     # the kernel's 32-bit element offsets inside one image
+            and hip.basicblock_supported(block.conv1.cin, block.conv1.stride, block.shortcut is not None)):
+        st = block.conv1.w.store
+        (s1, b1), (s2, b2) = block.conv1.scale_shift(), block.conv2.scale_shift()
+        return hip.basicblock_fwd_bf16(x, st.bf16(block.conv1.w), st.bf16(block.conv2.w), s1, b1, s2, b2)
+    sc = block.shortcut(x) if block.shortcut is not None else x
+    return block.conv2(block.conv1(x), residual=sc)
+
+
 class _StemFn(torch.autograd.Function):
     """A TRAINABLE ResNet stem (MODEL.BACKBONE.FREEZE_AT < 1; D2 BasicStem: 7x7 stride-2 conv + FrozenBN + ReLU + 3x3 stride-2 max pool)
     on the fp32 NHWC4 image as one autograd node: the backward routes the pooled gradient to the first maximum of every window and
