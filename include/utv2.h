@@ -756,6 +756,25 @@ int utv2_bn_bwd_apply(const void* dy, const void* y, const void* x, void* dx, in
                       const float* gamma, const double* sums, float* dgamma, float* dbeta, int64_t P, int C, int nlevels, int nsets,
                       const int* set_row0_host, const int* set_rows_host, const int* set_level_host, int count_mul, utv2_stream_t stream);
 
+/* ---- TEST.PRECISE_BN for the BatchNorm towers (csrc/bn_precise.hip): population statistics estimated on the device --------------------
+ * state: fp64 [nlevels][3][C] per layer = pop_mean | pop_sq (population mean of squares) | num (images seen, carried per channel);
+ * zero-initialised by the caller.  The set tables are those of the section above; set_images_host[s] = B, the images of set s's call.
+ *   precise_update  for the sets in order, from moments[s] = [mean, mean of squares] (utv2_bn_reduce with divide, or the mean of
+ *                   count_mul ranks' outputs): var = max(moments[s][1] - mean^2, 0), v = var * n / (n - 1) with n = set_rows[s] *
+ *                   count_mul (biased_running: v = var) - what utv2_bn_finalize mode 0 moves the running variance by - then
+ *                   [fvcore-recall]  num += B; q = mean^2 + v * (B - 1) / B; pop_mean += (mean - pop_mean) * (B / num);
+ *                   pop_sq += (q - pop_sq) * (B / num).  Also writes mean / rstd / scale [nsets][C] exactly as utv2_bn_finalize mode 0
+ *                   does (bit for bit), for utv2_bn_apply_relu.  No running buffer is read or written.  One thread per channel, no atomics.
+ *                   UTV2_EARG: C % 4 != 0, n < 2, B < 1, a bad set table, a null pointer.
+ *   precise_commit  state: [nlayers][nlevels][3][C]; running_mean_host / running_var_host: HOST arrays of nlayers device pointers to
+ *                   [nlevels][C] fp32.  running_mean = fp32(pop_mean), running_var = fp32(pop_sq - pop_mean^2), one rounding each; a
+ *                   level whose num is 0 keeps its buffers. */
+int utv2_bn_precise_update(const double* moments, const float* gamma, double* state, double* mean, double* rstd, double* scale, int C,
+                           int nlevels, int nsets, const int* set_rows_host, const int* set_level_host, const int* set_images_host,
+                           double eps, int count_mul, int biased_running, utv2_stream_t stream);
+int utv2_bn_precise_commit(const double* state, float* const* running_mean_host, float* const* running_var_host, int nlayers, int nlevels,
+                           int C, utv2_stream_t stream);
+
 /* ---- test-time augmentation (TEST.AUG; Detectron2 GeneralizedRCNNWithTTA._inverse_augmented_boxes and the head of _merge_detections
  * [D2-recall]): the detections of the V views of ONE image, each in its view's pixel frame, brought back to the original image and
  * packed view-major into one candidate set for utv2_nms_batched.

@@ -29,6 +29,7 @@ from ..utils import comm
 from ..data.synthetic import SyntheticTwoCropLoader
 from ..checkpoint import DetectionTSCheckpointer
 from .step_gc import StepGC
+from . import precise_bn
 
 
 class ArenaSGD:
@@ -414,8 +415,20 @@ class _TrainerBase:
                                                     grad_scaler=AmpScalerState(self))
         self._setup_grad_sync()
         self.sync_replicas()
+        # TEST.PRECISE_BN (reference build_hooks, engine/trainer.py:503-521 / :974-992): a hook only when the key is on and the student has
+        # BatchNorm layers (the FCOS "BN" / "SyncBN" towers; never a Faster-RCNN model)
+        self._precise_bn = precise_bn.build_hook(cfg, self.model, self._build_precise_bn_loader)
 
     _dp_single_rank = False
+    _precise_bn = None
+
+    def _build_precise_bn_loader(self):
+        """the hook's own train loader: DATALOADER.NUM_WORKERS 0, built once, at the hook's first update"""
+        c = self.cfg.clone()
+        c.defrost()
+        c.DATALOADER.NUM_WORKERS = 0
+        c.freeze()
+        return self.build_train_loader(c)
 
     @property
     def data_parallel(self):
@@ -491,6 +504,12 @@ class _TrainerBase:
                     lr = float(self.optimizer.param_groups[0]["lr"])     # the rate this step ran at (hooks.LRScheduler logs it before stepping)
                     self.scheduler.step()
                     step_gc.tick()
+                    # hooks.PreciseBN stands in front of the checkpointer and the EvalHooks: what is saved and evaluated at this
+                    # iteration holds the re-estimated statistics (its time is not iteration time)
+                    if self._precise_bn is not None:
+                        t_acc += time.perf_counter() - t_mark
+                        self._precise_bn.after_step(self.iter, max_iter)
+                        t_mark = time.perf_counter()
                     period = self.cfg.SOLVER.CHECKPOINT_PERIOD
                     if comm.is_main_process() and period > 0 and (self.iter + 1) % period == 0:
                         self.checkpointer.save("model_{:07d}".format(self.iter), iteration=self.iter)

@@ -1715,6 +1715,16 @@ class BnSets:
         self.p_row0, self.p_rows, self.p_level = (ctypes.cast(a, c_p) for a in (self.row0, self.rows, self.level))
         self.end = max(r0 + n for r0, n, _ in sets)
         self.nchunks = sum((n + 63) // 64 for _, n, _ in sets)     # == utv2_bn_chunks
+        self.images = self.p_images = None     # set_images(): B per set, read by bn_precise_update only
+
+    def set_images(self, images):
+        """images of the forward call each set belongs to (the batch size B of the precise-BN estimator)"""
+        images = [int(b) for b in images]
+        if len(images) != self.n or min(images) < 1:
+            raise ValueError("BatchNorm: %r images for %d statistic sets" % (images, self.n))
+        self.images = _iarr(images)
+        self.p_images = ctypes.cast(self.images, c_p)
+        return self
 
     def check_training(self, count_mul=1):
         for _, n, l in self.sets:
@@ -1792,3 +1802,35 @@ def bn_bwd_apply(dy, y, x, mean, rstd, gamma, sums, dgamma, dbeta, sets, count_m
     call("utv2_bn_bwd_apply", _p(dy), _p(y), _p(x), _p(dx), _same_dt(dy, y, x), _p(mean), _p(rstd), _p(gamma), _p(sums), _p(dgamma), _p(dbeta),
          P, C, sets.nlevels, sets.n, sets.p_row0, sets.p_rows, sets.p_level, int(count_mul), _stream())
     return dx
+
+
+# ---- TEST.PRECISE_BN: population statistics of the BatchNorm towers (csrc/bn_precise.hip) ----------------------------------------------
+def bn_precise_state(nlayers, nlevels, C, device):
+    """the estimator's fp64 state of a head, zeroed: [nlayers, nlevels, 3, C] = pop_mean | pop_sq | num per (layer, level, channel)"""
+    return torch.zeros((nlayers, nlevels, 3, C), dtype=torch.float64, device=device)
+
+
+def bn_precise_update(moments, gamma, state, sets, eps=1e-5, count_mul=1, biased_running=False):
+    """One layer's statistic sets (in order) into its estimator state [L, 3, C] fp64, from `moments` [S, 2, C] fp64 (bn_stats, or the mean of
+    count_mul ranks' moments) and sets.images (B per set).  -> (mean, rstd, scale) [S, C] fp64, bit for bit what bn_finalize(training=True)
+    returns for the same moments.  No running buffer is touched."""
+    L, C = gamma.shape
+    assert L == sets.nlevels and sets.p_images is not None, "BnSets.set_images() names B per set"
+    assert gamma.dtype == torch.float32 and C % 4 == 0
+    assert state.dtype == torch.float64 and tuple(state.shape) == (L, 3, C) and state.is_contiguous()
+    assert moments.dtype == torch.float64 and tuple(moments.shape) == (sets.n, 2, C)
+    sets.check_training(count_mul)
+    mean, rstd, scale = (torch.empty((sets.n, C), dtype=torch.float64, device=gamma.device) for _ in range(3))
+    call("utv2_bn_precise_update", _p(moments), _p(gamma), _p(state), _p(mean), _p(rstd), _p(scale), C, L, sets.n, sets.p_rows, sets.p_level,
+         sets.p_images, float(eps), int(count_mul), int(bool(biased_running)), _stream())
+    return mean, rstd, scale
+
+
+def bn_precise_commit(state, running_means, running_vars):
+    """running_mean = fp32(pop_mean), running_var = fp32(pop_sq - pop_mean^2) for every level of every layer, one launch.
+    state [nlayers, L, 3, C] fp64; running_means / running_vars: nlayers [L, C] fp32 tensors each."""
+    K, L, three, C = state.shape
+    assert three == 3 and state.dtype == torch.float64 and len(running_means) == len(running_vars) == K
+    assert all(t.dtype == torch.float32 and tuple(t.shape) == (L, C) for t in list(running_means) + list(running_vars))
+    pm, pv = ((ctypes.c_void_p * K)(*[_p(t) for t in ts]) for ts in (running_means, running_vars))
+    call("utv2_bn_precise_commit", _p(state), ctypes.cast(pm, c_p), ctypes.cast(pv, c_p), K, L, C, _stream())

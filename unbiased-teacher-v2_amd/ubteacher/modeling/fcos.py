@@ -449,6 +449,31 @@ class FCOSHead:
             return norm(t, meta)
         return norm(t, meta, calls)
 
+    def bn_chains(self):
+        """the tower layers as chains of (conv, BatchNorm) in forward order: [(layers, index of the chain whose output feeds it or None)]"""
+        if self.paired:
+            return [(self.towers["pair"], None)]
+        share = self.towers["share"]
+        return [(share, None)] + [(self.towers[k], 0) for k in ("cls", "bbox")]
+
+    @torch.no_grad()
+    def bn_statistics_pass(self, big, meta, state, calls=None):
+        """The forward TEST.PRECISE_BN needs of a NORM "BN" / "SyncBN" head and nothing else: per tower depth the conv, the two statistics
+        launches, hip.bn_precise_update into state[i] (i = the layer's place in bn_layers; state: hip.bn_precise_state) and the
+        normalisation with the batch statistics, ending at the last BatchNorm of each tower (whose output nobody reads: no apply pass).
+        No prediction convs, Scale, losses or targets; no autograd nodes, so no weight-gradient work is queued."""
+        assert self.bn_layers and tuple(state.shape[:2]) == (len(self.bn_layers), self.num_levels)
+        index = {id(bn): i for i, bn in enumerate(self.bn_layers)}
+        chains = self.bn_chains()
+        outs = []
+        for k, (layers, src) in enumerate(chains):
+            t = big if src is None else outs[src]
+            feeds = any(s == k and ls for ls, s in chains)      # a later chain starts from this one's output
+            for j, (conv, bn) in enumerate(layers):
+                t = conv(t, meta=meta)
+                t = bn.statistics_pass(t, meta, calls, state[index[id(bn)]], need_output=feeds or j + 1 < len(layers))
+            outs.append(t)
+
     def __call__(self, big, meta, calls=None):
         """big: level-first [P, C] features of all levels; ONE launch per conv for all levels.
         calls (BN towers): images per forward call of the reference in this batch, in order (fused student pass: [labeled, unlabeled]).
@@ -839,8 +864,7 @@ class FCOS:
         self.fcos_outputs.training = mode
         self.fcos_head.train(mode)
 
-    def forward(self, image_sizes, features, gt_instances=None, output_raw=False, nms_method="cls_n_ctr",
-                ignore_near=False, branch="labeled"):
+    def _level_first(self, features):
         feats = [features[f] for f in self.in_features]
         level_hw = [(f.shape[1], f.shape[2]) for f in feats]
         lf = features.get("_levelfirst")
@@ -849,6 +873,16 @@ class FCOS:
         else:  # features that do not share a level-first buffer: build one (copy)
             meta = ops.LevelMeta(feats[0].shape[0], level_hw)
             big = torch.cat([f.reshape(-1, f.shape[-1]) for f in feats], dim=0)
+        return big, meta, level_hw
+
+    def bn_statistics_pass(self, features, state, calls=None):
+        """the head's statistics-only forward (FCOSHead.bn_statistics_pass) on the FPN features; calls: images per forward call"""
+        big, meta, _ = self._level_first(features)
+        self.fcos_head.bn_statistics_pass(big, meta, state, None if calls is None or len(calls) < 2 else calls)
+
+    def forward(self, image_sizes, features, gt_instances=None, output_raw=False, nms_method="cls_n_ctr",
+                ignore_near=False, branch="labeled"):
+        big, meta, level_hw = self._level_first(features)
         head_out = self.fcos_head(big, meta)
         raw_output = RawOutput(head_out, level_hw, image_sizes, self.fpn_strides, self.fcos_outputs.reg_max)
         results = {}

@@ -79,6 +79,15 @@ class PseudoProposalNetwork(ArenaModel):
 
     __call__ = forward
 
+    @torch.no_grad()
+    def bn_statistics_pass(self, call_inputs, state):
+        """TEST.PRECISE_BN (engine/precise_bn.py): backbone, FPN and the towers up to their last BatchNorm on ONE batch made of the
+        image lists in call_inputs (one list per forward call of the reference, equal padded canvases); each list is one statistic
+        set per level, accumulated into `state` (hip.bn_precise_state).  Nothing is returned and no running buffer is written."""
+        both = [x for c in call_inputs for x in c]
+        features, _ = self._features(both)
+        self.proposal_generator.bn_statistics_pass(features, state, tuple(len(c) for c in call_inputs) if len(call_inputs) > 1 else None)
+
     def padded_canvas(self, batched_inputs):
         """(H, W) the batch is zero-padded to by preprocess_image (ImageList.from_tensors with size_divisibility)."""
         d = self.backbone.size_divisibility

@@ -1196,13 +1196,14 @@ class BatchNormReLU:
         if st is None:
             if sum(calls) != meta.N or min(calls) < 1:
                 raise ValueError("BatchNorm: forward calls of %r images in a batch of %d" % (calls, meta.N))
-            rows = []
+            rows, images = [], []
             for l, ((h, w), (r0, _)) in enumerate(zip(meta.level_hw, meta.rows)):
                 i0 = 0
                 for n in calls:
                     rows.append((r0 + i0 * h * w, n * h * w, l))
+                    images.append(n)
                     i0 += n
-            st = self._sets[key] = hip.BnSets(rows, len(meta.level_hw))
+            st = self._sets[key] = hip.BnSets(rows, len(meta.level_hw)).set_images(images)
         return st
 
     def world(self):
@@ -1234,6 +1235,30 @@ class BatchNormReLU:
             mean, rstd, scale = hip.bn_finalize(moments, self.gamma.t, self.running_mean.t, self.running_var.t, st, self.eps, self.momentum,
                                                 training=True, count_mul=W, biased_running=W > 1)
         return hip.bn_apply_relu(x, mean, scale, self.beta.t, st), mean, rstd
+
+    @torch.no_grad()
+    def statistics_pass(self, x, meta, calls, state, need_output=True):
+        """One training-mode forward call of TEST.PRECISE_BN (engine/precise_bn.py): the batch moments of every statistic set go into the
+        layer's fp64 estimator state [L, 3, C] (hip.bn_precise_update, one launch in the place of bn_finalize) and the activation is
+        normalised with the batch statistics, as in training.  The running buffers are neither read nor written and no autograd node is
+        built; num_batches_tracked advances as in any training call.  need_output False (the last BatchNorm of a tower: nothing reads
+        its output) skips the apply pass and returns None.  No device-to-host read."""
+        st = self.sets(meta, calls)
+        W = 1
+        if self.sync:
+            from .utils import comm
+            W = comm.get_world_size()
+        st.check_training(W)
+        if self.count_calls:
+            self.counter.value += len(calls) if calls is not None else 1
+        if not x.is_contiguous():
+            x = x.contiguous()
+        moments = hip.bn_stats(x, st)
+        if W > 1:   # [D2-recall] NaiveSyncBatchNorm's moments, as in _fwd; B stays the local image count
+            from .utils import comm
+            moments = comm.reduce_sum(moments) / W
+        mean, _, scale = hip.bn_precise_update(moments, self.gamma.t, state, st, self.eps, count_mul=W, biased_running=W > 1)
+        return hip.bn_apply_relu(x, mean, scale, self.beta.t, st) if need_output else None
 
 
 class _BNFn(torch.autograd.Function):
