@@ -10,7 +10,8 @@ COCOEvaluator / pycocotools - neither is in the reference tree nor installed, so
   * per category / area range, detections of all images are merged by score, precision is made monotonically
     non-increasing from the right and sampled at the 101 recall points 0, 0.01, ..., 1;
   * AP = mean over (IoU thresholds, recall points, categories with ground truth); AP50 / AP75 fix the threshold;
-    APs / APm / APl restrict the area to (0, 32^2), [32^2, 96^2), [96^2, inf).
+    APs / APm / APl restrict the area to the closed ranges [0, 32^2], [32^2, 96^2], [96^2, 1e10] (an area outside
+    `area < lo or area > hi` is ignored, so a box of area exactly 32^2 counts as small and as medium).
 """
 import numpy as np
 
